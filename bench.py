@@ -6,13 +6,17 @@ steps with template-projection physics correction - over one batch of synthetic 
 (BASELINE.json configs[1]: crop_size=256 / atom_crop_size=2048, 64 diffusion samples,
 medium model, fp32).  Metric: poses/sec, whole job.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: launched by torch.distributed.run, one rank per GPU; samples shard across ranks
      with no data-path collective, one RCCL gather of the poses at the end of every step)
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-"roofline" for the dominant kernel (live HIP-event timing of its launches in an
-instrumented pass) and "cpu_baseline" (the CPU oracle timed on the host cores, N=1 only).
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up, W warm-up
+calls, K timed calls (`ms_per_step` = milliseconds per timed call), the outputs of the last
+timed call written as DIR/<name>.npy when --dump-outputs is given, the line.
+--full adds the side measurements: "roofline" for the dominant kernel (live HIP-event timing
+of its launches in an instrumented pass), "extra" (other sample counts, screening flow, graph
+cache, MMFF branch, bf16 x 6 fallback, the cfg2 crop) and "cpu_baseline" (the CPU oracle timed
+on the host cores, N=1 only); --no-roofline / --no-extra / --no-cpu-baseline drop one of them.
 """
 import argparse
 import json
@@ -56,15 +60,25 @@ def parse():
     ap.add_argument("--model", default="medium")
     ap.add_argument("--cfg", default="cfg1", choices=["cfg1", "cfg2", "small"])
     ap.add_argument("--no-physics", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements (roofline pass, extra configurations, "
+                                                        "CPU baseline); a plain run times the headline call only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the poses of the last timed call (float32, what the caller receives) as DIR/poses.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline", default="full", choices=["full", "quick"],
-                    help="full: B = 1 measured with 3 complete oracle calls (about 3 minutes of host time); quick: extrapolated only")
+    ap.add_argument("--cpu-baseline", default="b1", choices=["b1", "full", "quick"],
+                    help="b1: B = 1 measured with complete oracle calls, B = 20 extrapolated and labelled (about 4 minutes of host "
+                         "time); full: B = 20 also measured with one complete call (5 - 6 minutes more); quick: extrapolated only")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the B=1 / B=20 / cfg2 / MMFF / screening side measurements")
     ap.add_argument("--launch-log", default=None, help="write the GEMM / attention launch sequence (symbol, shape) of the timed "
                                                        "calls as JSON (tools/pmc_report.py joins it with rocprofv3 dispatches)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:           # a plain run: the headline call only
+        args.no_roofline = args.no_extra = args.no_cpu_baseline = True
+    return args
 
 
 def make_crop(name, device):
@@ -128,9 +142,10 @@ def cpu_baseline(cfg, P, batch, confs, args):
     """the CPU oracle (torch CPU fp32, all usable cores) on the same synthetic crop, seeded weights and
     physics branch (template projection, 40 conformers, factor 6).
     B = 1 is MEASURED by the book: 2 timed COMPLETE calls (conditioning trunk + all `diffusion_steps` steps inside the timed region;
-    2-step calls as warm-up), median - `value`, `extrapolated: false`.  B = 20 (the demo's samples per round): ONE complete call,
-    measured (round 6; 4 - 6 minutes).  --cpu-baseline quick skips the complete calls: both rows are then labelled extrapolations
-    (trunk timed on its own, the loop through 2-step sampler calls, call = t_trunk + steps * t_step) and `value` says so."""
+    2-step calls as warm-up), median - `value`, `extrapolated: false`.  B = 20 (the demo's samples per round): labelled extrapolation
+    (trunk timed on its own, the loop through 2-step sampler calls, call = t_trunk + steps * t_step); with --cpu-baseline full ONE
+    complete call, measured (4 - 6 minutes more, beyond the 10 minutes a --full run is given).  --cpu-baseline quick skips the complete
+    calls: both rows are then labelled extrapolations and `value` says so."""
     import statistics
     sys.path.insert(0, os.path.join(REPO, "oracle"))
     import physdock_oracle as orc
@@ -164,7 +179,7 @@ def cpu_baseline(cfg, P, batch, confs, args):
             t_step = statistics.median(ts[1:])
             by_b[str(B)] = {"poses_per_s": B / (t_trunk + n * t_step), "t_step_s": t_step, "extrapolated": True}
         full = full20 = None
-        if args.cpu_baseline == "full":
+        if args.cpu_baseline in ("b1", "full"):
             n_noisy = int((orc.karras_noise_schedule(n, p=1000)[:-1] > 1.0).sum())
             tf = []
             for rep in range(2):                               # complete calls: trunk + n steps, nothing reused (the 2-step calls above were the warm-up)
@@ -175,6 +190,7 @@ def cpu_baseline(cfg, P, batch, confs, args):
             full = statistics.median(tf)
             by_b["1"] = {"poses_per_s": 1.0 / full, "call_s": full, "calls_timed": 2, "call_times_s": [round(t, 2) for t in tf],
                          "extrapolated": False, "extrapolated_estimate_poses_per_s": by_b["1"]["poses_per_s"], "t_step_s": by_b["1"]["t_step_s"]}
+        if args.cpu_baseline == "full":
             # B = 20, the demo's samples per round (BASELINE.md section 3 asks for B in {1, 20}): ONE complete call, measured (round 6;
             # 4 - 6 minutes of the host cores - the 2-step calls above were its warm-up)
             noise = draws(20, n, n_noisy, 20)
@@ -318,6 +334,23 @@ class LaunchTimer:
         return sorted(out, key=lambda d: -d["total_s"])
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32, 64 MB in all at most - an array over its share of that keeps a
+    fixed, seeded sample of its rows (leading dimension, in order); at the benchmark's shapes nothing is sampled"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > share:
+            keep = max(1, share // max(a.nbytes // a.shape[0], 1))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 class _DryRunSampler:
     """stand-in for PhysDock on the CPU (PD_BENCH_DRYRUN): poses are a deterministic function of (seed, global sample id), as the
     Philox-keyed sampler's are, so the rank-block checks of the real run apply unchanged"""
@@ -338,9 +371,11 @@ def main():
         if torch.cuda.device_count() < args.gpus and os.environ.get("PD_BENCH_DRYRUN") != "1":
             sys.exit(f"bench.py --gpus {args.gpus}: only {torch.cuda.device_count()} GPU(s) visible on this node")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+        # (a fresh child process, not an exec of this one: device_count() above may already have initialised the runtime here)
+        import subprocess
+        sys.exit(subprocess.call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                                   "--master-addr", "127.0.0.1", "--master-port", os.environ.get("MASTER_PORT", "29511"),
-                                  os.path.abspath(__file__)] + sys.argv[1:])
+                                  os.path.abspath(__file__)] + sys.argv[1:]))
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local = int(os.environ.get("LOCAL_RANK", 0))
@@ -429,6 +464,8 @@ def main():
         assert torch.equal(gathered[0], x), "rank 0's own block changed in the gather"
         assert all(not torch.equal(gathered[0], gathered[r]) for r in range(1, world)), \
             "rank blocks are identical: sample_offset did not separate the ranks' Philox streams"
+    if args.dump_outputs and rank == 0:      # what the caller of the timed path receives from its last call (the whole node's poses)
+        dump_outputs(args.dump_outputs, {"poses": torch.cat(gathered) if dist else x})
     poses = B * world * args.steps
     value = poses / elapsed
 
@@ -694,7 +731,8 @@ def main():
         out["cpu_baseline"] = cpu_baseline(cfg, P, batch, confs, args)
         best = max(v["poses_per_s"] for v in out["cpu_baseline"]["by_samples"].values())
         out["gpu_over_cpu"] = value / best        # against the CPU's BEST figure (B = 20), not the B = 1 value
-        out["gpu_over_cpu_basis"] = "GPU value (B = %d) / max over the CPU rows (B = 1 and B = 20, both measured with --cpu-baseline full)" % B
+        out["gpu_over_cpu_basis"] = "GPU value (B = %d) / max over the CPU rows (B = 1 and B = 20; measured or extrapolated as " \
+                                    "by_samples labels them, --cpu-baseline %s)" % (B, args.cpu_baseline)
     if rank == 0:
         print(json.dumps(out))
     if dist:

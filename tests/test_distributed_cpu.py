@@ -117,3 +117,36 @@ def test_bench_distributed_branch_world2_gloo():
     bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1"], env=dict(env, WORLD_SIZE="2", RANK="0"),
                          capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "must agree" in (bad.stderr + bad.stdout)
+
+
+def test_bench_dump_outputs_world2_gloo(tmp_path):
+    """bench.py --dump-outputs on the same distributed branch (PD_BENCH_DRYRUN=1): rank 0 writes the whole node's poses of the LAST
+    timed call as float32 .npy, a rerun with the same arguments writes the same array, and --steps is the number of timed calls"""
+    import json
+    import socket
+    import subprocess
+    import sys
+
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PD_BENCH_DRYRUN="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    got = []
+    for run in range(2):
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", 0))
+            port = s.getsockname()[1]
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+               "--master-port", str(port), os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+               "--cfg", "small", "--samples", "3", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == 3 and "roofline" not in out and "cpu_baseline" not in out       # a plain run: the headline only
+        assert sorted(os.listdir(d)) == ["poses.npy"]
+        got.append(np.load(d / "poses.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (6, 96, 3)
+    assert np.array_equal(got[0], got[1])
+    # the last timed call is call warmup + steps - 1 = 3: seed 1234 + 3, global sample ids 0..5 (rank r holds 3r..3r+2)
+    ref = np.stack([torch.randn(96, 3, generator=torch.Generator().manual_seed(1000003 * (1234 + 3) + i)).numpy() for i in range(6)])
+    assert np.array_equal(got[0], ref)

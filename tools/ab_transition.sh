@@ -5,7 +5,7 @@ for bm in 128 64; do
   PD_TRANSITION_BM=$bm python -m physdock_amd.build --force > /dev/null 2>&1
   echo "== PD_TRANSITION_BM=$bm"
   python -m pytest tests/test_gemm_f16_gpu.py -q -x -k "fused_atom_transition" 2>&1 | tail -1
-  PD_TRANSITION_BM=$bm python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > /tmp/ab_t_$bm.json 2>/dev/null
+  PD_TRANSITION_BM=$bm python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra > /tmp/ab_t_$bm.json 2>/dev/null
   python - /tmp/ab_t_$bm.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -8,7 +8,7 @@ TAG=${1:-r04}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
-python bench.py --steps 3 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --steps 3 --warmup 1 --full > $OUT/bench.json 2> $OUT/bench.err
 # the traces below are about the step loop and the trunk: the first-call check of the fp16-format bounds (three eager denoiser passes with
 # ATen reductions, engine.check_dit_bounds) is switched off for them - it runs once per (weights, schedule) and never inside a timed call
 export PD_BOUND_CHECK=0
