@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PD_ABI_VERSION 9
+#define PD_ABI_VERSION 10
 
 enum { PD_OUT_ROWMAJOR = 0, PD_OUT_TRANSPOSED = 1, PD_OUT_OPM = 2, PD_OUT_BIASFRAG = 3 };
 
@@ -286,6 +286,15 @@ typedef struct pd_attn_args {
     /* ABI 8: rows of one part plane of O2 when the launch covers only a slice of the samples that share the O2 buffer (the low parts
        sit o2_rows * nheads * 32 elements behind the high parts); 0: nbatch * nq.  pd_attention sets it for its own sub-launches.    */
     long long o2_rows;
+    /* ABI 10: several systems in one launch (PhysDock.sample_diffusion_many).  Consecutive runs of group_samples batches share one
+       bias set: batch b reads the fragments at bias + (b / group_samples) * bias_gstride floats, all laid out for the same bias_nk
+       (the padded key count).  nk_group (device int[G], or NULL = nk for every group) holds each group's real key count; nk is
+       the launch's bound (every group count is clamped to [1, nk]) and what the launcher picks its kernel by.  group_samples = 0:
+       every batch shares group 0 (the behaviour before ABI 10).  Every kernel family honours the fields; the tail round of
+       pd_attention_tail is not taken by grouped launches.                                                                       */
+    int group_samples;
+    long long bias_gstride;
+    const int* nk_group;
 } pd_attn_args;
 /* Launches that cannot fill the chip (nbatch * nheads * ceil(nq/128) < 512 blocks) with a long key range are split into
  * up to 8 key chunks when ws holds nsplit * nbatch * nq * nheads * 34 floats; a second kernel merges the chunks. */
@@ -329,6 +338,12 @@ int pd_pair_init_z(const float* si, const float* sj, const float* WT, const floa
 int pd_segment_pool(const float* u, const int* tok_start, const float* add, float* out, int B, int A, int T, int C,
                     void* stream);
 int pd_unpool_add(float* ba, const float* us, const long long* a2t, int B, int A, int T, int C, void* stream);
+/* ABI 10, G systems of B samples each in one launch (PhysDock.sample_diffusion_many): sample g B + b of the [G B] rows belongs to
+ * system g and reads that system's own table - tok_start [G][T + 1], add [G][T][C] (or NULL), a2t [G][A].  At G = 1 each is
+ * bit-identical to its single-system counterpart.                                                                               */
+int pd_segment_pool_g(const float* u, const int* tok_start, const float* add, float* out, int G, int B, int A, int T, int C,
+                      void* stream);
+int pd_unpool_add_g(float* ba, const float* us, const long long* a2t, int G, int B, int A, int T, int C, void* stream);
 /* pd_downscale_pool (ABI 8): linear_downscale + SiLU + token mean pooling + s of the denoiser in one launch (reference
  * layers/transformers.py:205-212; csrc/pool.hip): out[b,t,:] = sum_{atoms l of t} silu(W ba[b,l,:] + bias) / (n_t + 1e-3) + add[t,:].
  * ba [B][A][128]; W2 / w_inv = the two fp16 parts of W [N][128] (fragment-major) and its inverse row scales (packing.split2_f16) -
@@ -337,6 +352,9 @@ int pd_unpool_add(float* ba, const float* us, const long long* a2t, int B, int A
  * finds more writes NaN into its tokens' rows instead of a wrong mean).  PD_ERR_UNSUPPORTED: other shapes.                         */
 int pd_downscale_pool(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
                       float* out, int B, int A, int T, int Cin, int N, int tpb, void* stream);
+/* ABI 10: the same for G systems of B samples (tok_start [G][T + 1], add [G][T][N]); tpb must hold for every system of the group */
+int pd_downscale_pool_g(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
+                        float* out, int G, int B, int A, int T, int Cin, int N, int tpb, void* stream);
 int pd_gather_rows_add(float* y, const float* x, const long long* idx, int R, int C, void* stream);
 int pd_axpby(float* out, const float* a, float sa, const float* b, const float* sb_ptr, float sb, long long n, void* stream);
 /* pd_template_feat  : templ_feat [T,T,no_bins+1] = [distogram bins of the pseudo-beta distance | mask] * mask, mask = z_mask *
@@ -397,6 +415,9 @@ int pd_augment(const float* x, float x_scale, const float* mask, const float* ro
 int pd_init_noise(float* x, const unsigned long long* seed, int sample0, float sigma0, int B, int A, void* stream);
 int pd_precond(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx, const float* a,
                float* ba, int B, int A, int C, void* stream);
+/* ABI 10: G systems of B samples, a [G][A][C] (system g's samples read a[g]); c_in_b, if given, [G B]                        */
+int pd_precond_g(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx, const float* a,
+                 float* ba, int G, int B, int A, int C, void* stream);
 int pd_denoise(const float* ba, const float* x_hat, const float* nw, const float* nb, const float* Wr, float eps,
                float c_skip, float c_out, const float* cs_b, const float* co_b, float* x_den, int B, int A, int C,
                void* stream);

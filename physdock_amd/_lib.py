@@ -76,6 +76,7 @@ class AttnArgs(C.Structure):
         ("K2", _fp), ("V2", _fp), ("kv2_bs", C.c_longlong), ("kv2_ss", C.c_longlong),      # ABI 6
         ("bias_prescale", C.c_float),                                                       # ABI 7
         ("o2_rows", C.c_longlong),                                                          # ABI 8
+        ("group_samples", C.c_int), ("bias_gstride", C.c_longlong), ("nk_group", _fp),    # ABI 10
     ]
 
 
@@ -174,6 +175,9 @@ def _declare(L):
     sig("pd_segment_pool", p, p, p, p, i, i, i, i, p)
     sig("pd_unpool_add", p, p, p, i, i, i, i, p)
     sig("pd_downscale_pool", p, p, p, p, p, p, p, i, i, i, i, i, i, p)
+    sig("pd_segment_pool_g", p, p, p, p, i, i, i, i, i, p)                # ABI 10: G systems x B samples
+    sig("pd_unpool_add_g", p, p, p, i, i, i, i, i, p)
+    sig("pd_downscale_pool_g", p, p, p, p, p, p, p, i, i, i, i, i, i, i, p)
     sig("pd_gather_rows_add", p, p, p, i, i, p)
     sig("pd_axpby", p, p, f, p, p, f, ll, p)
     sig("pd_template_mask", p, p, p, p, i, i, p)
@@ -189,6 +193,7 @@ def _declare(L):
     sig("pd_augment", p, f, p, p, p, p, f, f, p, i, i, p, i, i, p)
     sig("pd_init_noise", p, p, i, f, i, i, p)
     sig("pd_precond", p, f, p, p, p, p, p, i, i, i, p)
+    sig("pd_precond_g", p, f, p, p, p, p, p, i, i, i, i, p)
     sig("pd_denoise", p, p, p, p, p, f, f, f, p, p, p, i, i, i, p)
     sig("pd_kabsch_align", p, p, p, ll, p, p, i, i, p)
     sig("pd_template_match", p, p, p, p, p, p, p, i, i, i, i, p)

@@ -23,6 +23,7 @@
 #include <type_traits>
 #include "common.h"
 #include "physdock_hip.h"
+#include "attn_group.h"
 
 namespace {
 
@@ -40,7 +41,7 @@ __device__ unsigned long long* g_attn_trace = nullptr;
 // each writes its un-normalised output and (running max, sum) to the workspace, attn_combine_kernel merges them.  For
 // launches that cannot fill the chip (few samples): every wave's key loop is serial, so only shorter loops cut latency.
 template <int NW, bool SPLIT>
-__global__ __launch_bounds__(64 * NW, 4) void attn_kernel(const pd_attn_args p) {
+__global__ __launch_bounds__(64 * NW, 4) void attn_kernel(const pd_attn_args p_) {
     __shared__ __attribute__((aligned(16))) float sK[2][KT * LDKS];
     __shared__ __attribute__((aligned(16))) float sV[2][KT * LDVS];
 
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(64 * NW, 4) void attn_kernel(const pd_attn_args p) 
     // block, head) groups per XCD, interleaved or contiguous) were measured: both raise the fetch traffic of the DiT atom
     // attention from 433 to 637 MB (FETCH_SIZE) at unchanged run time, so the plain order stays.
     const int b = blockIdx.x, h = blockIdx.z;
+    const pd_attn_args p = pd_attn_group(p_, b);           // grouped launches (ABI 10): this block's bias set and key count
     const int qb = SPLIT ? blockIdx.y / p.nsplit : blockIdx.y, chunk = SPLIT ? blockIdx.y % p.nsplit : 0;
     const int q0 = qb * (32 * NW) + wave * 32;
     const int query = q0 + l31;
@@ -326,6 +328,7 @@ PD_EXPORT int pd_attention_variant(const pd_attn_args* a) {
 #endif
 static int attn_tail(const pd_attn_args* a, int* nsplit) {
     if (!PD_ATTN_TAIL || !a->ws || a->nq <= 128) return 0;
+    if (a->group_samples > 0 || a->nk_group) return 0;           // (its sub-launch renumbers the samples: grouped launches stay whole)
     const int bps = a->nheads * ((a->nq + 255) / 256);            // blocks per sample
     if (bps > 256 || 512 % bps) return 0;
     const int per = 512 / bps;                                    // samples per full round
@@ -357,6 +360,9 @@ PD_EXPORT int pd_attention(const pd_attn_args* a, void* stream) {
     for (long long s : strides) if (s % 4) return PD_ERR_UNSUPPORTED;
     if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->O | (uintptr_t)a->bias) & 15)
         return PD_ERR_UNSUPPORTED;
+    // grouped launches (ABI 10): every group's bias set starts 16-byte aligned
+    if (a->group_samples < 0 || a->bias_gstride < 0) return PD_ERR_ARG;
+    if (a->bias_gstride % 4) return PD_ERR_UNSUPPORTED;
     const int variant = pd_attention_variant(a);
     // A bias whose producer folded the operand-scale product into it (bias_prescale != 1) is only meaningful to the pipelined kernel:
     // any other kernel would consume it as an unscaled bias and return a wrong softmax silently - refuse instead.

@@ -13,6 +13,7 @@
 #include <type_traits>
 #include "common.h"
 #include "physdock_hip.h"
+#include "attn_group.h"
 
 namespace {
 
@@ -70,7 +71,7 @@ __device__ __forceinline__ int vpos(int k) {
 // SPLIT: the key range is cut into p.nsplit chunks (blockIdx.y = query block * nsplit + chunk), partial results to p.ws in the
 // format of attention.hip's attn_combine_kernel - the fp16-parts form of its key-split launch for a handful of samples
 template <int NW, int NP, bool PRE = false, bool SPLIT = false>
-__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_parts_kernel(const pd_attn_args p) {
+__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_parts_kernel(const pd_attn_args p_) {
     typedef Parts<NP> PT;
     typedef typename PT::frag frag;
     constexpr int STAGE = NP * (K_PART + V_PART);      // 16-bit elements per stage
@@ -78,6 +79,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
     const int b = blockIdx.x, h = blockIdx.z;
+    const pd_attn_args p = pd_attn_group(p_, b);           // grouped launches (ABI 10): this block's bias set and key count
     const int qb = SPLIT ? blockIdx.y / p.nsplit : blockIdx.y, chunk = SPLIT ? blockIdx.y % p.nsplit : 0;
     const int q0 = qb * (32 * NW) + wave * 32;
     const int query = q0 + l31;

@@ -20,6 +20,7 @@
 #include <string.h>
 #include "common.h"
 #include "physdock_hip.h"
+#include "attn_group.h"
 
 namespace {
 
@@ -100,7 +101,7 @@ __device__ __forceinline__ float max3(float a, float b, float c) { return __buil
 // Built, correct, and no faster (see PD_PIPE_RES below): kept as a lab form.
 constexpr int RES_TILES = 4;
 template <int NW, bool PRE, bool HASBIAS, bool RES = false>
-__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_pipe_kernel(const pd_attn_args p) {
+__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_pipe_kernel(const pd_attn_args p_) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -119,6 +120,8 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
             b = slot / ppx; h = pair / nqb; qb = pair % nqb;
         }
     }
+    // (after the XCD remapping: the group follows the sample the block really works on)
+    const pd_attn_args p = pd_attn_group(p_, b);           // grouped launches (ABI 10): this block's bias set and key count
     const int q0 = qb * (32 * NW) + wave * 32;
     const int query = q0 + l31;
     const bool wave_active = q0 < p.nq;

@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "common.h"
 #include "physdock_hip.h"
+#include "attn_group.h"
 
 namespace {
 
@@ -48,11 +49,12 @@ __device__ __forceinline__ int vpos(int k) {
 }
 
 template <int NW>
-__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_split_kernel(const pd_attn_args p) {
+__global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_split_kernel(const pd_attn_args p_) {
     extern __shared__ __attribute__((aligned(16))) __bf16 lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
     const int b = blockIdx.x, h = blockIdx.z, qb = blockIdx.y;
+    const pd_attn_args p = pd_attn_group(p_, b);           // grouped launches (ABI 10): this block's bias set and key count
     const int q0 = qb * (32 * NW) + wave * 32;
     const int query = q0 + l31;
     const bool wave_active = q0 < p.nq;

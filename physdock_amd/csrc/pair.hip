@@ -101,9 +101,16 @@ __global__ __launch_bounds__(256) void pair_init_z_kernel(const float* __restric
 // weight beyond the token) so every lane keeps 8 independent 16-byte loads in flight.
 __global__ __launch_bounds__(256) void segment_pool_kernel(const float* __restrict__ u, const int* __restrict__ tok_start,
                                                           const float* __restrict__ add, float* __restrict__ out,
-                                                          int A, int T, int C, long long n4) {
+                                                          int A, int T, int C, long long n4, int Bg) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n4) return;
+    if (Bg > 0) {              // pd_segment_pool_g: blockIdx.y = the system; its Bg samples, token table and add rows
+        const long long g = blockIdx.y;
+        u += g * Bg * A * C;
+        tok_start += g * (T + 1);
+        if (add) add += g * T * C;
+        out += g * Bg * T * C;
+    }
     const int c4 = idx % (C / 4);
     const long long bt = idx / (C / 4);
     const int t = bt % T;
@@ -130,9 +137,15 @@ __global__ __launch_bounds__(256) void segment_pool_kernel(const float* __restri
 // I: the index type - unsigned 32-bit whenever the element count allows (as pd_precond: 64-bit divisions cost ~300 instructions per 16 bytes)
 template <typename I>
 __global__ __launch_bounds__(256) void unpool_add_kernel(float* __restrict__ ba, const float* __restrict__ us,
-                                                        const long long* __restrict__ a2t, int A, int T, int C, long long n4) {
+                                                        const long long* __restrict__ a2t, int A, int T, int C, long long n4, int Bg) {
     const I idx = (I)blockIdx.x * 256 + threadIdx.x;
     if ((long long)idx >= n4) return;
+    if (Bg > 0) {              // pd_unpool_add_g: blockIdx.y = the system; its Bg samples and its atom -> token table
+        const long long g = blockIdx.y;
+        ba += g * Bg * A * C;
+        us += g * Bg * T * C;
+        a2t += g * A;
+    }
     const I nc4 = (I)(C / 4), row = idx / nc4;               // b*A + l
     const int c4 = (int)(idx - row * nc4);
     const I b = row / (I)A;
@@ -246,25 +259,46 @@ PD_EXPORT int pd_pair_init_z(const float* si, const float* sj, const float* WT, 
     return pd_check_launch();
 }
 
+static int segment_pool_launch(const float* u, const int* tok_start, const float* add, float* out, int G, int B, int A, int T,
+                               int C, int Bg, void* stream) {
+    if (!u || !tok_start || !out || C % 4 || G <= 0) return PD_ERR_ARG;
+    const long long n4 = (long long)B * T * (C / 4);
+    hipLaunchKernelGGL(segment_pool_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)G), dim3(256), 0, (hipStream_t)stream, u, tok_start,
+                       add, out, A, T, C, n4, Bg);
+    return pd_check_launch();
+}
+
 PD_EXPORT int pd_segment_pool(const float* u, const int* tok_start, const float* add, float* out, int B, int A, int T,
                               int C, void* stream) {
-    if (!u || !tok_start || !out || C % 4) return PD_ERR_ARG;
-    const long long n4 = (long long)B * T * (C / 4);
-    hipLaunchKernelGGL(segment_pool_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u, tok_start,
-                       add, out, A, T, C, n4);
+    return segment_pool_launch(u, tok_start, add, out, 1, B, A, T, C, 0, stream);
+}
+
+PD_EXPORT int pd_segment_pool_g(const float* u, const int* tok_start, const float* add, float* out, int G, int B, int A, int T,
+                                int C, void* stream) {
+    if (B <= 0) return PD_ERR_ARG;
+    return segment_pool_launch(u, tok_start, add, out, G, B, A, T, C, B, stream);
+}
+
+static int unpool_add_launch(float* ba, const float* us, const long long* a2t, int G, int B, int A, int T, int C, int Bg, void* stream) {
+    if (!ba || !us || !a2t || C % 4 || G <= 0) return PD_ERR_ARG;
+    const long long n4 = (long long)B * A * (C / 4);
+    const dim3 grid((unsigned)((n4 + 255) / 256), (unsigned)G);
+    if (n4 + 256 < 0x7fffffffll)
+        hipLaunchKernelGGL(unpool_add_kernel<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, ba, us, a2t,
+                           A, T, C, n4, Bg);
+    else
+        hipLaunchKernelGGL(unpool_add_kernel<long long>, grid, dim3(256), 0, (hipStream_t)stream, ba, us, a2t,
+                           A, T, C, n4, Bg);
     return pd_check_launch();
 }
 
 PD_EXPORT int pd_unpool_add(float* ba, const float* us, const long long* a2t, int B, int A, int T, int C, void* stream) {
-    if (!ba || !us || !a2t || C % 4) return PD_ERR_ARG;
-    const long long n4 = (long long)B * A * (C / 4);
-    if (n4 + 256 < 0x7fffffffll)
-        hipLaunchKernelGGL(unpool_add_kernel<unsigned>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ba, us, a2t,
-                           A, T, C, n4);
-    else
-        hipLaunchKernelGGL(unpool_add_kernel<long long>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ba, us, a2t,
-                           A, T, C, n4);
-    return pd_check_launch();
+    return unpool_add_launch(ba, us, a2t, 1, B, A, T, C, 0, stream);
+}
+
+PD_EXPORT int pd_unpool_add_g(float* ba, const float* us, const long long* a2t, int G, int B, int A, int T, int C, void* stream) {
+    if (B <= 0) return PD_ERR_ARG;
+    return unpool_add_launch(ba, us, a2t, G, B, A, T, C, B, stream);
 }
 
 PD_EXPORT int pd_gather_rows_add(float* y, const float* x, const long long* idx, int R, int C, void* stream) {

@@ -34,13 +34,18 @@ __global__ __launch_bounds__(256, PD_POOL_BPC) void downscale_pool_kernel(const 
                                                                 const float* __restrict__ w_inv, const float* __restrict__ bias,
                                                                 const int* __restrict__ tok_start,
                                                                 const float* __restrict__ add, float* __restrict__ out,
-                                                                int A, int T, int N, int tpb) {
+                                                                int A, int T, int N, int tpb, int Bg) {
     __shared__ __attribute__((aligned(16))) unsigned short lds[2 * PART];
     __shared__ float wmax[4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
     const int b = blockIdx.y, t0 = blockIdx.x * tpb;
+    if (Bg > 0) {              // pd_downscale_pool_g: sample b belongs to system b / Bg (once per block, 32-bit scalars)
+        const int g = b / Bg;
+        tok_start += g * (T + 1);
+        if (add) add += (long long)g * T * N;
+    }
     const int ntok = T - t0 < tpb ? T - t0 : tpb;
     const int a0 = tok_start[t0];
     int n = tok_start[t0 + ntok] - a0;
@@ -173,13 +178,26 @@ __global__ __launch_bounds__(256, PD_POOL_BPC) void downscale_pool_kernel(const 
 // [B][T][N].  tpb tokens per block, 1 .. 32, and the caller guarantees that tpb consecutive tokens never hold more than 64 atoms (tpb =
 // 64 / max atoms per token); a block that finds more writes NaN into its tokens' rows.  PD_ERR_UNSUPPORTED for other shapes: run pd_gemm
 // (act = SiLU) + pd_segment_pool.
-PD_EXPORT int pd_downscale_pool(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
-                                float* out, int B, int A, int T, int Cin, int N, int tpb, void* stream) {
+static int downscale_pool_launch(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
+                                 float* out, int B, int A, int T, int Cin, int N, int tpb, int Bg, void* stream) {
     if (!ba || !W2 || !w_inv || !tok_start || !out || B <= 0 || A <= 0 || T <= 0) return PD_ERR_ARG;
     if (Cin != CIN || N <= 0 || N % 32 != 0 || tpb < 1 || tpb > 32) return PD_ERR_UNSUPPORTED;
     if ((((uintptr_t)ba | (uintptr_t)W2) & 15) != 0) return PD_ERR_UNSUPPORTED;
     dim3 grid((unsigned)((T + tpb - 1) / tpb), (unsigned)B);
     hipLaunchKernelGGL(downscale_pool_kernel, grid, dim3(256), 0, (hipStream_t)stream, ba, reinterpret_cast<const _Float16*>(W2), w_inv, bias,
-                       tok_start, add, out, A, T, N, tpb);
+                       tok_start, add, out, A, T, N, tpb, Bg);
     return pd_check_launch();
+}
+
+PD_EXPORT int pd_downscale_pool(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
+                                float* out, int B, int A, int T, int Cin, int N, int tpb, void* stream) {
+    return downscale_pool_launch(ba, W2, w_inv, bias, tok_start, add, out, B, A, T, Cin, N, tpb, 0, stream);
+}
+
+// G systems of B samples each: ba [G B][A][128], tok_start [G][T + 1], add [G][T][N] or NULL, out [G B][T][N]; tpb must hold for every
+// system (the minimum over the group)
+PD_EXPORT int pd_downscale_pool_g(const float* ba, const void* W2, const float* w_inv, const float* bias, const int* tok_start, const float* add,
+                                  float* out, int G, int B, int A, int T, int Cin, int N, int tpb, void* stream) {
+    if (G <= 0 || B <= 0) return PD_ERR_ARG;
+    return downscale_pool_launch(ba, W2, w_inv, bias, tok_start, add, out, G * B, A, T, Cin, N, tpb, B, stream);
 }

@@ -132,9 +132,16 @@ template <typename I>
 __global__ __launch_bounds__(256) void precond_kernel(const float* __restrict__ x_hat, float c_in, const float* __restrict__ c_in_b,
                                                      const float* __restrict__ Wx, const float* __restrict__ bx,
                                                      const float* __restrict__ a, float* __restrict__ ba, int A, int C,
-                                                     long long n4) {
+                                                     long long n4, int Bg) {
     const I idx = (I)blockIdx.x * 256 + threadIdx.x;
     if ((long long)idx >= n4) return;
+    if (Bg > 0) {              // pd_precond_g: blockIdx.y = the system; its Bg samples and its own a (n4 = one system's elements)
+        const long long g = blockIdx.y;
+        x_hat += g * Bg * A * 3;
+        ba += g * Bg * A * C;
+        a += g * A * C;
+        if (c_in_b) c_in_b += g * Bg;
+    }
     const I nc4 = (I)(C / 4), row = idx / nc4;
     const int c4 = (int)(idx - row * nc4);
     const I smp = row / (I)A;
@@ -498,17 +505,29 @@ PD_EXPORT int pd_init_noise(float* x, const unsigned long long* seed, int sample
     return pd_check_launch();
 }
 
+static int precond_launch(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx,
+                          const float* a, float* ba, int G, int B, int A, int C, int Bg, void* stream) {
+    if (!x_hat || !Wx || !bx || !a || !ba || C % 4 || G <= 0) return PD_ERR_ARG;
+    const long long n4 = (long long)B * A * (C / 4);
+    const dim3 grid((unsigned)((n4 + 255) / 256), (unsigned)G);
+    if (n4 + 256 < 0x7fffffffll)
+        hipLaunchKernelGGL(precond_kernel<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, x_hat, c_in,
+                           c_in_b, Wx, bx, a, ba, A, C, n4, Bg);
+    else
+        hipLaunchKernelGGL(precond_kernel<long long>, grid, dim3(256), 0, (hipStream_t)stream, x_hat, c_in,
+                           c_in_b, Wx, bx, a, ba, A, C, n4, Bg);
+    return pd_check_launch();
+}
+
 PD_EXPORT int pd_precond(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx,
                          const float* a, float* ba, int B, int A, int C, void* stream) {
-    if (!x_hat || !Wx || !bx || !a || !ba || C % 4) return PD_ERR_ARG;
-    const long long n4 = (long long)B * A * (C / 4);
-    if (n4 + 256 < 0x7fffffffll)
-        hipLaunchKernelGGL(precond_kernel<unsigned>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_hat, c_in,
-                           c_in_b, Wx, bx, a, ba, A, C, n4);
-    else
-        hipLaunchKernelGGL(precond_kernel<long long>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_hat, c_in,
-                           c_in_b, Wx, bx, a, ba, A, C, n4);
-    return pd_check_launch();
+    return precond_launch(x_hat, c_in, c_in_b, Wx, bx, a, ba, 1, B, A, C, 0, stream);
+}
+
+PD_EXPORT int pd_precond_g(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx,
+                           const float* a, float* ba, int G, int B, int A, int C, void* stream) {
+    if (B <= 0) return PD_ERR_ARG;
+    return precond_launch(x_hat, c_in, c_in_b, Wx, bx, a, ba, G, B, A, C, B, stream);
 }
 
 PD_EXPORT int pd_denoise(const float* ba, const float* x_hat, const float* nw, const float* nb, const float* Wr, float eps,

@@ -193,7 +193,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     return out
 
 
-def redock_many(model, systems, *, streams: Optional[int] = None, **common) -> List[dict]:
+def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
     `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `infer_meta_data` ... differ per system); `common`:
@@ -204,12 +204,209 @@ def redock_many(model, systems, *, streams: Optional[int] = None, **common) -> L
     than 32 samples (`parallel.StreamPool`: one model replica, stream and host thread each; poses are bit-identical to the
     one-at-a-time run, `tests/test_concurrent_streams_gpu.py`, `tests/test_configs_3_5_gpu.py`).  `streams=1` runs them one by one;
     rounds of 32 or more samples already fill the chip and run one by one unless `streams` says otherwise.  Across GPUs the same list
-    is dealt out by `parallel.map_systems`."""
+    is dealt out by `parallel.map_systems`.
+
+    `group=G` samples up to G systems TOGETHER instead (`PhysDock.sample_diffusion_many`: one step loop, every denoiser launch over
+    G x num_samples_per_round rows): the systems are dealt out in groups ordered by padded shape (`group_order`), each group's round
+    loops run in lockstep - one grouped sampler call per round over its systems still active - with redock's per-system rules
+    (accept / reject, adaptive threshold, template pool, conditioning reuse, top-up, ranking).  Systems whose relaxation runs on
+    the host (an RDKit molecule on the host backend, `relax_fn=`) go through `redock` one by one."""
     items = [(s, {}) if isinstance(s, dict) else (s[0], dict(s[1])) for s in systems]
-    n = streams if streams is not None else (2 if int(common.get("num_samples_per_round", 5)) < 32 else 1)
+    pool = common.pop("pool", None)
     on_gpu = bool(items) and items[0][0]["x_gt"].is_cuda and hasattr(model, "config")
+    if group is not None and on_gpu and hasattr(model, "sample_diffusion_many"):
+        out: List[Optional[dict]] = [None] * len(items)
+        grouped = []
+        for i, (b, kw) in enumerate(items):
+            args = dict(common, **kw)
+            if _needs_host_relax(model, b, args.get("ref_mol"), dict(args.get("sampler_kwargs") or {})):
+                out[i] = redock(model, b, **args)
+            else:
+                grouped.append(i)
+        shapes = [tuple(model._prepare_batch(items[i][0])[k].shape[0] for k in ("ref_pos", "target_feat")) for i in grouped]
+        for members in group_order(shapes, int(group)):
+            idx = [grouped[m] for m in members]
+            for i, r in zip(idx, _redock_group(model, [items[i] for i in idx], common)):
+                out[i] = r
+        return out
+    n = streams if streams is not None else (2 if int(common.get("num_samples_per_round", 5)) < 32 else 1)
     if n <= 1 or len(items) <= 1 or not on_gpu:
         return [redock(model, b, **dict(common, **kw)) for b, kw in items]
     from .parallel import StreamPool
-    pool = common.pop("pool", None) or StreamPool.for_model(model, n=n)      # cached on the model: replicas are built once
+    pool = pool or StreamPool.for_model(model, n=n)      # cached on the model: replicas are built once
     return pool.map(lambda m, it: redock(m, it[0], **dict(common, **it[1])), items)
+
+
+def group_order(shapes, group: int) -> List[List[int]]:
+    """redock_many(group=G): the systems dealt out in groups of up to G, ordered by padded shape (largest first; input order
+    among equal shapes) so that a group pads little.  shapes: per system a sortable padded shape, e.g. (A, T)."""
+    if group < 1:
+        raise ValueError(f"group={group}: expected a positive group size")
+    order = sorted(range(len(shapes)), key=lambda i: (tuple(-int(v) for v in shapes[i]), i))
+    return [order[k:k + group] for k in range(0, len(order), group)]
+
+
+def _needs_host_relax(model, batch, ref_mol, kw) -> bool:
+    """would this system's relaxation branch run on the host (an RDKit molecule on the host backend, or relax_fn=)?"""
+    if ref_mol is None:
+        return False
+    n_mol = _mol_num_atoms(ref_mol)
+    if n_mol is not None and n_mol != int(ligand_atom_mask(batch).sum()):
+        return False                          # redock drops the molecule (ref_mol_num_error)
+    if kw.get("relax_fn") is not None:
+        return True
+    from . import physics
+    return physics.resolve_relaxer(ref_mol, None, kw.get("mmff_backend", "auto")).kind == "host"
+
+
+class _RedockState:
+    """one system's state in redock_many's lockstep round loop: redock's per-system bookkeeping, round by round"""
+
+    def __init__(self, batch, pbatch, *, ref_mol=None, ref_mol_poses=None, accept_fn=None, chirality=None, physics_correction=False,
+                 max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
+                 align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
+                 steps=40, karras_noise_schedule_power=1000):
+        # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
+        #  the group's - _redock_group passes them to the sampler)
+        if physics_correction and ref_mol_poses is None:
+            raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
+                             "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
+        self.batch, self.pbatch = dict(batch), dict(pbatch)
+        self.ref_mol_poses = ref_mol_poses.to(batch["x_gt"].device) if ref_mol_poses is not None else None
+        self.is_lig = ligand_atom_mask(batch)
+        self.ligand_idx = torch.nonzero(self.is_lig).flatten().to(torch.int32)
+        self.accept, self.reject = [], deque([], maxlen=max_samples)
+        self.ligand_templates, self.reference_templates = [], []
+        self.factor = float(mmff_gamma_0_factor_start)
+        self.log = []
+        self.kw = dict(sampler_kwargs or {})
+        n_mol = _mol_num_atoms(ref_mol) if ref_mol is not None else None
+        self.ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(self.is_lig.sum()))
+        self.ref_mol, self.accept_fn, self.chirality, self.pc = ref_mol, accept_fn, chirality, physics_correction
+        self.max_samples, self.max_rounds, self.nspr = max_samples, max_rounds, num_samples_per_round
+        self.use_pocket, self.align_weights, self.ranking, self.seed = use_pocket, align_weights, ranking, seed
+        self.infer_meta_data, self.reuse = infer_meta_data, reuse_conditioning
+        self.cond, self.done, self.templates = None, False, None
+
+    def round_args(self, rnd):
+        """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
+        if self.done or (rnd > 0 and not self.pc):
+            self.done = True
+            return None
+        if rnd >= 1 and "batch_msa_feat" in self.batch:
+            if rnd >= self.batch["batch_msa_feat"].shape[0]:
+                raise ValueError(f"batch_msa_feat holds {self.batch['batch_msa_feat'].shape[0]} re-sampled MSAs, round {rnd} needs "
+                                 "its own (the reference loads num_recycles = max_rounds of them, redocking.py:83)")
+            msa = self.batch["batch_msa_feat"][rnd]
+            self.batch["msa_feat"] = msa
+            pt = self.pbatch["target_feat"].shape[0] - msa.shape[1]        # the group-padded token count
+            self.pbatch["msa_feat"] = torch.nn.functional.pad(msa.float(), (0, 0, 0, pt)).contiguous()
+            self.cond = None
+        self.templates = torch.stack(self.ligand_templates + self.reference_templates, 0) if rnd > 0 else None
+        want_cond = (self.reuse and self.cond is None and self.pc and rnd + 1 < self.max_rounds and "batch_msa_feat" not in self.batch)
+        return dict(factor=self.factor, ref_mol=None if self.ref_mol_num_error else self.ref_mol, ref_mol_poses=self.templates,
+                    eta=1.5 if self.ref_mol_num_error else 1.0, seed=self.kw.get("seed", (self.seed + rnd) if self.seed is not None else 0),
+                    sample_offset=self.kw.get("sample_offset", 0), noise=self.kw.get("noise"), cond=self.cond if self.reuse else None,
+                    want_cond=want_cond)
+
+    def consume(self, rnd, x_pred, cond):
+        """redock's accept / reject, adaptive factor and template pool for this round's poses"""
+        if cond is not None and self.reuse:
+            self.cond = cond
+        if rnd + 1 >= self.max_rounds:
+            self.cond = None
+        dev_ok = self.chirality.accept(x_pred).tolist() if (self.pc and self.chirality is not None) else None
+        x_cpu = x_pred.cpu() if (self.pc and self.accept_fn is not None) else x_pred
+        flags = []
+        for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
+            ok = True
+            if dev_ok is not None:
+                ok = bool(dev_ok[b])
+            if ok and self.pc and self.accept_fn is not None:
+                ok = bool(self.accept_fn(xc))
+            flags.append(ok)
+            if ok:
+                self.ligand_templates.append(x[self.is_lig])
+                self.accept.append(x)
+            else:
+                self.reject.append(x)
+        self.log.append({"round": rnd, "gamma_factor": self.factor, "accepted": int(sum(flags)), "sampled": len(flags),
+                         "templates": 0 if self.templates is None else int(self.templates.shape[0])})
+        if self.pc:
+            self.factor = next_gamma_factor(self.factor, any(flags))
+            if len(self.accept) >= self.max_samples:
+                self.cond, self.done = None, True
+                return
+            used = select_reference_templates(x_pred, self.ligand_idx, self.ref_mol_poses, self.max_samples - len(self.ligand_templates))
+            self.reference_templates = [self.ref_mol_poses[i] for i in used.tolist()]
+        else:
+            self.done = True
+        if rnd + 1 >= self.max_rounds:
+            self.done = True
+
+    def result(self):
+        """redock's top-up, alignment into the ground-truth frame, ranking and PDB text"""
+        self.cond = None
+        n_accepted = len(self.accept)
+        accept = self.accept + list(self.reject) if len(self.accept) < self.nspr else self.accept
+        poses = torch.stack(accept[:self.max_samples], 0)
+        w = self.align_weights if self.align_weights is not None else pocket_align_weights(self.batch, self.use_pocket)
+        x_gt = self.batch["x_gt"].float()
+        aligned = weighted_rigid_align(x_gt[None].expand(poses.shape[0], -1, -1).contiguous(), poses, w)
+        out = {"poses": aligned, "accepted": n_accepted, "rounds": self.log, "gamma_factor": self.factor, "ranking": None}
+        if self.ranking:
+            from .ranking import rank_poses
+            out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig)
+        if self.infer_meta_data is not None:
+            from .pdbio import PdbTemplate
+            out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
+            out["receptor_pdb_blocks"] = PdbTemplate(self.infer_meta_data, receptor_only=True).blocks(aligned)
+        return out
+
+
+_MANY_SAMPLER_KEYS = {"seed", "sample_offset", "noise", "use_graph", "mmff_backend", "mmff_iters"}
+
+
+def _redock_group(model, items, common) -> List[dict]:
+    """redock for the systems of one group, their round loops in lockstep: each round is ONE sample_diffusion_many call over the
+    systems still active (same schedule and sample count for all; per-system threshold, template pool, seed, relaxation)"""
+    pbs = model._pad_to_group([model._prepare_batch(b) for b, _ in items])
+    states = []
+    for (b, kw), pb in zip(items, pbs):
+        args = dict(common, **kw)
+        bad = set((args.get("sampler_kwargs") or {})) - _MANY_SAMPLER_KEYS
+        if bad:
+            raise ValueError(f"redock_many(group=): sampler_kwargs {sorted(bad)} are not supported by grouped sampling")
+        states.append(_RedockState(b, pb, **args))
+    for k in ("steps", "karras_noise_schedule_power", "num_samples_per_round", "use_graph", "mmff_backend", "mmff_iters"):
+        # one sampler call per round serves the whole group: what it shares must be the same for every system
+        vals = {repr(st.kw.get(k)) if k in _MANY_SAMPLER_KEYS else repr(dict(common, **kw).get(k)) for st, (_, kw) in zip(states, items)}
+        if len(vals) > 1:
+            raise ValueError(f"redock_many(group=): the systems of one group differ in {k} ({sorted(vals)}); it is shared by "
+                             "the grouped sampler call - give it in the common keywords or run those systems without group=")
+    args0 = dict(common, **items[0][1])
+    steps = int(args0.get("steps", 40))
+    power = args0.get("karras_noise_schedule_power", 1000)
+    nspr = int(args0.get("num_samples_per_round", 5))
+    max_rounds = max(st.max_rounds for st in states)      # (each system stops at its own max_rounds: round_args / consume)
+    for rnd in range(max_rounds):
+        active = [(st, a) for st in states if (a := st.round_args(rnd)) is not None]
+        if not active:
+            break
+        sk = active[0][0].kw
+        call = dict(num_sample=nspr, steps=steps, align_ref_pos=rnd > 0, karras_noise_schedule_power=power,
+                    mmff_gamma_0_factor=[a["factor"] for _, a in active], ode_step_scale_eta=[a["eta"] for _, a in active],
+                    ref_mol=[a["ref_mol"] for _, a in active], ref_mol_poses=[a["ref_mol_poses"] for _, a in active],
+                    seeds=[a["seed"] for _, a in active], sample_offsets=[a["sample_offset"] for _, a in active],
+                    conditionings=[a["cond"] for _, a in active], return_conditioning=any(a["want_cond"] for _, a in active))
+        if any(a["noise"] is not None for _, a in active):
+            call.update(noises=[a["noise"] for _, a in active])
+        for k in ("use_graph", "mmff_backend", "mmff_iters"):
+            if k in sk:
+                call[k] = sk[k]
+        with torch.no_grad():
+            r = model.sample_diffusion_many([st.pbatch for st, _ in active], **call)
+        outs, conds = r if isinstance(r, tuple) else (r, [None] * len(active))
+        for (st, a), x, c in zip(active, outs, conds):
+            st.consume(rnd, x, c if a["want_cond"] else None)
+    return [st.result() for st in states]

@@ -583,10 +583,8 @@ class Engine:
         instead of 18 x steps times) and the AdaLN tables of every step (adaptive_layer_norm_zero.py:19)."""
         P, ws = self.P, self.ws
         dt = self.cfg.model.dit
-        Ca, Cap, Cs, Cz = dt.c_a, dt.c_ap, dt.c_s, dt.c_z
+        Ca, Cs = dt.c_a, dt.c_s
         A, T = a.shape[0], s.shape[0]
-        n = tau.shape[0]
-        L = ops._lib.init()
         # --- hoisted biases (times the product of the q, k operand scales when the step loop's launches - B samples - take the
         # pipelined attention kernel: attn_prescale)
         Ar, Tr = batch.get("_A_real", A), batch.get("_T_real", T)
@@ -594,8 +592,20 @@ class Engine:
         ps_a = self.attn_prescale(P.dit_qk_bounds_host("atom"), B, A, Ar, Ca // 32, self.attn_ws(B, A, Ar, Ca // 32), strides=(A * 3 * Ca, 3 * Ca)) if (B and f16 and "atom" not in self.f16_off) else 0.0
         ps_t = self.attn_prescale(P.dit_qk_bounds_host("token"), B, T, Tr, Cs // 32, self.attn_ws(B, T, Tr, Cs // 32), strides=(T * 3 * Cs, 3 * Cs)) if (B and f16 and "token" not in self.f16_off) else 0.0
         osc_a, osc_t = LOG2E * (ps_a or 1.0), LOG2E * (ps_t or 1.0)
-        Wa, ba_, na = P.dit_bias("atom")                  # [2*nb_atom*H, Cap] with LN affine folded
+        na, nt = P.dit_bias("atom")[2], P.dit_bias("token")[2]
         fa = ws.get("dit_atom_bias", ops.bias_frag_numel(na, A, A), zero=True)
+        ft = ws.get("dit_token_bias", ops.bias_frag_numel(nt, T, T), zero=True)
+        self._dit_biases(ap, z, batch, A, T, fa, ft, osc_a, osc_t)
+        tab_a, tab_t, bnd = self._dit_tables(tau, per_sample)
+        return {"atom_bias": fa, "token_bias": ft, "tab_atom": tab_a, "tab_token": tab_t, "bnd_atom": bnd["atom"],
+                "bnd_token": bnd["token"], "ps_atom": ps_a, "ps_token": ps_t, "B": B}
+
+    def _dit_biases(self, ap, z, batch, A, T, fa, ft, osc_a, osc_t):
+        """the hoisted atom / token pair biases of the DiT blocks of one system, in fragment layout (x log2 e x the pre-scale)"""
+        P = self.P
+        dt = self.cfg.model.dit
+        Cap, Cz = dt.c_ap, dt.c_z
+        Wa, ba_, na = P.dit_bias("atom")                  # [2*nb_atom*H, Cap] with LN affine folded
         if not (Wa.shape[1] == Cap and ops.pair_bias(ap, Wa, fa, A, A, Cap, na, c2=ba_, maskadd=batch["ap_mask"],
                                                       maskval=-self.inf, out_scale=osc_a, mode=LN, eps=1e-5,
                                                       only_if_faster=True)):
@@ -604,9 +614,16 @@ class Engine:
                       maskadd=batch["ap_mask"], maskval=-self.inf, out_scale=osc_a)
         Wt, bt_, nt = P.dit_bias("token")
         st = self.stats(z, T * T, Cz, LN, 1e-5, "stats_pb")
-        ft = ws.get("dit_token_bias", ops.bias_frag_numel(nt, T, T), zero=True)
         self.gemm(z, Wt, ft, T * T, nt, Cz, stats=st, bias=bt_, out_mode=OUT_BIASFRAG, T1=T, T2=T,
-                 maskadd=batch["z_mask"], maskval=-self.inf, out_scale=osc_t)
+                  maskadd=batch["z_mask"], maskval=-self.inf, out_scale=osc_t)
+
+    def _dit_tables(self, tau, per_sample=False):
+        """AdaLN tables of every step and the magnitude bounds derived from them: functions of the noise levels only"""
+        P, ws = self.P, self.ws
+        dt = self.cfg.model.dit
+        Ca, Cs = dt.c_a, dt.c_s
+        n = tau.shape[0]
+        L = ops._lib.init()
         # --- AdaLN tables: t = MLP(sincos(tau)); table = Linear(silu(t)) with 1 folded into the scale bias
         emb = ws.get("t_emb", n, 256)
         ops.check(L.pd_timestep_embed(ops.ptr(tau), ops.ptr(emb), n, ops.stream()), "timestep_embed")
@@ -631,14 +648,49 @@ class Engine:
             if per_sample:                  # rows = samples of ONE launch (training-time forward): the launch needs the largest
                 out.copy_(out.amax(0, keepdim=True).expand_as(out))
             bnd[kind] = out
-        return {"atom_bias": fa, "token_bias": ft, "tab_atom": tab_a, "tab_token": tab_t, "bnd_atom": bnd["atom"],
-                "bnd_token": bnd["token"], "ps_atom": ps_a, "ps_token": ps_t, "B": B}
+        return tab_a, tab_t, bnd
 
-    def dit_block(self, prefix, x, B, N, C, bias, tab, tab_off, tab_ld, per_sample, nk, bnd=None, bias_prescale=0.0, rows_alloc=0):
+    def prepare_dit_many(self, cond_of, batches, tau, B):
+        """prepare_dit for G systems of one padded shape sampled together (PhysDock.sample_diffusion_many).  cond_of(g) -> the
+        (a, ap, s, z) of system g, consumed before the next one is asked for (the trunk's outputs are shape-keyed workspace buffers):
+        its hoisted biases go into slot g of stacked [G][fragments] buffers, its a / s into stacked [G][A][c_a] / [G][T][c_s]
+        buffers (prep["a"] / prep["s"]).  The AdaLN tables and bounds depend on the schedule only and are built once.  The pre-scale
+        is decided for the launch that really runs: G B batches, the group's largest real key count."""
+        P, ws = self.P, self.ws
+        dt = self.cfg.model.dit
+        Ca, Cs = dt.c_a, dt.c_s
+        G = len(batches)
+        A, T = batches[0]["ref_pos"].shape[0], batches[0]["target_feat"].shape[0]
+        Ar = max(b.get("_A_real", A) for b in batches)
+        Tr = max(b.get("_T_real", T) for b in batches)
+        nb = G * B
+        f16 = ops.SPLIT_GEMM and ops.F16_GEMM
+        ps_a = self.attn_prescale(P.dit_qk_bounds_host("atom"), nb, A, Ar, Ca // 32, self.attn_ws(nb, A, Ar, Ca // 32), strides=(A * 3 * Ca, 3 * Ca)) if (B and f16 and "atom" not in self.f16_off) else 0.0
+        ps_t = self.attn_prescale(P.dit_qk_bounds_host("token"), nb, T, Tr, Cs // 32, self.attn_ws(nb, T, Tr, Cs // 32), strides=(T * 3 * Cs, 3 * Cs)) if (B and f16 and "token" not in self.f16_off) else 0.0
+        osc_a, osc_t = LOG2E * (ps_a or 1.0), LOG2E * (ps_t or 1.0)
+        na, nt = P.dit_bias("atom")[2], P.dit_bias("token")[2]
+        ga, gt = ops.bias_frag_numel(na, A, A), ops.bias_frag_numel(nt, T, T)
+        fa = ws.get("dit_atom_bias_g", G, ga, zero=True)
+        ft = ws.get("dit_token_bias_g", G, gt, zero=True)
+        a_g = ws.get("grp:a", G, A, Ca)
+        s_g = ws.get("grp:s", G, T, Cs)
+        for g, b in enumerate(batches):
+            a, ap, s, z = cond_of(g)
+            self._dit_biases(ap, z, b, A, T, fa[g], ft[g], osc_a, osc_t)
+            a_g[g].copy_(a.reshape(A, Ca))
+            s_g[g].copy_(s.reshape(T, Cs))
+        tab_a, tab_t, bnd = self._dit_tables(tau)
+        return {"atom_bias": fa, "token_bias": ft, "tab_atom": tab_a, "tab_token": tab_t, "bnd_atom": bnd["atom"],
+                "bnd_token": bnd["token"], "ps_atom": ps_a, "ps_token": ps_t, "B": nb, "G": G, "gstride_atom": ga, "gstride_token": gt,
+                "a": a_g, "s": s_g}
+
+    def dit_block(self, prefix, x, B, N, C, bias, tab, tab_off, tab_ld, per_sample, nk, bnd=None, bias_prescale=0.0, rows_alloc=0,
+                  gkw=None):
         """DiTBlock (transformers.py:155-159; attentions.py:241-265; transitions.py:27-30).
         tab: AdaLN table row(s) [shift | 1+scale | gate] x (attention, transition) for this block.
         rows_alloc: rows x is allocated with (>= B N, see af3_dit): every row-wise launch of the block then covers that many rows -
-        whole 64-row tiles - and the rows past B N hold garbage nobody reads (the attention addresses rows by (sample, position))."""
+        whole 64-row tiles - and the rows past B N hold garbage nobody reads (the attention addresses rows by (sample, position)).
+        gkw: the group fields of a launch over several systems (af3_dit(grp=)): bias set and real key count per run of samples."""
         P, eps = self.P, self.eps
         rows = rows_alloc or B * N
         H = C // 32
@@ -675,7 +727,7 @@ class Engine:
         # bnd: device address of this (step, block)'s magnitude bounds: chip-filling attention launches then take the two-part
         # fp16 operand format too - and write their output already split for linear_o (no split VALU in that GEMM's staging)
         akw = dict(nq=N, nk=nk, nbatch=B, nheads=H, q_strides=st3, k_strides=st3, v_strides=st3, o_strides=(N * C, C), bias=bias,
-                   bias_nk=N, ws=self.attn_ws(B, N, nk, H), f16_amax=bnd, bias_prescale=bias_prescale)
+                   bias_nk=N, ws=self.attn_ws(B, N, nk, H), f16_amax=bnd, bias_prescale=bias_prescale, **(gkw or {}))
         # (K = 512 rows in chip-filling launches: the wide-rows kernel normalises and splits a block's rows inside the projection -
         #  no pre-split copy for q | k | v at all; asked of the library)
         wrows = bool(f16 and ops.F16_ROWS and ops.F16_WIDE_ROWS and C == 512 and ops.rows_inline_supported(
@@ -808,15 +860,27 @@ class Engine:
         self.f16_off |= off_now
         return off_now
 
-    def af3_dit(self, batch, x_hat, x_den, a, s, prep, B, scal, row=0, per_sample=False):
+    def af3_dit(self, batch, x_hat, x_den, a, s, prep, B, scal, row=0, per_sample=False, grp=None):
         """AF3DiT.forward (transformers.py:235-262) for one noise level.
-        scal: dict(c_in, c_skip, c_out) floats, or per-sample device arrays when per_sample."""
+        scal: dict(c_in, c_skip, c_out) floats, or per-sample device arrays when per_sample.
+        grp (PhysDock.sample_diffusion_many): dict(G, B, nk_atom, nk_token) - G systems of grp["B"] samples each, B = G grp["B"] in
+        all.  a [G][A][Ca] and s [G][T][Cs] are then stacked, batch["_tok_start"] [G][T + 1] and batch["atom_id_to_token_id"] [G][A]
+        too, nk_atom / nk_token device int32 [G] the real counts, batch["_A_real"] / ["_T_real"] their maxima, batch["_pool_tpb"]
+        the minimum, prep from prepare_dit_many.  Every row-wise launch runs once over the G B samples; the per-system inputs go
+        through the grouped entry points."""
         P, ws = self.P, self.ws
         dt = self.cfg.model.dit
         Ca, Cs = dt.c_a, dt.c_s
-        A, T = a.shape[0], s.shape[0]
+        A, T = a.shape[-2], s.shape[-2]
         Ar, Tr = batch.get("_A_real", A), batch.get("_T_real", T)
         Ha, Hs = Ca // 32, Cs // 32
+        G, Bg = (grp["G"], grp["B"]) if grp is not None else (1, B)
+        gka = gkt = None
+        if grp is not None:
+            if per_sample or G * Bg != B:
+                raise ValueError("a grouped denoiser pass takes G x B samples on one schedule")
+            gka = dict(group_samples=Bg, bias_gstride=prep["gstride_atom"], nk_group=grp["nk_atom"])
+            gkt = dict(group_samples=Bg, bias_gstride=prep["gstride_token"], nk_group=grp["nk_token"])
         L = ops._lib.init()
         sp = ops.stream()
         # Sample-major activations [B N, C] are allocated - and run through every row-wise launch - in whole 64-row tiles: a ragged
@@ -827,8 +891,12 @@ class Engine:
         RT = B * T if per_sample else -(-(B * T) // 64) * 64
         ba = self.lws("dit_ba", RA, Ca)
         cin_b = ops.ptr(scal["c_in"]) if per_sample else None
-        ops.check(L.pd_precond(ops.ptr(x_hat), 0.0 if per_sample else scal["c_in"], cin_b, ops.ptr(P["dit.linear_x.weight"]),
-                               ops.ptr(P["dit.linear_x.bias"]), ops.ptr(a), ops.ptr(ba), B, A, Ca, sp), "precond")
+        if grp is not None:
+            ops.check(L.pd_precond_g(ops.ptr(x_hat), scal["c_in"], None, ops.ptr(P["dit.linear_x.weight"]),
+                                     ops.ptr(P["dit.linear_x.bias"]), ops.ptr(a), ops.ptr(ba), G, Bg, A, Ca, sp), "precond_g")
+        else:
+            ops.check(L.pd_precond(ops.ptr(x_hat), 0.0 if per_sample else scal["c_in"], cin_b, ops.ptr(P["dit.linear_x.weight"]),
+                                   ops.ptr(P["dit.linear_x.bias"]), ops.ptr(a), ops.ptr(ba), B, A, Ca, sp), "precond")
         tab_a, tab_t = prep["tab_atom"], prep["tab_token"]
         lda_, ldt_ = tab_a.shape[1], tab_t.shape[1]
         fa_stride = ops.bias_frag_numel(Ha, A, A)
@@ -845,7 +913,7 @@ class Engine:
         for b in range(nb_a):
             self.dit_block(f"dit.atom_dit_encoder.blocks.{b}", ba, B, A, Ca, off(prep["atom_bias"], b * fa_stride),
                            tab_a, row * lda_ + b * 6 * Ca, lda_, per_sample, Ar, bnd=boff(bnd_a, (row * 2 * nb_a + b) * 8), bias_prescale=psa,
-                           rows_alloc=RA)
+                           rows_alloc=RA, gkw=gka)
         bs = self.lws("dit_bs", RT, Cs)
         Wd, bd, _, Kd, ldwd = P.linear("dit.linear_downscale")
         tpb = batch.get("_pool_tpb", 0)
@@ -853,25 +921,35 @@ class Engine:
         if ops.FUSED_POOL and ops.SPLIT_GEMM and ops.F16_GEMM and tpb > 0 and Kd == Ca and ldwd == Ca:
             # linear_downscale + SiLU + token mean + s in one launch: u [B A, 512] (268 MB at the benchmark shape) is never written
             w2p, w2i = P.w2(Wd, Kd)
-            rc = L.pd_downscale_pool(ops.ptr(ba), w2p.data_ptr(), ops.ptr(w2i), ops.ptr(bd), ops.ptr(batch["_tok_start"]), ops.ptr(s), ops.ptr(bs),
-                                     B, A, T, Ca, Cs, tpb, sp)
+            if grp is not None:
+                rc = L.pd_downscale_pool_g(ops.ptr(ba), w2p.data_ptr(), ops.ptr(w2i), ops.ptr(bd), ops.ptr(batch["_tok_start"]), ops.ptr(s),
+                                           ops.ptr(bs), G, Bg, A, T, Ca, Cs, tpb, sp)
+            else:
+                rc = L.pd_downscale_pool(ops.ptr(ba), w2p.data_ptr(), ops.ptr(w2i), ops.ptr(bd), ops.ptr(batch["_tok_start"]), ops.ptr(s), ops.ptr(bs),
+                                         B, A, T, Ca, Cs, tpb, sp)
         if rc == -3:            # PD_ERR_UNSUPPORTED (other widths, a token of more than 64 atoms): projection, then the segment mean
             u = self.lws("dit_u", RA, Cs)
             self.lin(ba, "dit.linear_downscale", RA, out=u, act=ACT_SILU)
-            ops.check(L.pd_segment_pool(ops.ptr(u), ops.ptr(batch["_tok_start"]), ops.ptr(s), ops.ptr(bs), B, A, T, Cs, sp), "pool")
+            if grp is not None:
+                ops.check(L.pd_segment_pool_g(ops.ptr(u), ops.ptr(batch["_tok_start"]), ops.ptr(s), ops.ptr(bs), G, Bg, A, T, Cs, sp), "pool_g")
+            else:
+                ops.check(L.pd_segment_pool(ops.ptr(u), ops.ptr(batch["_tok_start"]), ops.ptr(s), ops.ptr(bs), B, A, T, Cs, sp), "pool")
         else:
             ops.check(rc, "downscale_pool")
         for b in range(nb_t):
             self.dit_block(f"dit.token_dit.blocks.{b}", bs, B, T, Cs, off(prep["token_bias"], b * ft_stride),
                            tab_t, row * ldt_ + b * 6 * Cs, ldt_, per_sample, Tr, bnd=boff(bnd_t, (row * nb_t + b) * 8), bias_prescale=pst,
-                           rows_alloc=RT)
+                           rows_alloc=RT, gkw=gkt)
         us = self.lws("dit_us", RT, Ca)
         self.lin(bs, "dit.linear_upscale", RT, out=us)
-        ops.check(L.pd_unpool_add(ops.ptr(ba), ops.ptr(us), ops.ptr(batch["atom_id_to_token_id"]), B, A, T, Ca, sp), "unpool")
+        if grp is not None:
+            ops.check(L.pd_unpool_add_g(ops.ptr(ba), ops.ptr(us), ops.ptr(batch["atom_id_to_token_id"]), G, Bg, A, T, Ca, sp), "unpool_g")
+        else:
+            ops.check(L.pd_unpool_add(ops.ptr(ba), ops.ptr(us), ops.ptr(batch["atom_id_to_token_id"]), B, A, T, Ca, sp), "unpool")
         for b in range(nb_a):
             self.dit_block(f"dit.atom_dit_decoder.blocks.{b}", ba, B, A, Ca,
                            off(prep["atom_bias"], (nb_a + b) * fa_stride), tab_a, row * lda_ + (nb_a + b) * 6 * Ca, lda_,
-                           per_sample, Ar, bnd=boff(bnd_a, (row * 2 * nb_a + nb_a + b) * 8), bias_prescale=psa, rows_alloc=RA)
+                           per_sample, Ar, bnd=boff(bnd_a, (row * 2 * nb_a + nb_a + b) * 8), bias_prescale=psa, rows_alloc=RA, gkw=gka)
         cs_b = ops.ptr(scal["c_skip"]) if per_sample else None
         co_b = ops.ptr(scal["c_out"]) if per_sample else None
         ops.check(L.pd_denoise(ops.ptr(ba), ops.ptr(x_hat), ops.ptr(P["dit.norm_r.weight"]), ops.ptr(P["dit.norm_r.bias"]),

@@ -139,6 +139,39 @@ class PhysDock(nn.Module):
         return self._engine
 
     @staticmethod
+    def _pad_masked(b, pa, pt):
+        """append `pa` MASKED atoms and `pt` MASKED tokens to the feature dict b (in place; `_prepare_batch` and `_pad_to_group`):
+        padded atoms belong to no token segment and point at token 0, padded tokens own no atoms, every mask is 0 on them"""
+        import torch.nn.functional as F
+        dev = b["ref_pos"].device
+
+        def pad(k, dims, value=0):
+            v = b[k]
+            spec = []
+            for d in range(v.dim() - 1, -1, -1):
+                spec += [0, dims.get(d, 0)]
+            b[k] = F.pad(v, spec, value=value)
+        for k in ("ref_feat", "ref_pos", "a_mask", "x_gt"):
+            pad(k, {0: pa})
+        if "x_exists" in b:
+            pad("x_exists", {0: pa})
+        pad("ap_mask", {0: pa, 1: pa})
+        b["ref_space_uid"] = torch.cat([b["ref_space_uid"], b["ref_space_uid"].max() + 1 +
+                                        torch.arange(pa, device=dev, dtype=b["ref_space_uid"].dtype)])
+        b["atom_id_to_token_id"] = torch.cat([b["atom_id_to_token_id"],
+                                              torch.zeros(pa, device=dev, dtype=b["atom_id_to_token_id"].dtype)])
+        b["token_id_to_chunk_sizes"] = torch.cat([b["token_id_to_chunk_sizes"],
+                                                  torch.zeros(pt, device=dev, dtype=b["token_id_to_chunk_sizes"].dtype)])
+        for k in ("target_feat", "key_res_feat", "pocket_res_feat", "is_ligand"):
+            pad(k, {0: pt})
+        for k in ("token_bonds_feature", "rel_tok_feat", "templ_feat", "z_mask"):
+            pad(k, {0: pt, 1: pt})
+        pad("msa_feat", {1: pt})
+        for k in ("asym_id", "sym_id", "entity_id"):
+            b[k] = torch.cat([b[k], (b[k].max() + 1).expand(pt).to(b[k].dtype)])
+        b["residue_index"] = torch.cat([b["residue_index"], torch.zeros(pt, device=dev, dtype=b["residue_index"].dtype)])
+
+    @staticmethod
     def _prepare_batch(batch):
         """Boundary bookkeeping (layout only): int32 token start offsets for the pooling kernels, fp32
         contiguity, and - for un-padded real systems whose token / atom counts are not multiples of 4
@@ -159,34 +192,7 @@ class PhysDock(nn.Module):
         #  kernels never see them - and point at token 0 where an index is needed; adding a padded TOKEN for them, as this did, turned a
         #  256-token system into 260 tokens: sample-major token rows with a remainder in every projection)
         if pa or pt:
-            import torch.nn.functional as F
-            dev = b["ref_pos"].device
-
-            def pad(k, dims, value=0):
-                v = b[k]
-                spec = []
-                for d in range(v.dim() - 1, -1, -1):
-                    spec += [0, dims.get(d, 0)]
-                b[k] = F.pad(v, spec, value=value)
-            for k in ("ref_feat", "ref_pos", "a_mask", "x_gt"):
-                pad(k, {0: pa})
-            if "x_exists" in b:
-                pad("x_exists", {0: pa})
-            pad("ap_mask", {0: pa, 1: pa})
-            b["ref_space_uid"] = torch.cat([b["ref_space_uid"], b["ref_space_uid"].max() + 1 +
-                                            torch.arange(pa, device=dev, dtype=b["ref_space_uid"].dtype)])
-            b["atom_id_to_token_id"] = torch.cat([b["atom_id_to_token_id"],
-                                                  torch.zeros(pa, device=dev, dtype=b["atom_id_to_token_id"].dtype)])
-            b["token_id_to_chunk_sizes"] = torch.cat([b["token_id_to_chunk_sizes"],
-                                                      torch.zeros(pt, device=dev, dtype=b["token_id_to_chunk_sizes"].dtype)])
-            for k in ("target_feat", "key_res_feat", "pocket_res_feat", "is_ligand"):
-                pad(k, {0: pt})
-            for k in ("token_bonds_feature", "rel_tok_feat", "templ_feat", "z_mask"):
-                pad(k, {0: pt, 1: pt})
-            pad("msa_feat", {1: pt})
-            for k in ("asym_id", "sym_id", "entity_id"):
-                b[k] = torch.cat([b[k], (b[k].max() + 1).expand(pt).to(b[k].dtype)])
-            b["residue_index"] = torch.cat([b["residue_index"], torch.zeros(pt, device=dev, dtype=b["residue_index"].dtype)])
+            PhysDock._pad_masked(b, pa, pt)
         chunk = b["token_id_to_chunk_sizes"]
         ts = torch.zeros(chunk.shape[0] + 1, dtype=torch.int32, device=chunk.device)
         ts[1:] = torch.cumsum(chunk, 0).to(torch.int32)
@@ -581,6 +587,327 @@ class PhysDock(nn.Module):
         if return_conditioning:
             return out, tuple(t.clone() for t in cond_out)
         return out
+
+    @staticmethod
+    def _pad_to_group(batches):
+        """Group padding for sample_diffusion_many: every (already `_prepare_batch`ed) system padded to the group's largest padded
+        atom and token counts with MASKED atoms / tokens, as `_prepare_batch` pads (padded atoms belong to no token segment and
+        point at token 0; padded tokens own no atoms).  The real counts are kept; a system that has the group shape is returned
+        as it is."""
+        A = max(b["ref_pos"].shape[0] for b in batches)
+        T = max(b["target_feat"].shape[0] for b in batches)
+        out = []
+        for b in batches:
+            pa, pt = A - b["ref_pos"].shape[0], T - b["target_feat"].shape[0]
+            if not (pa or pt):
+                out.append(b)
+                continue
+            b = dict(b)
+            PhysDock._pad_masked(b, pa, pt)
+            b["_tok_start"] = torch.cat([b["_tok_start"], b["_tok_start"][-1:].expand(pt)]).contiguous()
+            out.append(b)
+        return out
+
+    def _capture_lists(self, fn_lists):
+        """record (not run) each launch list as one hipGraph (as sample_diffusion's capture, with device synchronisation)"""
+        import time as _time
+        L = ops._lib.init()
+        with _CAPTURE_LOCK:
+            torch.cuda.synchronize()
+            t_cap = _time.perf_counter()
+            execs = []
+            cap = self._capture_stream if getattr(self, "_capture_stream", None) is not None else torch.cuda.Stream()
+            self._capture_stream = cap
+            with torch.cuda.stream(cap):
+                for fns in fn_lists:
+                    ops.check(L.pd_graph_begin(ops.stream()), "graph_begin")
+                    for fn, arg in fns:
+                        fn(*arg)
+                    ex = C.c_void_p()
+                    ops.check(L.pd_graph_end(ops.stream(), C.byref(ex)), "graph_end")
+                    execs.append(ex)
+            torch.cuda.synchronize()
+            self.last_capture_ms = 1e3 * (_time.perf_counter() - t_cap)
+        return execs
+
+    @torch.no_grad()
+    def sample_diffusion_many(self, batches, num_sample=5, steps=200, gamma_0=0.8, gamma_min=1.0, noise_scale_lambda=1.003,
+                              step_scale_eta=1.5, align_ref_pos=True, karras_noise_schedule_power=7, *,
+                              ode_step_scale_eta=1.0, mmff_gamma_0_factor=1.0, ref_mol_poses=None, ref_mol=None,
+                              mmff_iters=5, seeds=None, sample_offsets=None, noises=None, conditionings=None,
+                              return_conditioning=False, use_graph=True, mmff_backend="auto", relax_fn=None):
+        """`sample_diffusion` for several systems in ONE step loop: G systems x num_sample samples run every denoiser launch
+        together as G num_sample rows (the row-wise launches), through grouped launches (attention: one bias set and real key count
+        per system; pooling, unpooling and the preconditioning: per-system tables), so that rounds of few samples fill the chip.
+        Returns a list of [num_sample, A_real_g, 3] in input order (with return_conditioning: (that list, list of (a, ap, s, z))).
+
+        Shared across the group: the schedule and its scalars, num_sample, align_ref_pos, noise_scale_lambda.  Per system (a scalar
+        or a list): ode_step_scale_eta, mmff_gamma_0_factor; lists with None entries: ref_mol_poses, ref_mol, noises (dicts as
+        sample_diffusion's noise=; all or none), conditionings (each (a, ap, s, z) at the GROUP's padded shape - as
+        return_conditioning=True returns them - not at the shape sample_diffusion gives a smaller system alone); seeds /
+        sample_offsets (ints).  Each system draws exactly the
+        random numbers of its own sample_diffusion call and gets its own physics tail.  Systems are padded (masked atoms / tokens)
+        to the group's largest padded shape.  Host-side relaxation (an RDKit molecule on the host backend, relax_fn=) would break
+        the loop once per system and step: ValueError; the device MMFF relaxation (mmff.MMFFTerms) is supported."""
+        from . import physics
+        batches = list(batches)
+        G = len(batches)
+        if G == 0:
+            return ([], []) if return_conditioning else []
+
+        def per(v, name, lists_only=False):
+            if isinstance(v, (list, tuple)):
+                if len(v) != G:
+                    raise ValueError(f"sample_diffusion_many: {name} has {len(v)} entries for {G} systems")
+                return list(v)
+            if lists_only and v is not None:
+                raise ValueError(f"sample_diffusion_many: {name} must be a list with one entry per system (None entries allowed)")
+            return [v] * G
+        etas = [float(v) for v in per(ode_step_scale_eta, "ode_step_scale_eta")]
+        facs = [float(v) for v in per(mmff_gamma_0_factor, "mmff_gamma_0_factor")]
+        poses_in = per(ref_mol_poses, "ref_mol_poses", True)
+        mols = per(ref_mol, "ref_mol", True)
+        seeds_ = [int(v) for v in per(0 if seeds is None else seeds, "seeds")]
+        offs = [int(v) for v in per(0 if sample_offsets is None else sample_offsets, "sample_offsets")]
+        noises_ = per(noises, "noises", True)
+        conds_in = per(conditionings, "conditionings", True)
+        if any(n is None for n in noises_) and any(n is not None for n in noises_):
+            raise ValueError("sample_diffusion_many: noises must be given for every system or for none")
+        if relax_fn is not None:
+            raise ValueError("sample_diffusion_many: relax_fn= relaxes on the host - one host break per system and step would "
+                             "serialise the group; use sample_diffusion for it (or an mmff.MMFFTerms ref_mol: device relaxation)")
+        relaxers = [physics.resolve_relaxer(m, None, mmff_backend) for m in mols]
+        for r in relaxers:
+            if r.kind == "host":
+                raise ValueError("sample_diffusion_many: this ref_mol relaxes on the host (RDKit backend) - one host break per "
+                                 "system and step would serialise the group; pass an mmff.MMFFTerms table (device relaxation) or "
+                                 "use sample_diffusion")
+        device = batches[0]["x_gt"].device
+        eng = self.engine(device)
+        if eng.ws.nbytes() > self.workspace_limit_bytes:
+            self.release_workspace()
+        bats = self._pad_to_group([self._prepare_batch(b) for b in batches])
+        L = ops._lib.init()
+        ws = eng.ws
+        B = num_sample
+        A, T = bats[0]["ref_pos"].shape[0], bats[0]["target_feat"].shape[0]
+        Ars = [int(b["_A_real"]) for b in bats]
+        Trs = [int(b["_T_real"]) for b in bats]
+        sp = ops.stream()
+        if B <= 0:
+            outs = [torch.empty(0, ar, 3, device=device) for ar in Ars]
+            return (outs, [None] * G) if return_conditioning else outs
+        noise_mode = noises_[0] is not None
+        plans = []
+        for g in range(G):
+            sig, plan = self._step_plan(steps, gamma_0, gamma_min, step_scale_eta, etas[g], facs[g], align_ref_pos,
+                                        karras_noise_schedule_power)
+            for p in plan:
+                p["mmff"] = bool(p["mmff"] and not p["align"] and relaxers[g].kind != "none")
+            plans.append(plan)
+        plan0 = plans[0]
+
+        # ---- conditioning per system (the trunk's outputs are shape-keyed workspace buffers: each is consumed before the next runs)
+        tau = ws.get("tau", steps)
+        tau.copy_(torch.tensor([p["tau"] for p in plan0], dtype=torch.float32))
+        memo = {}
+        cond_out = [None] * G
+
+        for g, c in enumerate(conds_in):
+            if c is not None and tuple(int(t.shape[0]) for t in c) != (A, A * A, T, T * T):
+                raise ValueError(f"sample_diffusion_many: conditionings[{g}] has (a, ap, s, z) for another shape than the group's padded "
+                                 f"{A} atoms / {T} tokens (a conditioning is only reusable by a group that pads the system the same "
+                                 f"way: take it from sample_diffusion_many(return_conditioning=True) on the same group)")
+
+        def cond_of(g):
+            if g not in memo:
+                c = conds_in[g] if conds_in[g] is not None else eng.conditioning(bats[g])
+                memo.clear()
+                memo[g] = c
+                if return_conditioning:
+                    cond_out[g] = tuple(t.clone() for t in c)
+            return memo[g]
+        ck = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min))
+        if _BOUND_CHECK and ops.F16_GEMM and ops.SPLIT_GEMM and ck not in eng._bounds_checked:
+            # the once-per-(weights, schedule) check of sample_diffusion, on the first system
+            if ck in eng._bounds_failed:
+                raise eng._bounds_failed[ck]
+            a0, ap0, s0, z0 = cond_of(0)
+            prep0 = eng.prepare_dit(a0, ap0, s0, z0, bats[0], tau, B=B)
+            try:
+                switched = eng.check_dit_bounds(bats[0], a0, s0, prep0, plan0, B, float(self.sigma_data))
+            except FloatingPointError as e:
+                eng._bounds_failed[ck] = e
+                raise
+            eng._bounds_checked.add(ck)
+            if switched:
+                self._drop_graphs()
+        prep = eng.prepare_dit_many(cond_of, bats, tau, B)
+        memo.clear()
+        a_g, s_g = prep["a"], prep["s"]
+
+        # ---- the group descriptor and every per-system input of the loop, staged in shape-keyed workspace buffers (graphs replay
+        #      raw addresses)
+        def stacked(name, ts, dtype=None):
+            buf = ws.get("grp:" + name, G, *ts[0].shape, dtype=dtype or ts[0].dtype)
+            for g, t in enumerate(ts):
+                buf[g].copy_(t)
+            return buf
+        tok_start = stacked("tok_start", [b["_tok_start"] for b in bats])
+        a2t = stacked("a2t", [b["atom_id_to_token_id"] for b in bats])
+        a_mask = stacked("a_mask", [b["a_mask"] for b in bats])
+        ref_pos = stacked("ref_pos", [b["ref_pos"] for b in bats])
+        nk_a = stacked("nk_atom", [torch.tensor(v, dtype=torch.int32) for v in Ars])
+        nk_t = stacked("nk_token", [torch.tensor(v, dtype=torch.int32) for v in Trs])
+        tpbs = [int(b["_pool_tpb"]) for b in bats]
+        gbatch = {"_A_real": max(Ars), "_T_real": max(Trs), "_pool_tpb": 0 if min(tpbs) <= 0 else min(tpbs),
+                  "_tok_start": tok_start, "atom_id_to_token_id": a2t}
+        grp = {"G": G, "B": B, "nk_atom": nk_a, "nk_token": nk_t}
+        lig_ws = []
+        for g, b in enumerate(bats):
+            lf = b["is_ligand"][b["atom_id_to_token_id"]].clone()
+            lf[Ars[g]:] = 0
+            lig_ws.append(b["a_mask"] * lf)
+        lig_w = stacked("lig_w", lig_ws)
+        x_a = ws.get("grp:x_a", G * B, A, 3)
+        x_hat = ws.get("grp:x_hat", G * B, A, 3)
+        x_den = ws.get("grp:x_den", G * B, A, 3)
+        x_proj = ws.get("grp:x_proj", G * B, A, 3)
+        any_align = [any(p["align"] for p in pl) for pl in plans]
+        any_mmff = [any(p["mmff"] for p in pl) for pl in plans]
+        bref = ws.get("grp:bref", G * B, A, 3) if any(any_align) else None
+        x_ref = ws.get("grp:x_ref", G * B, A, 3) if any(any_mmff) else None
+        phys = []                                 # per system: lig_idx, poses, ref_dist, tm_eps, n_lig, n_conf, mmff tables / scratch
+        for g in range(G):
+            d = {"poses": None, "n_lig": 0, "n_conf": 0}
+            if (any_align[g] and poses_in[g] is not None) or any_mmff[g]:
+                li = torch.nonzero(lig_ws[g] > 0).flatten().to(torch.int32)
+                d["n_lig"] = int(li.numel())
+                d["lig_idx"] = ws.get(f"grp{g}:lig_idx", *li.shape, dtype=li.dtype)
+                d["lig_idx"].copy_(li)
+            if any_align[g] and poses_in[g] is not None and poses_in[g].shape[1] == d["n_lig"]:
+                pz = poses_in[g].to(device).float()
+                d["poses"] = ws.get(f"grp{g}:poses", *pz.shape)
+                d["poses"].copy_(pz)
+                d["n_conf"] = n_conf = pz.shape[0]
+                d["ref_dist"] = ws.get(f"grp{g}:ref_dist", n_conf, d["n_lig"], d["n_lig"])
+                d["tm_eps"] = ws.get(f"grp{g}:tm_eps", B, n_conf)
+                ops.check(L.pd_pose_dist(ops.ptr(d["poses"]), ops.ptr(d["ref_dist"]), n_conf, d["n_lig"], sp), "pose_dist")
+            if any_mmff[g]:
+                if d["n_lig"] == 0:
+                    raise ValueError(f"ref_mol given but system {g}'s crop has no ligand atoms")
+                d["mm"] = relaxers[g].terms.device_tables(device, d["n_lig"])
+                d["mm_ws"] = ws.get(f"grp{g}:mmff_ws", relaxers[g].terms.workspace_numel(B), dtype=torch.float64)
+            phys.append(d)
+
+        # ---- random numbers: per system, exactly the draws of its own sample_diffusion call
+        n_noisy = sum(p["noisy"] for p in plan0)
+        k_noisy = [sum(q["noisy"] for q in plan0[:i]) for i in range(steps)]
+        if noise_mode:
+            n_init = ws.get("grp:n_init", G * B, A, 3, zero=True)
+            n_rot = ws.get("grp:n_rot", G, steps, 4, B)
+            n_tr = ws.get("grp:n_trans", G, steps, B, 3)
+            n_dif = ws.get("grp:n_diffuse", G, max(n_noisy, 1), B, A, 3, zero=True)
+            for g, nz in enumerate(noises_):
+                n_init[g * B:(g + 1) * B, :Ars[g]].copy_(nz["init"])
+                n_rot[g].copy_(nz["rot_u"])
+                n_tr[g].copy_(nz["trans"])
+                if n_noisy:
+                    n_dif[g, :n_noisy, :, :Ars[g]].copy_(nz["diffuse"])
+        else:
+            seed_buf = ws.get("grp:seed", G, dtype=torch.int64)
+            seed_buf.copy_(torch.tensor(seeds_, dtype=torch.int64))
+        xo = [g * B * A * 3 for g in range(G)]
+
+        def step_head(i):
+            p = plan0[i]
+            sp_ = ops.stream()
+            for g in range(G):
+                if i == 0 and any_align[g]:
+                    bref[g * B:(g + 1) * B].copy_(ref_pos[g][None].expand(B, A, 3))
+                if noise_mode:
+                    ru, tr = off(n_rot, (g * steps + i) * 4 * B), off(n_tr, (g * steps + i) * B * 3)
+                    nz = off(n_dif, ((g * max(n_noisy, 1) + k_noisy[i]) * B) * A * 3) if p["noisy"] else None
+                    sd_ptr = None
+                    src, x_scale = (off(n_init, xo[g]), float(sig[0])) if i == 0 else (off(x_a, xo[g]), 1.0)
+                else:
+                    ru = tr = nz = None
+                    sd_ptr = seed_buf.data_ptr() + 8 * g
+                    src, x_scale = off(x_a, xo[g]), 1.0
+                    if i == 0:
+                        ops.check(L.pd_init_noise(off(x_a, xo[g]), sd_ptr, offs[g], float(sig[0]), B, A, sp_), "init_noise")
+                ops.check(L.pd_augment(src, x_scale, off(a_mask, g * A), ru, tr, nz, float(noise_scale_lambda),
+                                       p["sdev"], sd_ptr, i, offs[g], off(x_hat, xo[g]), B, A, sp_), "augment")
+            eng.af3_dit(gbatch, x_hat, x_den, a_g, s_g, prep, G * B, p, row=i, grp=grp)
+
+        def step_tail(i, g):
+            p = plans[g][i]
+            d = phys[g]
+            sp_ = ops.stream()
+            xd, xh, xp, xa = off(x_den, xo[g]), off(x_hat, xo[g]), off(x_proj, xo[g]), off(x_a, xo[g])
+            lw = off(lig_w, g * A)
+            if p["align"]:
+                if d["poses"] is not None:
+                    ops.check(L.pd_template_match(xd, ops.ptr(d["lig_idx"]), ops.ptr(d["ref_dist"]), ops.ptr(d["poses"]),
+                                                  off(bref, xo[g]), ops.ptr(d["tm_eps"]), None, B, A, d["n_lig"], d["n_conf"], sp_),
+                              "template_match")
+                target = off(bref, xo[g])
+            elif p["mmff"]:
+                relaxers[g].terms.launch_relax(d["mm"], x_den[g * B:(g + 1) * B], d["lig_idx"], x_ref[g * B:(g + 1) * B], d["mm_ws"],
+                                               B, A, int(mmff_iters), sp_)
+                target = off(x_ref, xo[g])
+            else:
+                ops.check(L.pd_euler(xh, xd, None, None, p["t_hat"], p["eta"], p["dt"], xa, B, A, sp_), "euler")
+                return
+            ops.check(L.pd_kabsch_align(xd, off(a_mask, g * A), target, A * 3, lw, xp, B, A, sp_), "kabsch")
+            ops.check(L.pd_euler(xh, xd, xp, lw, p["t_hat"], p["eta"], p["dt"], xa, B, A, sp_), "euler")
+
+        # ---- the loop as units (sample_diffusion): one head per step for the whole group, one tail per step and system slot
+        sched_id = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min), float(karras_noise_schedule_power))
+        common = ("many", G, B, A, T, tuple(Ars), tuple(Trs), gbatch["_pool_tpb"], sched_id, noise_mode, float(noise_scale_lambda),
+                  tuple(offs))
+        units = []
+        for i, p in enumerate(plan0):
+            units.append(((common, "H", i, p["noisy"], p["sdev"], p["t_hat"], tuple(i == 0 and al for al in any_align)),
+                          [(step_head, (i,))], None))
+            for g in range(G):
+                q, r = plans[g][i], relaxers[g]
+                pool_sig = phys[g]["poses"] is not None and (phys[g]["n_conf"], phys[g]["n_lig"])
+                relax_sig = (r.kind, r.kind == "device" and r.terms.signature(), int(mmff_iters), phys[g]["n_lig"])
+                kind = ("align", pool_sig) if q["align"] else (("mmff", relax_sig) if q["mmff"] else ("plain",))
+                units.append(((common, "T", g, i, q["t_hat"], q["eta"], q["dt"], kind), [(step_tail, (i, g))],
+                              r.terms if q["mmff"] else None))
+        fresh = not use_graph
+        missing = []
+        for ukey, fns, terms in units:
+            u = self._units.get(ukey) if use_graph else None
+            if u is not None:
+                self._units[ukey] = self._units.pop(ukey)          # LRU order
+                ops.check(L.pd_graph_launch(u["exec"], sp), "graph_launch")
+            else:
+                fresh = True
+                for fn, arg in fns:
+                    fn(*arg)
+                if use_graph:
+                    missing.append((ukey, fns, terms))
+        self.last_unit_misses = len(missing)
+        self.last_head_misses = sum(1 for k, _, _ in missing if k[1] == "H")
+        if missing:
+            # (a unit keeps the MMFF table object whose device tables it captured alive, as in sample_diffusion)
+            for (ukey, _, terms), ex in zip(missing, self._capture_lists([fns for _, fns, _ in missing])):
+                self._units[ukey] = {"exec": ex, "terms": terms}
+            self.unit_captures += len(missing)
+            while len(self._units) > self.max_cached_units:
+                L.pd_graph_destroy(self._units.pop(next(iter(self._units)))["exec"])
+        outs = [x_a[g * B:(g + 1) * B, :Ars[g]].clone() for g in range(G)]
+        if (_CHECK_FINITE or fresh) and not all(bool(torch.isfinite(o).all()) for o in outs):
+            if use_graph:
+                self._drop_graphs()
+            raise FloatingPointError("sample_diffusion_many produced non-finite coordinates: an fp16-format operand bound was violated "
+                                     "(rebuild the engine after changing weights; ops.F16_GEMM / F16_ATTN = False to confirm)")
+        if return_conditioning:
+            return outs, cond_out
+        return outs
 
     @torch.no_grad()
     def forward(self, batch):

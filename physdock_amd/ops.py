@@ -466,10 +466,12 @@ def unsplit_f16_attention(variant):
 
 def attention(Q, K, V, O, *, nq, nk, nbatch, nheads, q_strides, k_strides, v_strides, o_strides, bias=None,
               scale=1.0 / math.sqrt(32.0), ws=None, bias_nk=0, f16_amax=None, O2=None, query_only=False,
-              KV2=None, kv2_strides=None, bias_prescale=0.0):
+              KV2=None, kv2_strides=None, bias_prescale=0.0, group_samples=0, bias_gstride=0, nk_group=None):
     """strides = (batch_stride, seq_stride) in floats; Q/K/V/O tensors or raw addresses.  ws: optional float scratch
     tensor (attn_split_ws_numel) enabling key-split launches for small grids.  bias_nk: key count the bias buffer was laid
-    out for (the padded count when nk is the real one)."""
+    out for (the padded count when nk is the real one).  Grouped launches (several systems, ABI 10): runs of `group_samples`
+    batches share one bias set, `bias_gstride` floats apart; `nk_group` (device int32 [G] or address) holds each group's real
+    key count, bounded by nk."""
     def P(x):
         return x if (x is None or isinstance(x, int)) else ptr(x)
     a = AttnArgs()
@@ -483,6 +485,7 @@ def attention(Q, K, V, O, *, nq, nk, nbatch, nheads, q_strides, k_strides, v_str
     a.bias = P(bias)
     a.scale = scale
     a.bias_nk = bias_nk
+    a.group_samples, a.bias_gstride, a.nk_group = int(group_samples), int(bias_gstride), P(nk_group)
     a.bias_prescale = (float(bias_prescale) if bias is not None else 0.0) if PIPE_ATTN else -1.0
     a.fp32_mfma = 0 if SPLIT_ATTN else 1
     if f16_amax is not None and F16_ATTN:      # (max|q|, max|k|, max|v|) upper bounds: three floats by value, or a device tensor [3]
