@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define PD_ABI_VERSION 10
+#define PD_ABI_VERSION 11
 
 enum { PD_OUT_ROWMAJOR = 0, PD_OUT_TRANSPOSED = 1, PD_OUT_OPM = 2, PD_OUT_BIASFRAG = 3 };
 
@@ -487,6 +487,34 @@ int pd_mmff_energy_grad(const pd_mmff_terms* terms, const double* pos, double* e
  * ws: B * (9 L^2 + 24 L) float64 of scratch (inverse Hessian + BFGS vectors per sample)                            */
 int pd_mmff_relax(const pd_mmff_terms* terms, const float* x, const int* lig_idx, float* x_ref, double* ws,
                   long long ws_doubles, int B, int A, int max_iters, void* stream);
+
+/* ---- loss terms of the training-time forward (loss.hip; ABI 11) -----------------------------
+ * The five terms of PhysDockLoss (models/loss.py:576-625), forward only, fp32 in, one fp32 scalar out per term.  No [B,A,A],
+ * [B,T,T] or [T,T,bins] intermediate is written: pairs are formed in registers and reduced per block into `ws`, a second pass
+ * adds the partial sums in a fixed order in float64 (the same bits on every call, no floating-point atomics).
+ * `ws` holds at least pd_loss_workspace_numel(B, A, T) floats (= max(n (n + 1) / 2 * (B + 1) with n = ceil(A / 64), 2 T B,
+ * 2 ceil(T^2 / 256), B)); the launchers may share it when they run on one stream.  Index arrays are int64 (torch.long).
+ * pd_loss_smooth_lddt  : smooth_lddt_loss (loss.py:162-181)   mean_b sum_ij m_ij eps(|d_pred - d_gt|) / (1e-9 + sum m_ij),
+ *                        m_ij = (d_gt < max_clamp_distance) exists_i exists_j, eps(d) = 1/4 sum_c sigmoid(d - c), c = .5, 1, 2, 4
+ * pd_loss_centre_pairs : bond_loss (loss.py:245-318) -> out[0] and key_res_loss (loss.py:535-559) -> out[1] in one pass over the
+ *                        centre-atom pairs: mean_b scale_b(sigma) * mean_b sum_ij mask_ij f(diff_ij) / (sum mask + eps)
+ * pd_loss_distogram    : distogram_loss (loss.py:78-115); boundaries_sq = linspace(min_bin, max_bin, no_bins - 1) ** 2 from the
+ *                        host (the reference's own expression); no_bins <= 63
+ * pd_loss_weighted_mse : weighted_mse_loss (loss.py:118-159) after the alignment: x_gt_aligned [B,A,3] is the output of
+ *                        pd_kabsch_align(x_denoised, x_exists, x_gt, 0, weights).  As the reference computes it: sigma_data = 16
+ *                        whatever the configuration says, scale (t^2 + 16^2) / (16 t)^2 / 3, clamped at 10000               */
+int pd_loss_workspace_numel(int B, int A, int T);
+int pd_loss_smooth_lddt(const float* x_denoised, const float* x_gt, const float* x_exists, float max_clamp_distance, float* ws,
+                        float* out, int B, int A, void* stream);
+int pd_loss_centre_pairs(const float* x_denoised, const float* x_gt, const long long* token_id_to_centre_atom_id,
+                         const float* token_bonds, const float* is_key_res, const float* is_ligand, const float* t_hat,
+                         float sigma_data_bond, float sigma_data_key, float eps, float* ws, float* out, int B, int A, int T,
+                         void* stream);
+int pd_loss_distogram(const float* p_distogram, const float* x_gt, const float* x_exists,
+                      const long long* token_id_to_pseudo_beta_atom_id, const float* boundaries_sq, int no_bins, float* ws,
+                      float* out, int A, int T, void* stream);
+int pd_loss_weighted_mse(const float* x_denoised, const float* x_gt_aligned, const float* weights, const float* t_hat, float* ws,
+                         float* out, int B, int A, void* stream);
 
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);

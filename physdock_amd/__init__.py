@@ -14,3 +14,4 @@ from .model import PhysDock, weighted_rigid_align  # noqa: F401
 from .confidence import ConfidenceModule  # noqa: F401  (reference layers/confidence_module.py)
 from .params import param_shapes, seeded_state_dict  # noqa: F401
 from .driver import redock, redock_many  # noqa: F401  (multi-round caller of the sampler, reference redocking.py:156-342)
+from .loss import PhysDockLoss  # noqa: F401  (reference models/loss.py:576-625, forward values; csrc/loss.hip)

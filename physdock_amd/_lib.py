@@ -213,6 +213,11 @@ def _declare(L):
     sig("pd_chirality", p, p, p, p, p, i, i, i, p)
     sig("pd_ligand_gather", p, p, p, i, i, i, p)
     sig("pd_ligand_scatter", p, p, p, p, i, i, i, p)
+    sig("pd_loss_workspace_numel", i, i, i)                                          # ABI 11 (loss.hip)
+    sig("pd_loss_smooth_lddt", p, p, p, f, p, p, i, i, p)
+    sig("pd_loss_centre_pairs", p, p, p, p, p, p, p, f, f, f, p, p, i, i, i, p)
+    sig("pd_loss_distogram", p, p, p, p, p, i, p, p, i, i, p)
+    sig("pd_loss_weighted_mse", p, p, p, p, p, p, i, i, p)
 
 
 def ptr(t):

@@ -57,6 +57,12 @@ def PhysDockConfig(
         max_msa_clusters=128,
         token_bond_threshold=2.4,
         sigma_data=16.,
+        # loss weights (reference configs.py:12-16, names as spelt there)
+        alpha_confifdence=1e-4,
+        alpha_diffusion=4,
+        alpha_bond=0,
+        alpha_distogram=3e-2,
+        alpha_pae=0,
         # extension (not in the reference): override channel widths / depths, used by
         # the small-dimension parity fixtures.  Keys: c_m c_s c_z c_a c_ap and
         # no_blocks_atom no_blocks_evoformer no_blocks_pairformer no_blocks_dit
@@ -107,6 +113,19 @@ def PhysDockConfig(
                 "no_blocks_heads": dims.get("no_blocks_heads", nb_heads),
                 "no_blocks_atom": dims["no_blocks_atom"],
             },
+        },
+        # reference configs.py:152-193: field names and defaults are the schema physdock_amd.PhysDockLoss reads (the three confidence
+        # blocks are kept for the schema; the reference's loss class has them commented out)
+        "loss": {
+            "weighted_mse_loss": {"weight": alpha_diffusion, "sigma_data": sigma_data,
+                                  "alpha_dna": 5.0, "alpha_rna": 5.0, "alpha_ligand": 10.0},
+            "smooth_lddt_loss": {"weight": alpha_diffusion, "max_clamp_distance": 15.},
+            "bond_loss": {"weight": alpha_diffusion * alpha_bond, "sigma_data": sigma_data},
+            "key_res_loss": {"weight": alpha_diffusion * alpha_bond, "sigma_data": sigma_data},
+            "distogram_loss": {"weight": alpha_distogram, "min_bin": 3.25, "max_bin": 50.75, "no_bins": 39, "eps": 1e-9},
+            "plddt_loss": {"weight": alpha_confifdence, "no_bins": 50},
+            "pae_loss": {"weight": alpha_confifdence * alpha_pae},
+            "pde_loss": {"weight": alpha_confifdence, "min_bin": 0, "max_bin": 32, "no_bins": 64},
         },
     }
     return ConfigDict(cfg)

@@ -910,10 +910,13 @@ class PhysDock(nn.Module):
         return outs
 
     @torch.no_grad()
-    def forward(self, batch):
+    def forward(self, batch, return_loss=False):
         """reference models/model.py:99-115 (training-time forward; kept for API completeness):
-        conditioning -> 48 noised copies (per-sample noise level) -> denoiser -> distogram logits."""
+        conditioning -> 48 noised copies (per-sample noise level) -> denoiser -> distogram logits.
+        return_loss=True: returns (outputs, cum_loss, losses) with `cum_loss, losses = PhysDockLoss(config)(outputs, batch)`
+        (physdock_amd.loss; `batch` then also carries the reference's loss features, in its real - un-padded - sizes)."""
         device = batch["x_gt"].device
+        feats = batch
         eng = self.engine(device)
         if eng.ws.nbytes() > self.workspace_limit_bytes:
             self.release_workspace()
@@ -942,8 +945,13 @@ class PhysDock(nn.Module):
         x_den = ws.get("fw_xden", B, A, 3)
         eng.af3_dit(batch, x_hat, x_den, a, s, prep, B, scal, row=0, per_sample=True)
         pd = eng.lin(z, "linear_distogram", T * T).reshape(T, T, -1)[:T_real, :T_real]
-        return {"x_denoised": x_den[:, :A_real].clone(), "x_hat": x_hat[:, :A_real].clone(), "t_hat": t_hat,
-                "p_distogram": pd + pd.transpose(0, 1)}
+        outputs = {"x_denoised": x_den[:, :A_real].clone(), "x_hat": x_hat[:, :A_real].clone(), "t_hat": t_hat,
+                   "p_distogram": pd + pd.transpose(0, 1)}
+        if not return_loss:
+            return outputs
+        from .loss import PhysDockLoss
+        cum_loss, losses = PhysDockLoss(self.config)(outputs, feats)
+        return outputs, cum_loss, losses
 
 
 def weighted_rigid_align(x_pred, x_gt, weights):

@@ -334,3 +334,132 @@ def replay_draws(seed, B, steps, A, n_noisy):
         torch.set_rng_state(state)
     return {"init": init, "rot_u": torch.stack(rot), "trans": torch.stack(trans),
             "diffuse": torch.stack(dif) if dif else torch.zeros(0, B, A, 3)}
+
+
+def loss_features(batch, seed=0, n_dna=0, n_rna=0, n_key=6, masked_atoms=(), bonds=True):
+    """The reference's loss features (models/loss.py keyword names) that `make_batch` does not carry, derived from a batch:
+    centre / pseudo-beta atom of every token (second / fifth atom of a residue, the atom itself for one-atom tokens), token
+    bonds (the ligand graph), DNA / RNA flags on the first protein tokens, `n_key` key residues, and `x_exists` with the
+    atoms `masked_atoms` switched off.  Returns a new dict: the batch plus these keys."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    chunk = batch["token_id_to_chunk_sizes"].long()
+    T = chunk.shape[0]
+    start = torch.cumsum(chunk, 0) - chunk
+    is_lig = batch["is_ligand"].float()
+    n_prot = int((is_lig == 0).sum())
+    out = dict(batch)
+    out["token_id_to_centre_atom_id"] = start + torch.clamp(chunk - 1, max=1)
+    out["token_id_to_pseudo_beta_atom_id"] = start + torch.clamp(chunk - 1, max=4)
+    out["token_bonds"] = batch["token_bonds_feature"].float().clone() if bonds else torch.zeros(T, T)
+    is_dna, is_rna = torch.zeros(T), torch.zeros(T)
+    is_dna[:n_dna] = 1.0
+    is_rna[n_dna:n_dna + n_rna] = 1.0
+    out["is_dna"], out["is_rna"] = is_dna, is_rna
+    key = torch.zeros(T)
+    if n_key:
+        key[torch.randperm(n_prot, generator=g)[:n_key]] = 1.0
+    out["is_key_res"] = key
+    ex = torch.ones(batch["x_gt"].shape[0])
+    for a in masked_atoms:
+        ex[a] = 0.0
+    out["x_exists"] = ex
+    return out
+
+
+def hashed_uniform(n, seed):
+    """n float32 values in (-0.5, 0.5) from a counter hash (splitmix64) in integer arithmetic only: the same bits on every
+    machine and library version, which a seeded normal draw (log / cos inside) is not.  The loss fixtures store checksums of
+    arrays too large to commit and rebuild them from this."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        z = np.arange(n, dtype=np.uint64) + np.uint64(seed + 1) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(40)).astype(np.float32) + np.float32(0.5)) * np.float32(2.0 ** -24) - np.float32(0.5)
+
+
+def loss_outputs(feats, B, seed=0, t_hat=None):
+    """Stand-in for the `outputs` of `PhysDock.forward` at B samples: per-sample noise levels t_hat drawn as the reference draws
+    them (model.py:87-97) unless given, x_denoised = x_gt + 0.1 t_hat u with u uniform of unit variance, symmetric uniform
+    distogram logits in (-4, 4).  Given t_hat and x_gt, the result is bit-identical everywhere (hashed_uniform)."""
+    import numpy as np
+    A, T = feats["x_gt"].shape[0], feats["is_ligand"].shape[0]
+    if t_hat is None:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(seed)
+        t_hat = torch.exp(torch.randn(B, generator=g) * 1.5 - 1.2) * 16.0
+    t_hat = t_hat.float()
+    u = torch.from_numpy(hashed_uniform(B * A * 3, 2 * seed).reshape(B, A, 3)) * np.float32(3.4641016)
+    xd = feats["x_gt"].float()[None] + u * (t_hat * np.float32(0.1))[:, None, None]
+    pd = torch.from_numpy(hashed_uniform(T * T * 39, 2 * seed + 1).reshape(T, T, 39)) * np.float32(4.0)
+    return {"x_denoised": xd, "t_hat": t_hat, "p_distogram": pd + pd.transpose(0, 1)}
+
+
+LOSS_FEAT_KEYS = ("x_gt", "x_exists", "atom_id_to_token_id", "token_id_to_centre_atom_id", "token_id_to_pseudo_beta_atom_id",
+                  "token_bonds", "is_dna", "is_rna", "is_ligand", "is_key_res")
+LOSS_OUT_KEYS = ("x_denoised", "t_hat", "p_distogram")
+
+
+def clear_thresholds(feats, clamp=15.0, min_bin=3.25, max_bin=50.75, no_bins=39, margin=3e-5, seed=0):
+    """Nudge (by ~0.01 A, seeded) the few atoms of x_gt that form a pair within a relative `margin` of a decision threshold of
+    the loss - the smooth-lDDT clamp on the distance, a distogram bin edge on the squared pseudo-beta distance - until no such
+    pair is left: among 4e6 pairs a few always are, and two fp32 implementations may put them on either side."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    x = feats["x_gt"].numpy().astype(np.float32).copy()
+    pb = feats["token_id_to_pseudo_beta_atom_id"].numpy()
+    b2 = np.linspace(min_bin, max_bin, no_bins - 1) ** 2
+    for _ in range(200):
+        x64 = x.astype(np.float64)
+        d = np.sqrt(((x64[:, None] - x64[None]) ** 2).sum(-1))
+        bad = set(np.nonzero(np.abs(d - clamp) < margin * clamp)[1].tolist())
+        d2 = ((x64[pb][:, None] - x64[pb][None]) ** 2).sum(-1)
+        bad |= set(pb[np.nonzero((np.abs(d2[..., None] - b2) < margin * b2).any(-1))[1]].tolist())
+        if not bad:
+            out = dict(feats)
+            out["x_gt"] = torch.from_numpy(x)
+            return out
+        for a in sorted(bad):
+            x[a] += (0.01 * rng.randn(3)).astype(np.float32)
+    raise RuntimeError("could not clear the decision thresholds")
+
+
+def loss_case(name, B_cfg1=48, stored=None):
+    """(outputs, feats, note) of the loss fixture tests/golden/g15_loss_<name>.npz (tools/make_golden_loss.py).  A fixture
+    stores its features and t_hat and, where they fit, the other outputs; with `stored` (the loaded fixture) the arrays too
+    large to commit ([48, 2048, 3], [T, T, 39]) are rebuilt from the stored ones, bit for bit (loss_outputs)."""
+    if stored is not None:
+        f = {k: torch.from_numpy(stored[k]) for k in LOSS_FEAT_KEYS}
+        seed = {"small": 2, "ragged": 5, "cfg1": 7, "degenerate": 10, "nan": 13}[name]
+        o = loss_outputs(f, int(stored["t_hat"].shape[0]), seed=seed, t_hat=torch.from_numpy(stored["t_hat"]))
+        o = {k: (torch.from_numpy(stored[k]) if k in stored else o[k]) for k in LOSS_OUT_KEYS}
+        return o, f, str(stored["note"])
+    note = ""
+    if name == "small":             # the small test configuration's shape (T = 24, A = 96)
+        f = loss_features(make_batch(18, 5, 6, 8, seed=0), seed=1, n_dna=2, n_rna=2, n_key=4, masked_atoms=(7,))
+        o = loss_outputs(f, 4, seed=2)
+    elif name == "ragged":          # T = 221, A = 1805: multiples of no tile size
+        f = clear_thresholds(loss_features(make_batch(198, 9, 23, 8, seed=3), seed=4, n_dna=5, n_rna=7, n_key=6, masked_atoms=(11, 900)))
+        assert f["x_gt"].shape[0] == 1805 and f["is_ligand"].shape[0] == 221
+        o = loss_outputs(f, 5, seed=5)
+    elif name == "cfg1":            # T = 256, A = 2048
+        f = clear_thresholds(loss_features(make_batch(224, 9, 32, 8, seed=0), seed=6, n_dna=0, n_rna=0, n_key=6))
+        o = loss_outputs(f, B_cfg1, seed=7)
+        note = f"B = {B_cfg1}"
+    elif name == "degenerate":      # no token bonds, no key residues: the eps denominators
+        f = loss_features(make_batch(18, 5, 6, 8, seed=8), seed=9, n_key=0, bonds=False)
+        o = loss_outputs(f, 4, seed=10)
+    elif name == "nan":             # a NaN in one sample: the reference's skip-and-warn path
+        f = loss_features(make_batch(18, 5, 6, 8, seed=11), seed=12, n_dna=2, n_rna=2, n_key=4)
+        o = loss_outputs(f, 4, seed=13)
+        o["x_denoised"][2, int(f["token_id_to_centre_atom_id"][-1]), 1] = float("nan")
+        note = ("x_denoised[2, centre atom of the last (ligand) token, 1] = NaN.  On the CPU the reference's weighted_mse_loss raises "
+                "(torch.linalg.svd refuses the non-finite matrix) - recorded as NaN with ref_raised set - and PhysDockLoss with it; "
+                "ref_loss is the weighted sum of the terms the reference does return as finite")
+    else:
+        raise ValueError(name)
+    f = {k: f[k] for k in LOSS_FEAT_KEYS}
+    o = {k: o[k] for k in LOSS_OUT_KEYS}
+    return o, f, note
