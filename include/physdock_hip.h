@@ -489,7 +489,7 @@ int pd_mmff_relax(const pd_mmff_terms* terms, const float* x, const int* lig_idx
                   long long ws_doubles, int B, int A, int max_iters, void* stream);
 
 /* ---- loss terms of the training-time forward (loss.hip; ABI 11) -----------------------------
- * The five terms of PhysDockLoss (models/loss.py:576-625), forward only, fp32 in, one fp32 scalar out per term.  No [B,A,A],
+ * The five terms of PhysDockLoss (models/loss.py:576-625), fp32 in, one fp32 scalar out per term (gradients: next block).  No [B,A,A],
  * [B,T,T] or [T,T,bins] intermediate is written: pairs are formed in registers and reduced per block into `ws`, a second pass
  * adds the partial sums in a fixed order in float64 (the same bits on every call, no floating-point atomics).
  * `ws` holds at least pd_loss_workspace_numel(B, A, T) floats (= max(n (n + 1) / 2 * (B + 1) with n = ceil(A / 64), 2 T B,
@@ -515,6 +515,31 @@ int pd_loss_distogram(const float* p_distogram, const float* x_gt, const float* 
                       float* out, int A, int T, void* stream);
 int pd_loss_weighted_mse(const float* x_denoised, const float* x_gt_aligned, const float* weights, const float* t_hat, float* ws,
                          float* out, int B, int A, void* stream);
+
+/* ---- gradients of the loss terms (loss_grad.hip; additive exports of ABI 11) ----------------
+ * d term / d x_denoised [B,A,3] and d distogram_loss / d p_distogram [T,T,no_bins], as torch autograd gives them for the
+ * reference's code: |.| has derivative 0 at 0, a zero distance a zero direction, torch.clamp blocks the weighted MSE above 1e4.
+ * Same rules as the forward block: no pair tensor, ordered reductions, no floating-point atomics, no allocation or host read.
+ * `scale` is a DEVICE pointer to the upstream factor (term weight x upstream gradient x finite flag); a zero scale writes / adds
+ * an exact 0 (never 0 * NaN).  accumulate = 0 writes g_x, 1 adds to it.  `ws` holds at least pd_loss_grad_workspace_numel(B, A, T)
+ * floats (= max(3 B A + ceil(A / 64), 4 + 3 B T, B + 1)); it is not shared with a forward launch still reading its own.
+ * pd_loss_weighted_mse_grad : 2 w_a (x_denoised - x_gt_aligned) mean_b scale_b(16) / (3 (1e-9 + B sum w)) x scale[0]
+ * pd_loss_smooth_lddt_grad  : full-row sweep, (1 / B) / (1e-9 + sum m) sum_j 2 m_ij eps'(delta) sign(delta) (x_i - x_j) / d_ij
+ * pd_loss_centre_pairs_grad : scale[0] x bond_loss + scale[1] x key_res_loss (both orientations of each mask), added per
+ *                             centre atom in token order (two tokens may name one atom); accumulate = 0 zeroes g_x first
+ * pd_loss_distogram_grad    : g_p = scale m^3 (softmax(m p) - onehot(bin)) / (1e-9 + sum m), m = exists_i exists_j (written) */
+int pd_loss_grad_workspace_numel(int B, int A, int T);
+int pd_loss_weighted_mse_grad(const float* x_denoised, const float* x_gt_aligned, const float* weights, const float* t_hat,
+                              const float* scale, float* ws, float* g_x, int B, int A, int accumulate, void* stream);
+int pd_loss_smooth_lddt_grad(const float* x_denoised, const float* x_gt, const float* x_exists, float max_clamp_distance,
+                             const float* scale, float* ws, float* g_x, int B, int A, int accumulate, void* stream);
+int pd_loss_centre_pairs_grad(const float* x_denoised, const float* x_gt, const long long* token_id_to_centre_atom_id,
+                              const float* token_bonds, const float* is_key_res, const float* is_ligand, const float* t_hat,
+                              float sigma_data_bond, float sigma_data_key, float eps, const float* scale, float* ws, float* g_x,
+                              int B, int A, int T, int accumulate, void* stream);
+int pd_loss_distogram_grad(const float* p_distogram, const float* x_gt, const float* x_exists,
+                           const long long* token_id_to_pseudo_beta_atom_id, const float* boundaries_sq, int no_bins,
+                           const float* scale, float* ws, float* g_p, int A, int T, void* stream);
 
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);

@@ -218,6 +218,11 @@ def _declare(L):
     sig("pd_loss_centre_pairs", p, p, p, p, p, p, p, f, f, f, p, p, i, i, i, p)
     sig("pd_loss_distogram", p, p, p, p, p, i, p, p, i, i, p)
     sig("pd_loss_weighted_mse", p, p, p, p, p, p, i, i, p)
+    sig("pd_loss_grad_workspace_numel", i, i, i)                                     # ABI 11, additive (loss_grad.hip)
+    sig("pd_loss_weighted_mse_grad", p, p, p, p, p, p, p, i, i, i, p)
+    sig("pd_loss_smooth_lddt_grad", p, p, p, f, p, p, p, i, i, i, p)
+    sig("pd_loss_centre_pairs_grad", p, p, p, p, p, p, p, f, f, f, p, p, p, i, i, i, i, p)
+    sig("pd_loss_distogram_grad", p, p, p, p, p, i, p, p, p, i, i, p)
 
 
 def ptr(t):
