@@ -96,7 +96,13 @@ __global__ __launch_bounds__(256) void augment_kernel(const float* __restrict__ 
     const float mx = sx / sm, my = sy / sm, mz = sz / sm;
     float* ob = out + (long long)b * A * 3;
     for (int a = threadIdx.x; a < A; a += 256) {
-        const float px = xb[3 * a] * x_scale - mx, py = xb[3 * a + 1] * x_scale - my, pz = xb[3 * a + 2] * x_scale - mz;
+        float px, py, pz;
+        {   // the scaled coordinate is ROUNDED before the mean is taken off (the reference centres the fp32 tensor sigma_0 * noise,
+            // and the sums above add rounded products): contracted into an fma this would keep the product's rounding residual
+            // (A = 1: out = R . residual + t instead of t).  x_scale = 1 - every step but the first - gives the same bits either way.
+#pragma clang fp contract(off)
+            px = xb[3 * a] * x_scale - mx; py = xb[3 * a + 1] * x_scale - my; pz = xb[3 * a + 2] * x_scale - mz;
+        }
         float o[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) o[i] = (sR[3 * i] * px + sR[3 * i + 1] * py + sR[3 * i + 2] * pz) + sR[9 + i];
@@ -499,7 +505,7 @@ PD_EXPORT int pd_augment(const float* x, float x_scale, const float* mask, const
 }
 
 PD_EXPORT int pd_init_noise(float* x, const unsigned long long* seed, int sample0, float sigma0, int B, int A, void* stream) {
-    if (!x || !seed) return PD_ERR_ARG;
+    if (!x || !seed || B <= 0 || A <= 0) return PD_ERR_ARG;
     hipLaunchKernelGGL(init_noise_kernel, dim3((unsigned)(((long long)B * A + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
                        seed, sample0, sigma0, B, A);
     return pd_check_launch();
@@ -507,7 +513,7 @@ PD_EXPORT int pd_init_noise(float* x, const unsigned long long* seed, int sample
 
 static int precond_launch(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx,
                           const float* a, float* ba, int G, int B, int A, int C, int Bg, void* stream) {
-    if (!x_hat || !Wx || !bx || !a || !ba || C % 4 || G <= 0) return PD_ERR_ARG;
+    if (!x_hat || !Wx || !bx || !a || !ba || C <= 0 || C % 4 || G <= 0 || B <= 0 || A <= 0) return PD_ERR_ARG;
     const long long n4 = (long long)B * A * (C / 4);
     const dim3 grid((unsigned)((n4 + 255) / 256), (unsigned)G);
     if (n4 + 256 < 0x7fffffffll)
@@ -526,14 +532,13 @@ PD_EXPORT int pd_precond(const float* x_hat, float c_in, const float* c_in_b, co
 
 PD_EXPORT int pd_precond_g(const float* x_hat, float c_in, const float* c_in_b, const float* Wx, const float* bx,
                            const float* a, float* ba, int G, int B, int A, int C, void* stream) {
-    if (B <= 0) return PD_ERR_ARG;
     return precond_launch(x_hat, c_in, c_in_b, Wx, bx, a, ba, G, B, A, C, B, stream);
 }
 
 PD_EXPORT int pd_denoise(const float* ba, const float* x_hat, const float* nw, const float* nb, const float* Wr, float eps,
                          float c_skip, float c_out, const float* cs_b, const float* co_b, float* x_den, int B, int A, int C,
                          void* stream) {
-    if (!ba || !x_hat || !nw || !nb || !Wr || !x_den || C % 4 || C > 512) return PD_ERR_ARG;
+    if (!ba || !x_hat || !nw || !nb || !Wr || !x_den || B <= 0 || A <= 0 || C <= 0 || C % 4 || C > 512) return PD_ERR_ARG;
     const long long rows = (long long)B * A;
     hipLaunchKernelGGL(denoise_kernel, dim3((unsigned)((rows + 7) / 8)), dim3(256), 0, (hipStream_t)stream, ba, x_hat, nw, nb,
                        Wr, eps, c_skip, c_out, cs_b, co_b, x_den, A, C, rows);
@@ -542,14 +547,14 @@ PD_EXPORT int pd_denoise(const float* ba, const float* x_hat, const float* nw, c
 
 PD_EXPORT int pd_kabsch_align(const float* x_pred, const float* pred_mask, const float* x_gt, long long gt_bstride,
                               const float* w, float* out, int B, int A, void* stream) {
-    if (!x_pred || !x_gt || !w || !out) return PD_ERR_ARG;
+    if (!x_pred || !x_gt || !w || !out || B <= 0 || A <= 0) return PD_ERR_ARG;
     hipLaunchKernelGGL(kabsch_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x_pred, pred_mask, x_gt, gt_bstride, w, out, A);
     return pd_check_launch();
 }
 
 PD_EXPORT int pd_template_match(const float* x, const int* lig_idx, const float* ref_dist, const float* poses,
                                 float* batch_ref_pos, float* eps_out, int* sel_out, int B, int A, int L, int Cn, void* stream) {
-    if (!x || !lig_idx || !ref_dist || L <= 0 || Cn <= 0) return PD_ERR_ARG;
+    if (!x || !lig_idx || !ref_dist || B <= 0 || A <= 0 || L <= 0 || Cn <= 0) return PD_ERR_ARG;
     if (batch_ref_pos && !poses) return PD_ERR_ARG;
     if (eps_out) {             // scratch for eps given: conformer-parallel pass + selection pass
         hipLaunchKernelGGL(template_eps_kernel, dim3(Cn, B), dim3(256), L * 3 * sizeof(float), (hipStream_t)stream, x, lig_idx,
@@ -565,7 +570,7 @@ PD_EXPORT int pd_template_match(const float* x, const int* lig_idx, const float*
 }
 
 PD_EXPORT int pd_pose_dist(const float* poses, float* D, int Cn, int L, void* stream) {
-    if (!poses || !D) return PD_ERR_ARG;
+    if (!poses || !D || Cn <= 0 || L <= 0) return PD_ERR_ARG;
     const long long n = (long long)Cn * L * L;
     hipLaunchKernelGGL(pose_dist_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, poses, D, L, n);
     return pd_check_launch();
@@ -581,7 +586,7 @@ PD_EXPORT int pd_pairwise_rmsd(const float* x, const int* idx, const float* ref,
 
 PD_EXPORT int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta,
                        float dt, float* x_next, int B, int A, void* stream) {
-    if (!x_hat || !x_den || !x_next || (x_proj && !w)) return PD_ERR_ARG;
+    if (!x_hat || !x_den || !x_next || (x_proj && !w) || B <= 0 || A <= 0) return PD_ERR_ARG;
     const long long n = (long long)B * A * 3;
     hipLaunchKernelGGL(euler_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_hat, x_den, x_proj,
                        w, t_hat, eta, dt, x_next, A, n);
