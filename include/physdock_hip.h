@@ -541,6 +541,32 @@ int pd_loss_distogram_grad(const float* p_distogram, const float* x_gt, const fl
                            const long long* token_id_to_pseudo_beta_atom_id, const float* boundaries_sq, int no_bins,
                            const float* scale, float* ws, float* g_p, int A, int T, void* stream);
 
+/* ---- confidence losses (confidence_loss.hip; additive exports of ABI 11) ---------------------
+ * cal_lddt, the token frames and the pLDDT / PDE / PAE losses (models/loss.py:184-207,320-532) with the gradient of each loss to
+ * its logits.  Same rules as the two blocks above: fp32, no [A,T], [T,T] or one-hot tensor, ordered reductions, no allocation or
+ * host read.  Every target is a hard bin: divisions that feed a bin index are IEEE, so lDDT (a ratio of two exact sums) and the
+ * bins equal the reference's wherever no distance sits on a threshold.  Only pose 0 enters the three losses.
+ * `ws` holds at least pd_conf_loss_workspace_numel(B, A, T) floats (= 4 + ceil(max(A, T^2) / 64)); the loss launchers may share it
+ * on one stream.  g (nullable) is OVERWRITTEN with scale[0] m^3 (softmax(m p) - onehot(bin)) / (1e-9 + sum m); `scale` is a DEVICE
+ * pointer (needed only with g); a zero scale or a masked row writes exact zeros.  no_bins <= 64.
+ * pd_lddt_atoms      : lddt [B,A] of x_pred [B,A,3] against x_gt over the T token centres; an empty inclusion set gives NaN
+ * pd_conf_frames     : frames [T,13] = e1 | e2 | e3 | origin | (cos theta < 0.906308) of x [A,3] (a pose or x_gt)
+ * pd_conf_loss_plddt : rows = atoms, m = x_exists, bin = clamp(long(lddt no_bins)) (NaN -> 0); lddt [A] is that of pose 0
+ * pd_conf_loss_pairs : rows = token pairs, m = exists_ci exists_cj, bin = clamp(long((e - min_bin) / bin_range no_bins));
+ *                      mode 0 (PDE) e = |d_pred - d_gt| of the centres, mode 1 (PAE) e = |R_i^pred (c_j - b_i)^pred -
+ *                      R_i^gt (c_j - b_i)^gt| valid_i^gt valid_i^pred (frames of pd_conf_frames; unused and nullable in mode 0) */
+int pd_conf_loss_workspace_numel(int B, int A, int T);
+int pd_lddt_atoms(const float* x_pred, const float* x_gt, const long long* token_id_to_centre_atom_id, const float* is_dna,
+                  const float* is_rna, const float* is_polymer, float* lddt, int B, int A, int T, void* stream);
+int pd_conf_frames(const float* x, const long long* frame_atom_0, const long long* frame_atom_1, const long long* frame_atom_2,
+                   float* frames, int A, int T, void* stream);
+int pd_conf_loss_plddt(const float* p_plddt, const float* lddt, const float* x_exists, int no_bins, const float* scale, float* ws,
+                       float* out, float* g_plddt, int A, void* stream);
+int pd_conf_loss_pairs(int mode, const float* p_pair, const float* x_pred0, const float* x_gt, const float* x_exists,
+                       const long long* token_id_to_centre_atom_id, const float* frames_pred, const float* frames_gt,
+                       float min_bin, float bin_range, int no_bins, const float* scale, float* ws, float* out, float* g_pair,
+                       int A, int T, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

@@ -15,3 +15,4 @@ from .confidence import ConfidenceModule  # noqa: F401  (reference layers/confid
 from .params import param_shapes, seeded_state_dict  # noqa: F401
 from .driver import redock, redock_many  # noqa: F401  (multi-round caller of the sampler, reference redocking.py:156-342)
 from .loss import PhysDockLoss  # noqa: F401  (reference models/loss.py:576-625, forward values; csrc/loss.hip)
+from .loss import ConfidenceLoss, cal_lddt, pae_loss, pde_loss, plddt_loss  # noqa: F401  (reference models/loss.py:320-532; csrc/confidence_loss.hip)

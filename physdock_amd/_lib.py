@@ -223,6 +223,11 @@ def _declare(L):
     sig("pd_loss_smooth_lddt_grad", p, p, p, f, p, p, p, i, i, i, p)
     sig("pd_loss_centre_pairs_grad", p, p, p, p, p, p, p, f, f, f, p, p, p, i, i, i, i, p)
     sig("pd_loss_distogram_grad", p, p, p, p, p, i, p, p, p, i, i, p)
+    sig("pd_conf_loss_workspace_numel", i, i, i)                                     # ABI 11, additive (confidence_loss.hip)
+    sig("pd_lddt_atoms", p, p, p, p, p, p, p, i, i, i, p)
+    sig("pd_conf_frames", p, p, p, p, p, i, i, p)
+    sig("pd_conf_loss_plddt", p, p, p, i, p, p, p, p, i, p)
+    sig("pd_conf_loss_pairs", i, p, p, p, p, p, p, p, f, f, i, p, p, p, p, i, i, p)
 
 
 def ptr(t):

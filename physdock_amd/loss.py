@@ -23,6 +23,9 @@ is_key_res [T].  As in the reference, what the functions compute is what its cod
 weighted_mse_loss uses sigma_data = 16 whatever it is given and one masked mean over samples AND atoms; bond_loss and
 key_res_loss multiply the sample mean of the EDM scale with the sample mean of the masked sum; a non-finite coordinate makes
 a term NaN even where its mask is zero (0 * NaN), and PhysDockLoss replaces such a term by zero with a warning.
+
+The second half of the file is ConfidenceLoss: cal_lddt, plddt_loss, pde_loss and pae_loss (reference loss.py:184-207, 320-532;
+csrc/confidence_loss.hip) with their gradients to the logits of ConfidenceModule.
 """
 from __future__ import annotations
 
@@ -32,7 +35,8 @@ import torch
 
 from . import _lib as ops
 
-__all__ = ["PhysDockLoss", "weighted_mse_loss", "smooth_lddt_loss", "bond_loss", "key_res_loss", "distogram_loss"]
+__all__ = ["PhysDockLoss", "weighted_mse_loss", "smooth_lddt_loss", "bond_loss", "key_res_loss", "distogram_loss",
+           "ConfidenceLoss", "cal_lddt", "plddt_loss", "pde_loss", "pae_loss"]
 
 LOSS_TERMS = ("weighted_mse_loss", "smooth_lddt_loss", "bond_loss", "key_res_loss", "distogram_loss")
 
@@ -75,13 +79,14 @@ def _wants_grad(t):
     return torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad
 
 
-def _no_grad_to(what, **tensors):
-    """gradients flow to x_denoised and p_distogram only; refuse the others loudly rather than return a silent None"""
+def _no_grad_to(what, _only="x_denoised and p_distogram", **tensors):
+    """gradients flow to x_denoised and p_distogram only (the confidence losses: to the logits only); refuse the others loudly
+    rather than return a silent None"""
     if not torch.is_grad_enabled():
         return
     for k, t in tensors.items():
         if isinstance(t, torch.Tensor) and t.requires_grad:
-            raise NotImplementedError(f"physdock_amd.{what}: no gradient to `{k}` (only x_denoised and p_distogram are "
+            raise NotImplementedError(f"physdock_amd.{what}: no gradient to `{k}` (only {_only} are "
                                       f"differentiable here); pass it detached")
 
 
@@ -414,3 +419,260 @@ class PhysDockLoss(torch.nn.Module):
 
 def _settings(block):
     return {k: v for k, v in block.items() if k != "weight"}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The confidence losses (reference loss.py:184-207, 320-532; csrc/confidence_loss.hip)
+#
+#     p_pae, p_pde, p_plddt = confidence_module(batch, s, z, x_pred)
+#     cum_loss, losses = ConfidenceLoss(cfg)({"p_plddt": p_plddt, "p_pde": p_pde, "p_pae": p_pae, "x_pred": x_pred}, batch)
+#     cum_loss.backward()                                    # where the logits require grad
+#     terms, g_plddt, g_pde, g_pae = ConfidenceLoss(cfg).grads(outputs, batch)     # the same gradients, no host read
+#
+# Every target is a hard bin of a distance, formed on the fly; gradients flow to the logits only.  Only pose 0 of x_pred enters
+# the three losses, as in the reference.
+CONF_TERMS = ("plddt_loss", "pde_loss", "pae_loss")
+CONF_LOGITS = ("p_plddt", "p_pde", "p_pae")
+FRAME_KEYS = ("token_id_to_frame_atom_id_0", "token_id_to_frame_atom_id_1", "token_id_to_frame_atom_id_2")
+_LOGITS_ONLY = "the logits"
+
+
+def _cws(A, T, device):
+    n = ops.init().pd_conf_loss_workspace_numel(1, A, T)
+    ops.check(min(n, 0), "conf_loss_workspace_numel")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def _poses(x_pred):
+    x = _f(x_pred)
+    if x.dim() != 3 or x.shape[-1] != 3:
+        raise ValueError(f"x_pred must be [num_poses, num_atoms, 3], got {tuple(x.shape)}")
+    return x
+
+
+def _lddt(xp, xg, dna, rna, poly, c):
+    """[B,A] per-atom lDDT of the fp32 contiguous poses xp [B,A,3]"""
+    B, A, T = xp.shape[0], xp.shape[1], c.shape[0]
+    if tuple(xg.shape) != (A, 3):
+        raise ValueError(f"x_gt must be [{A}, 3], got {tuple(xg.shape)}")
+    out = torch.empty(B, A, dtype=torch.float32, device=xp.device)
+    ops.check(ops.init().pd_lddt_atoms(ops.ptr(xp), ops.ptr(xg), ops.ptr(c), ops.ptr(dna), ops.ptr(rna), ops.ptr(poly), ops.ptr(out),
+                                       B, A, T, ops.stream()), "lddt_atoms")
+    return out
+
+
+def _polymer(is_ligand):
+    """the reference writes `~is_ligand`, which raises on the float32 is_ligand its own loader produces; `is_ligand == 0` is the
+    same for the bool input it accepts and works for every dtype"""
+    return (is_ligand == 0).float().contiguous()
+
+
+@torch.no_grad()
+def cal_lddt(x_pred, x_gt, is_dna, is_rna, is_polymer, token_id_to_centre_atom_id, **kwargs):
+    """reference loss.py:320-372: per-atom lDDT [B,A] of the poses x_pred [B,A,3] ([A] for one pose [A,3]) against x_gt over the
+    token-centre atoms: four hard thresholds 0.5 / 1 / 2 / 4 on |d_pred - d_gt|, inclusion d_gt < 30 (nucleotide tokens) or 15,
+    times is_polymer.  No epsilon: an atom with an empty inclusion set is NaN, as there.  Piecewise constant: no gradient."""
+    _dev("cal_lddt", x_pred, x_gt, is_dna, is_rna, is_polymer, token_id_to_centre_atom_id)
+    one = x_pred.dim() == 2
+    out = _lddt(_poses(x_pred[None] if one else x_pred), _f(x_gt), _f(is_dna), _f(is_rna), _f(is_polymer), _l(token_id_to_centre_atom_id))
+    return out[0] if one else out
+
+
+def _frames(x, ids):
+    """[T,13] frames (e1 | e2 | e3 | origin | valid) of the coordinates x [A,3]: express_coordinates_in_frame, loss.py:184-207"""
+    T = ids[0].shape[0]
+    out = torch.empty(T, 13, dtype=torch.float32, device=x.device)
+    ops.check(ops.init().pd_conf_frames(ops.ptr(x), ops.ptr(ids[0]), ops.ptr(ids[1]), ops.ptr(ids[2]), ops.ptr(out), x.shape[0], T,
+                                        ops.stream()), "conf_frames")
+    return out
+
+
+def _plddt_launch(p, no_bins, lddt0, ex, ws=None, out=None, grad=None, scale=None):
+    A = ex.shape[0]
+    if tuple(p.shape) != (A, no_bins):
+        raise ValueError(f"p_plddt must be [{A}, {no_bins}], got {tuple(p.shape)}")
+    ws = _cws(A, 1, p.device) if ws is None else ws
+    out = torch.empty(1, dtype=torch.float32, device=p.device) if out is None else out
+    ops.check(ops.init().pd_conf_loss_plddt(ops.ptr(p), ops.ptr(lddt0), ops.ptr(ex), int(no_bins), ops.ptr(scale), ops.ptr(ws),
+                                            ops.ptr(out), ops.ptr(grad), A, ops.stream()), "conf_loss_plddt")
+    return out[0]
+
+
+def _pairs_launch(mode, p, x0, xg, ex, c, fr, min_bin, max_bin, no_bins, ws=None, out=None, grad=None, scale=None):
+    A, T = xg.shape[0], c.shape[0]
+    if tuple(p.shape) != (T, T, no_bins):
+        raise ValueError(f"{('p_pde', 'p_pae')[mode]} must be [{T}, {T}, {no_bins}], got {tuple(p.shape)}")
+    ws = _cws(A, T, p.device) if ws is None else ws
+    out = torch.empty(1, dtype=torch.float32, device=p.device) if out is None else out
+    fp, fg = fr if fr is not None else (None, None)
+    ops.check(ops.init().pd_conf_loss_pairs(mode, ops.ptr(p), ops.ptr(x0), ops.ptr(xg), ops.ptr(ex), ops.ptr(c), ops.ptr(fp), ops.ptr(fg),
+                                            float(min_bin), float(max_bin - min_bin), int(no_bins), ops.ptr(scale), ops.ptr(ws),
+                                            ops.ptr(out), ops.ptr(grad), A, T, ops.stream()), "conf_loss_pairs")
+    return out[0]
+
+
+def _logit_term(what, logits, launch, **others):
+    """value of one confidence term, with a grad_fn where the logits require grad; launch(p, grad, scale) -> 0-d value"""
+    _no_grad_to(what, _only=_LOGITS_ONLY, **others)
+    with torch.no_grad():
+        p = _f(logits.detach())
+        v = launch(p, None, None)
+    if not _wants_grad(logits):
+        return v
+
+    def back(g):
+        gp = torch.empty_like(p)
+        launch(p, gp, _scale_ptr(g))
+        return (_as_input(gp, logits),)
+    return _attach(v, back, logits)
+
+
+def plddt_loss(p_plddt, no_bins, x_pred, x_gt, x_exists, is_dna, is_rna, is_ligand, token_id_to_centre_atom_id, **kwargs):
+    """reference loss.py:375-421.  is_polymer = (is_ligand == 0) for every dtype: the reference's `~is_ligand` is the same for the
+    bool input it accepts and raises on the float32 is_ligand of its own loader.  A NaN lDDT (an atom with no polymer centre in
+    range) goes to bin 0."""
+    _dev("plddt_loss", p_plddt, x_pred, x_gt, x_exists, is_dna, is_rna, is_ligand, token_id_to_centre_atom_id)
+    with torch.no_grad():
+        lddt0 = _lddt(_poses(x_pred)[0:1], _f(x_gt), _f(is_dna), _f(is_rna), _polymer(is_ligand), _l(token_id_to_centre_atom_id))[0]
+        ex = _f(x_exists)
+    return _logit_term("plddt_loss", p_plddt, lambda p, g, s: _plddt_launch(p, no_bins, lddt0, ex, grad=g, scale=s),
+                       x_pred=x_pred, x_gt=x_gt, x_exists=x_exists, is_dna=is_dna, is_rna=is_rna, is_ligand=is_ligand)
+
+
+def pde_loss(p_pde, x_pred, x_gt, x_exists, token_id_to_centre_atom_id, min_bin=0.0, max_bin=32.0, no_bins=64, **kwargs):
+    """reference loss.py:472-532"""
+    _dev("pde_loss", p_pde, x_pred, x_gt, x_exists, token_id_to_centre_atom_id)
+    with torch.no_grad():
+        x0, xg, ex, c = _poses(x_pred)[0], _f(x_gt), _f(x_exists), _l(token_id_to_centre_atom_id)
+    return _logit_term("pde_loss", p_pde,
+                       lambda p, g, s: _pairs_launch(0, p, x0, xg, ex, c, None, min_bin, max_bin, no_bins, grad=g, scale=s),
+                       x_pred=x_pred, x_gt=x_gt, x_exists=x_exists)
+
+
+def pae_loss(p_pae, x_pred, x_gt, x_exists, token_id_to_centre_atom_id, token_id_to_frame_atom_id_0, token_id_to_frame_atom_id_1,
+             token_id_to_frame_atom_id_2, min_bin=0, max_bin=32, no_bins=64, **kwargs):
+    """reference loss.py:424-469: the error of token j's centre expressed in token i's frame (express_coordinates_in_frame,
+    loss.py:184-207), zero where the frame of i is invalid (its three atoms within 25 degrees of a line) in x_gt or in pose 0"""
+    ids = (token_id_to_frame_atom_id_0, token_id_to_frame_atom_id_1, token_id_to_frame_atom_id_2)
+    _dev("pae_loss", p_pae, x_pred, x_gt, x_exists, token_id_to_centre_atom_id, *ids)
+    with torch.no_grad():
+        x0, xg, ex, c = _poses(x_pred)[0], _f(x_gt), _f(x_exists), _l(token_id_to_centre_atom_id)
+        ids = tuple(_l(i) for i in ids)
+        fr = (_frames(x0, ids), _frames(xg, ids))
+    return _logit_term("pae_loss", p_pae,
+                       lambda p, g, s: _pairs_launch(1, p, x0, xg, ex, c, fr, min_bin, max_bin, no_bins, grad=g, scale=s),
+                       x_pred=x_pred, x_gt=x_gt, x_exists=x_exists)
+
+
+class ConfidenceLoss(torch.nn.Module):
+    """`cum_loss, losses = ConfidenceLoss(config)(outputs, feats)`: the weighted sum of plddt_loss, pde_loss and pae_loss and a dict
+    of the three terms and the sum under "loss", each a detached 0-d fp32 device tensor.  `outputs` holds the logits of
+    ConfidenceModule, p_plddt [A,bins], p_pde and p_pae [T,T,bins], and the poses x_pred [B,A,3] (pose 0 is read); `feats` uses the
+    reference's key names: x_gt, x_exists (falls back to a_mask), is_dna, is_rna, is_ligand, token_id_to_centre_atom_id and the
+    three token_id_to_frame_atom_id_{0,1,2}.  Weights and settings come from config.loss.{plddt_loss, pde_loss, pae_loss}.
+    is_polymer = (is_ligand == 0) for every dtype (see plddt_loss).  A NaN / Inf term is replaced by zero with a logging.warning as
+    in PhysDockLoss; that check is the only host read.  Where a logit tensor requires grad `cum_loss` has a grad_fn.
+
+    The reference's feature loader never makes the frame-atom ids and the default PAE weight is 0: without the three keys and with
+    a zero weight the PAE term is not launched (losses["pae_loss"] = 0, g_pae = None); with a non-zero weight it is a KeyError."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config.loss
+        self._wdev = {}
+
+    def _prepare(self, outputs, feats):
+        """everything the launches read, fp32 / int64 contiguous, with the lDDT of pose 0 and the frames (no host read)"""
+        c = self.config
+        f = dict(feats)
+        if "x_exists" not in f:
+            f["x_exists"] = f["a_mask"]
+        has_frames = all(k in f for k in FRAME_KEYS)
+        if not has_frames and float(c.pae_loss.weight) != 0.0:
+            raise KeyError(f"pae_loss has weight {c.pae_loss.weight} but feats lacks {[k for k in FRAME_KEYS if k not in f]}")
+        _dev("ConfidenceLoss", outputs["p_plddt"], outputs["p_pde"], outputs["x_pred"], f["x_gt"], f["x_exists"],
+             *([outputs["p_pae"]] if has_frames else []))
+        _no_grad_to("ConfidenceLoss", _only=_LOGITS_ONLY, x_pred=outputs["x_pred"],
+                    **{k: f[k] for k in ("x_gt", "x_exists", "is_dna", "is_rna", "is_ligand")})
+        with torch.no_grad():
+            k = {"x0": _poses(outputs["x_pred"])[0], "xg": _f(f["x_gt"]), "ex": _f(f["x_exists"]),
+                 "c": _l(f["token_id_to_centre_atom_id"]), "fr": None}
+            k["p"] = [_f(outputs[n].detach()) if (n != "p_pae" or has_frames) else None for n in CONF_LOGITS]
+            k["lddt0"] = _lddt(k["x0"][None], k["xg"], _f(f["is_dna"]), _f(f["is_rna"]), _polymer(f["is_ligand"]), k["c"])[0]
+            if has_frames:
+                ids = tuple(_l(f[n]) for n in FRAME_KEYS)
+                k["fr"] = (_frames(k["x0"], ids), _frames(k["xg"], ids))
+            k["ws"] = _cws(k["xg"].shape[0], k["c"].shape[0], k["xg"].device)
+        return k
+
+    def _launch(self, k, out, grads=(None, None, None), sc=None):
+        """the three terms into out [3] (PAE untouched without frames); grads[t], where given, is overwritten with sc[t] x d term_t"""
+        c = self.config
+        s = [None if sc is None else sc[t:t + 1] for t in range(3)]
+        _plddt_launch(k["p"][0], c.plddt_loss.no_bins, k["lddt0"], k["ex"], ws=k["ws"], out=out[0:1], grad=grads[0], scale=s[0])
+        for t, name in ((1, "pde_loss"), (2, "pae_loss")):
+            if t == 2 and k["fr"] is None:
+                continue
+            st = {"min_bin": 0, "max_bin": 32, "no_bins": 64, **_settings(c[name])}
+            _pairs_launch(t - 1, k["p"][t], k["x0"], k["xg"], k["ex"], k["c"], k["fr"] if t == 2 else None, st["min_bin"], st["max_bin"],
+                          st["no_bins"], ws=k["ws"], out=out[t:t + 1], grad=grads[t], scale=s[t])
+        return out
+
+    @torch.no_grad()
+    def terms(self, outputs, feats, _k=None):
+        """the three raw terms as one [3] device tensor in the order of CONF_TERMS (no host read; capturable)"""
+        k = self._prepare(outputs, feats) if _k is None else _k
+        return self._launch(k, torch.zeros(3, dtype=torch.float32, device=k["xg"].device))
+
+    def _weights(self, device):
+        key = str(device)
+        if key not in self._wdev:
+            self._wdev[key] = torch.tensor([float(self.config[n].weight) for n in CONF_TERMS], dtype=torch.float32, device=device)
+        return self._wdev[key]
+
+    @torch.no_grad()
+    def _backward(self, k, t, up, need=(True, True, True)):
+        """the gradients of sum_t weight_t term_t x up to the logits, from the raw terms t [3]: the scale of a term is weight x up x
+        isfinite(term), read by the launchers from device memory (no host read)"""
+        w = self._weights(t.device)
+        sc = torch.where(torch.isfinite(t), w * up if up is not None else w, torch.zeros_like(t)).contiguous()
+        grads = [torch.empty_like(k["p"][i]) if (need[i] and k["p"][i] is not None) else None for i in range(3)]
+        if any(g is not None for g in grads):
+            self._launch(k, torch.empty(3, dtype=torch.float32, device=t.device), grads, sc)
+        return grads
+
+    @torch.no_grad()
+    def grads(self, outputs, feats, grad_scale=None):
+        """(terms [3], g_plddt, g_pde, g_pae): the raw terms and the gradients of the weighted total to the three logit tensors,
+        scaled by `grad_scale` (a 0-d device tensor, or None for 1).  A non-finite term adds no gradient; g_pae is None where the
+        PAE term is not launched.  No host read: capturable in a hipGraph.  The same bits as `cum_loss.backward()`."""
+        k = self._prepare(outputs, feats)
+        t = self.terms(outputs, feats, _k=k)
+        up = None if grad_scale is None else grad_scale.detach().float().reshape(())
+        return (t, *self._backward(k, t, up))
+
+    def forward(self, outputs, feats):
+        k = self._prepare(outputs, feats)
+        logits = [outputs[n] if k["p"][i] is not None else None for i, n in enumerate(CONF_LOGITS)]
+        need = [_wants_grad(p) for p in logits]
+        with torch.no_grad():
+            t = self.terms(outputs, feats, _k=k)
+            bad = (~torch.isfinite(t)).tolist()                    # the one host read
+            for name, b in zip(CONF_TERMS, bad):
+                if b:
+                    logging.warning(f"{name} loss is NaN. Skipping...")
+            tz = torch.where(torch.isfinite(t), t, torch.zeros_like(t)) if any(bad) else t
+            cum = torch.zeros((), dtype=torch.float32, device=t.device)
+            losses = {}
+            for i, name in enumerate(CONF_TERMS):
+                cum = cum + float(self.config[name].weight) * tz[i]
+                losses[name] = tz[i].clone()
+            losses["loss"] = cum.clone()
+        if any(need):
+            live = [p for p, n in zip(logits, need) if n]
+
+            def back(g):
+                gs = self._backward(k, t, g.detach().float().reshape(()), need)
+                return tuple(_as_input(gs[i], logits[i]) for i in range(3) if need[i])
+            cum = _Grad.apply(cum, back, *live)
+        return cum, losses

@@ -463,3 +463,164 @@ def loss_case(name, B_cfg1=48, stored=None):
     f = {k: f[k] for k in LOSS_FEAT_KEYS}
     o = {k: o[k] for k in LOSS_OUT_KEYS}
     return o, f, note
+
+
+CONF_FEAT_KEYS = ("x_gt", "x_exists", "token_id_to_centre_atom_id", "is_dna", "is_rna", "is_ligand", "token_id_to_frame_atom_id_0",
+                  "token_id_to_frame_atom_id_1", "token_id_to_frame_atom_id_2")
+CONF_OUT_KEYS = ("p_plddt", "p_pde", "p_pae", "x_pred")
+CONF_SEEDS = {"small": 21, "mid": 23, "ragged": 25, "empty": 27}
+#: margins of the decision thresholds of the confidence losses (Angstrom; cos theta of a frame; |w1 + w2| of a frame)
+CONF_MARGIN, CONF_COS_MARGIN, CONF_MIN_BISECTOR = 1e-4, 1e-5, 0.1
+
+
+def frame_atom_ids(feats):
+    """token_id_to_frame_atom_id_{0,1,2}: atoms 0, 1, 2 of a residue token; previous / self / next atom of a one-atom (ligand)
+    token (the last atom takes the one before the previous).  The reference's loader never makes them."""
+    chunk = feats["token_id_to_chunk_sizes"].long()
+    start = torch.cumsum(chunk, 0) - chunk
+    A = int(chunk.sum())
+    one = chunk < 3
+    nxt = torch.where(start + 1 < A, start + 1, start - 2)
+    return (torch.where(one, start - 1, start), torch.where(one, start, start + 1), torch.where(one, nxt, start + 2))
+
+
+def confidence_frames64(x, ids):
+    """express_coordinates_in_frame (reference loss.py:184-207) in float64: e1, e2, e3 [T,3] each, origin b, cos theta, |w1 + w2|"""
+    import numpy as np
+    a, b, c = x[ids[0]], x[ids[1]], x[ids[2]]
+    w1 = (a - b) / np.linalg.norm(a - b + 1e-6, axis=-1, keepdims=True)
+    w2 = (c - b) / np.linalg.norm(c - b + 1e-6, axis=-1, keepdims=True)
+    e1 = (w1 + w2) / np.linalg.norm(w1 + w2 + 1e-6, axis=-1, keepdims=True)
+    e2 = (w2 - w1) / np.linalg.norm(w2 - w1 + 1e-6, axis=-1, keepdims=True)
+    return e1, e2, np.cross(e1, e2), b, (w1 * w2).sum(-1), np.linalg.norm(w1 + w2, axis=-1)
+
+
+def confidence_decisions64(xp, xg, feats, no_bins_plddt=50, step=0.5):
+    """Every hard decision of the confidence losses in float64 (numpy), with the distance of its argument to the nearest
+    threshold.  Returns a dict: `d_gt` [A,T], `d_lm` [B,A,T], `include` [A,T] weights, `e_pde`, `e_pae` [T,T] of pose 0,
+    `cos` [2,T] (pose 0, x_gt), `bisector` [2,T], `num`, `den` [B,A] of the lDDT ratio."""
+    import numpy as np
+    xp, xg = np.asarray(xp, np.float64), np.asarray(xg, np.float64)
+    c = np.asarray(feats["token_id_to_centre_atom_id"])
+    ids = [np.asarray(feats[f"token_id_to_frame_atom_id_{k}"]) for k in range(3)]
+    nuc = (np.asarray(feats["is_dna"], np.float64) + np.asarray(feats["is_rna"], np.float64))[None]
+    poly = (np.asarray(feats["is_ligand"]) == 0).astype(np.float64)[None]
+    d_gt = np.linalg.norm(xg[:, None] - xg[c][None], axis=-1)
+    d_pred = np.linalg.norm(xp[:, :, None] - xp[:, c][:, None], axis=-1)
+    d_lm = np.abs(d_pred - d_gt[None])
+    w = ((d_gt < 30) * nuc + (d_gt < 15) * (1 - nuc)) * poly
+    score = 0.25 * sum((d_lm < t).astype(np.float64) for t in (0.5, 1.0, 2.0, 4.0))
+    out = {"d_gt": d_gt, "d_lm": d_lm, "include": w, "num": (w[None] * score).sum(-1), "den": np.broadcast_to(w.sum(-1), d_lm.shape[:2])}
+    out["e_pde"] = d_lm[0][c]
+    fr = [confidence_frames64(x, ids) for x in (xp[0], xg)]
+    u = [np.einsum("kti,tji->tjk", np.stack(f[:3]), x[c][None] - f[3][:, None]) for f, x in zip(fr, (xp[0], xg))]
+    valid = [(f[4] < 0.906308) for f in fr]
+    out["e_pae"] = np.linalg.norm(u[0] - u[1], axis=-1) * (valid[0] & valid[1])[:, None]
+    out["cos"], out["bisector"] = np.stack([f[4] for f in fr]), np.stack([f[5] for f in fr])
+    return out
+
+
+def lddt_bins32(num, den, no_bins):
+    """clamp(long(lddt * no_bins), 0, no_bins - 1) as the reference's fp32 expression evaluates it on the exact sums num, den (both
+    are sums of multiples of 0.25, exact in fp32 in any order): one IEEE fp32 division, one fp32 product, truncation; NaN -> 0"""
+    import numpy as np
+    with np.errstate(invalid="ignore", divide="ignore"):
+        v = (np.asarray(num, np.float32) / np.asarray(den, np.float32)) * np.float32(no_bins)
+    return np.where(np.isnan(v), 0, np.clip(np.nan_to_num(v, nan=0.0), 0, no_bins - 1)).astype(np.int64)
+
+
+def confidence_closest(dec, no_bins_plddt=50, step=0.5):
+    """closest approaches of a confidence case to its decision thresholds, and the atoms to nudge for those inside the margins:
+    (dict of distances, set of atoms of x_gt)"""
+    import numpy as np
+    def to_grid(e):
+        return np.abs(e - np.round(e / step) * step)
+    d_gt, d_lm = dec["d_gt"], dec["d_lm"]
+    near = {"d_gt": np.minimum(np.abs(d_gt - 15.0), np.abs(d_gt - 30.0)),
+            "d_lm": np.min([np.abs(d_lm - t) for t in (0.5, 1.0, 2.0, 4.0)], axis=0).min(0),
+            "e_pde": to_grid(dec["e_pde"]), "e_pae": to_grid(dec["e_pae"])}
+    # zero errors (the diagonal, invalid frames) are exact zeros in every implementation, not near a threshold
+    near["e_pde"] = np.where(dec["e_pde"] == 0, np.inf, near["e_pde"])
+    near["e_pae"] = np.where(dec["e_pae"] == 0, np.inf, near["e_pae"])
+    cos = np.abs(dec["cos"] - 0.906308)
+    # lddt * no_bins on an integer although the ratio is not a dyadic rational: fp32 and float64 may truncate it differently
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q = dec["num"] / dec["den"]
+        v = q * no_bins_plddt
+        tie = (np.abs(v - np.round(v)) < 1e-9) & (q.astype(np.float32).astype(np.float64) != q)
+    close = {"closest_d_gt": float(near["d_gt"].min()), "closest_d_lm": float(near["d_lm"].min()),
+             "closest_e_pde": float(near["e_pde"].min()), "closest_e_pae": float(near["e_pae"].min()),
+             "closest_cos": float(cos.min()), "smallest_bisector": float(dec["bisector"].min()), "lddt_integer_ties": int(tie.sum())}
+    return close, near, cos, tie
+
+
+def clear_confidence_thresholds(x_gt, noise, feats, seed=0, rounds=500):
+    """Nudge (0.01 A, seeded) atoms of x_gt until no decision of the confidence losses of (x_pred = x_gt + noise, x_gt) lies
+    within CONF_MARGIN of a threshold in float64 (confidence_closest).  The non-centre atom of an offending atom-centre pair is
+    moved: that redraws T pairs, a centre A + T.  Integer ties of lddt * no_bins are counted, not cleared: a 0.01 A nudge does
+    not move a ratio of counts, and the tie is decided by the fp32 expression on exact operands (lddt_bins32), the same bits in
+    every IEEE implementation.  Returns (x_gt, x_pred, closest approaches, rounds used)."""
+    import numpy as np
+    rng = np.random.RandomState(seed)
+    x = np.asarray(x_gt, np.float32).copy()
+    c = np.asarray(feats["token_id_to_centre_atom_id"])
+    ids = [np.asarray(feats[f"token_id_to_frame_atom_id_{k}"]) for k in range(3)]
+    is_centre = np.zeros(x.shape[0], bool)
+    is_centre[c] = True
+    for r in range(rounds):
+        xp = x[None] + noise
+        dec = confidence_decisions64(xp, x, feats)
+        close, near, cos, tie = confidence_closest(dec)
+        bad = set()
+        m = (near["d_gt"] < CONF_MARGIN) | (near["d_lm"] < CONF_MARGIN)
+        for a, t in zip(*np.nonzero(m)):
+            bad.add(int(c[t]) if (is_centre[a] and not is_centre[c[t]]) else int(a))
+        for k in ("e_pde", "e_pae"):
+            bad |= set(c[np.nonzero(near[k] < CONF_MARGIN)[1]].tolist())
+        fbad = (cos < CONF_COS_MARGIN).any(0) | (dec["bisector"] < CONF_MIN_BISECTOR).any(0)
+        bad |= set(ids[0][fbad].tolist())
+        if not bad:
+            return x, xp.astype(np.float32), close, r
+        for a in sorted(bad):
+            x[a] += (0.01 * rng.randn(3)).astype(np.float32)
+    raise RuntimeError("could not clear the decision thresholds of the confidence losses")
+
+
+def confidence_logits(A, T, seed, bins_plddt=50, bins_pair=64):
+    """hashed-uniform logits in (-4, 4): p_plddt [A,bins], p_pde, p_pae [T,T,bins] (bit-identical everywhere)"""
+    import numpy as np
+    mk = lambda n, s, shape: torch.from_numpy(hashed_uniform(n, s).reshape(shape)) * np.float32(8.0)
+    return {"p_plddt": mk(A * bins_plddt, 3 * seed, (A, bins_plddt)), "p_pde": mk(T * T * bins_pair, 3 * seed + 1, (T, T, bins_pair)),
+            "p_pae": mk(T * T * bins_pair, 3 * seed + 2, (T, T, bins_pair))}
+
+
+def confidence_loss_case(name, stored=None):
+    """(outputs, feats, info) of the confidence-loss fixture tests/golden/g17_conf_loss_<name>.npz
+    (tools/make_golden_confidence_loss.py).  outputs: p_plddt [A,50], p_pde, p_pae [T,T,64] (hashed uniform in (-4, 4)) and
+    x_pred [B,A,3] = x_gt + 0.6 u (u uniform of unit variance); feats: CONF_FEAT_KEYS.  A fixture stores feats and x_pred; with
+    `stored` (the loaded fixture) the logits are rebuilt bit for bit.  Without it the case is built and its decision thresholds
+    cleared (clear_confidence_thresholds); info then holds the closest approaches."""
+    import numpy as np
+    seed = CONF_SEEDS[name]
+    if stored is not None:
+        f = {k: torch.from_numpy(np.asarray(stored[k])) for k in CONF_FEAT_KEYS}
+        A, T = f["x_gt"].shape[0], f["is_ligand"].shape[0]
+        return {**confidence_logits(A, T, seed), "x_pred": torch.from_numpy(np.asarray(stored["x_pred"]))}, f, {}
+    # the first masked atom is the centre atom of token 1, so that token pairs are masked too, not only an atom
+    shape, B, kw = {"small": ((18, 5, 6, 8), 3, dict(n_dna=2, n_rna=2, masked_atoms=(6,))),
+                    "empty": ((18, 5, 6, 8), 3, dict(n_dna=2, n_rna=2, masked_atoms=(6,))),
+                    "mid": ((61, 7, 10, 8), 2, dict(n_dna=3, n_rna=3, masked_atoms=(8, 200))),
+                    "ragged": ((198, 9, 23, 8), 2, dict(n_dna=5, n_rna=7, masked_atoms=(10, 900)))}[name]
+    f = loss_features(make_batch(*shape, seed=seed), seed=seed + 1, n_key=0, **kw)
+    for k, v in enumerate(frame_atom_ids(f)):
+        f[f"token_id_to_frame_atom_id_{k}"] = v
+    f = {k: f[k] for k in CONF_FEAT_KEYS}
+    A, T = f["x_gt"].shape[0], f["is_ligand"].shape[0]
+    x = f["x_gt"].numpy().astype(np.float32).copy()
+    if name == "empty":            # the last ligand atom far from every polymer centre: empty inclusion set, lDDT = 0 / 0
+        x[A - 1] += np.float32(200.0)
+    noise = hashed_uniform(B * A * 3, 3 * seed + 7).reshape(B, A, 3) * np.float32(3.4641016) * np.float32(0.6)
+    fn = {k: v.numpy() for k, v in f.items()}
+    x, xp, close, used = clear_confidence_thresholds(x, noise, fn, seed=seed)
+    f["x_gt"] = torch.from_numpy(x)
+    return {**confidence_logits(A, T, seed), "x_pred": torch.from_numpy(xp)}, f, {**close, "rounds": used, "make_batch": shape, "B": B}
