@@ -567,6 +567,35 @@ int pd_conf_loss_pairs(int mode, const float* p_pair, const float* x_pred0, cons
                        float min_bin, float bin_range, int no_bins, const float* scale, float* ws, float* out, float* g_pair,
                        int A, int T, void* stream);
 
+/* ---- confidence metrics (metrics.hip; additive exports of ABI 11) ------------------------------
+ * The inference-time scores of data/tools/get_metrics.py from the logits of ConfidenceModule, for P stacked logit sets and B poses
+ * per call.  fp32; the logits are read once; ordered reductions (two calls give the same bits, and so do two bit-identical
+ * rows, for any P), no floating-point atomics, no allocation or host read.  no_bins <= 64 (else PD_ERR_UNSUPPORTED).
+ * pd_metrics_plddt  : atom_plddts [P,A] = 100 sum_k softmax(p_plddt [P,A,no_bins])_k (k + 0.5) / no_bins; mean_plddt [P] = the
+ *                     plain mean over all A atoms (no mask, as in the reference)
+ * pd_metrics_pae_tm : one pass over p_pae [P,T,T,no_bins].  `centres` [no_bins] is a DEVICE table of the bin centres, `weights`
+ *                     [T] the residue weights w (s_mask, may be fractional), asym_id [T] int32 (nullable: ipTM = 0, row 0).
+ *                     pae [P,T,T] (nullable) = sum_k prob_k centre_k.  With tm_ij = sum_k prob_k / (1 + centre_k^2 / d0^2),
+ *                     d0 = 1.24 (max(int(sum w), 19) - 15)^(1/3) - 1.8 formed on the device, and for the pair masks m = 1 (pTM)
+ *                     and m = asym_i != asym_j (ipTM): per_alignment_i = sum_j tm_ij m_ij w_i w_j / (1e-8 + sum_j m_ij w_i w_j);
+ *                     ptm / iptm [P] = per_alignment at the FIRST maximal row of per_alignment_i w_i, rows [P,2] int32 that row
+ *                     (pTM, ipTM), per_alignment [P,2,T] (nullable) all rows.  `ws` holds at least
+ *                     pd_metrics_workspace_numel(P, T) floats (= 64 + 2 P T ceil(T / 16)).  P <= 65535.
+ * pd_metrics_clash  : get_has_clash per pose of x_pred [B,A,3] over the atoms with a_mask == 1 and polymer != 0 ([A] floats);
+ *                     chain [A] int32 is the dense chain index 0 .. n_chain - 1 in ascending asym_id order, n_chain <= 64.
+ *                     counts [B,n_chain,n_chain] int32 (workspace, overwritten) = ordered atom pairs closer than 1.1 per chain
+ *                     pair.  has_clash [B] int64 = 1 if n > 100 or 2 n > min(N_a, N_c) for a chain pair of the reference's
+ *                     loop (a over all but the last, c over all but the first chain with eligible atoms, which pairs a middle
+ *                     chain with itself) or, with skip_self_pairs, of a < c.  ranking [B] (nullable) = 0.8 iptm + 0.2 ptm -
+ *                     has_clash with (i)ptm read at b * tm_stride (tm_stride 0 or 1).  B <= 65535, A <= 46340. */
+int pd_metrics_workspace_numel(int P, int T);
+int pd_metrics_plddt(const float* p_plddt, float* atom_plddts, float* mean_plddt, int P, int A, int no_bins, void* stream);
+int pd_metrics_pae_tm(const float* p_pae, const float* centres, const float* weights, const int* asym_id, float* ws, float* pae,
+                      float* ptm, float* iptm, int* rows, float* per_alignment, int P, int T, int no_bins, void* stream);
+int pd_metrics_clash(const float* x_pred, const float* a_mask, const int* chain, const float* polymer, int* counts,
+                     const float* ptm, const float* iptm, int tm_stride, long long* has_clash, float* ranking, int B, int A,
+                     int n_chain, int skip_self_pairs, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

@@ -16,3 +16,5 @@ from .params import param_shapes, seeded_state_dict  # noqa: F401
 from .driver import redock, redock_many  # noqa: F401  (multi-round caller of the sampler, reference redocking.py:156-342)
 from .loss import PhysDockLoss  # noqa: F401  (reference models/loss.py:576-625, forward values; csrc/loss.hip)
 from .loss import ConfidenceLoss, cal_lddt, pae_loss, pde_loss, plddt_loss  # noqa: F401  (reference models/loss.py:320-532; csrc/confidence_loss.hip)
+from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_clash, get_metrics,  # noqa: F401
+                      predicted_tm_score)  # (reference data/tools/get_metrics.py; csrc/metrics.hip)

@@ -228,6 +228,10 @@ def _declare(L):
     sig("pd_conf_frames", p, p, p, p, p, i, i, p)
     sig("pd_conf_loss_plddt", p, p, p, i, p, p, p, p, i, p)
     sig("pd_conf_loss_pairs", i, p, p, p, p, p, p, p, f, f, i, p, p, p, p, i, i, p)
+    sig("pd_metrics_workspace_numel", i, i)                                          # ABI 11, additive (metrics.hip)
+    sig("pd_metrics_plddt", p, p, p, i, i, i, p)
+    sig("pd_metrics_pae_tm", p, p, p, p, p, p, p, p, p, p, i, i, i, p)
+    sig("pd_metrics_clash", p, p, p, p, p, p, p, i, p, p, i, i, i, i, p)
 
 
 def ptr(t):

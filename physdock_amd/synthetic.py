@@ -624,3 +624,182 @@ def confidence_loss_case(name, stored=None):
     x, xp, close, used = clear_confidence_thresholds(x, noise, fn, seed=seed)
     f["x_gt"] = torch.from_numpy(x)
     return {**confidence_logits(A, T, seed), "x_pred": torch.from_numpy(xp)}, f, {**close, "rounds": used, "make_batch": shape, "B": B}
+
+
+# ------------------------------------------------------------------ get_metrics fixtures (tests/golden/g18_metrics_*.npz)
+METRICS_FEAT_KEYS = ("s_mask", "asym_id", "a_mask", "atom_id_to_token_id", "is_ligand")
+METRICS_CASES = ("small", "frac", "onechain", "chains3", "clash", "mid")
+METRICS_SEEDS = {"small": 31, "frac": 33, "onechain": 35, "chains3": 37, "clash": 39, "mid": 41}
+#: chains of a case: (tokens, atoms per token (cycled), is_ligand, asym_id).  asym ids are not dense on purpose.
+METRICS_LAYOUT = {
+    "small": [(10, (2, 3, 4), 0, 3), (9, (2, 3, 4), 0, 5), (5, (1,), 1, 9)],
+    "frac": [(10, (2, 3, 4), 0, 3), (9, (2, 3, 4), 0, 5), (5, (1,), 1, 9)],
+    "onechain": [(19, (2, 3, 4), 0, 7), (5, (1,), 1, 7)],
+    "chains3": [(6, (3, 4), 0, 2), (6, (3, 4), 0, 4), (6, (3, 4), 0, 8)],
+    "clash": [(53, (4,), 0, 1), (46, (5,), 0, 2), (8, (1,), 1, 6)],
+    "mid": [(120, (9,), 0, 1), (78, (9,), 0, 2), (23, (1,), 1, 3)],
+}
+METRICS_POSES = {"small": 3, "frac": 3, "onechain": 2, "chains3": 2, "clash": 5, "mid": 3}
+METRICS_STACKED = {"mid": 3}                      # P stacked logit sets (x_pred then has P rows)
+METRICS_BEST_ROW = {"small": 7, "frac": 7, "onechain": 5, "chains3": 11, "clash": 40, "mid": 150}
+CLASH_DIST, CLASH_MARGIN, TM_GAP, FRAC_MARGIN = 1.1, 1e-4, 1e-4, 1e-3
+
+
+def metrics_logits(A, T, seed, P=None, best_row=0, bins_plddt=50, bins_pae=64):
+    """p_plddt [A,bins] hashed uniform in (-4, 4); p_pae [T,T,bins] = the same minus a per-row slope g_i 6 k / bins that favours
+    the low-error bins, g_i hashed in (0, 1) and 1.5 for `best_row`, so that per_alignment differs from row to row (plain uniform
+    logits give every row the same expectation and no argmax gap).  With P a leading dimension [P, ...] (set p: seed + 100 p,
+    best row best_row + p).  IEEE fp32 products and differences of hashed integers only: bit-identical everywhere."""
+    import numpy as np
+    def one(s, row):
+        pl = hashed_uniform(A * bins_plddt, 3 * s).reshape(A, bins_plddt) * np.float32(8.0)
+        g = hashed_uniform(T, 3 * s + 1) + np.float32(0.5)
+        g[row] = np.float32(1.5)
+        ramp = np.arange(bins_pae, dtype=np.float32) * np.float32(6.0 / bins_pae)
+        pa = hashed_uniform(T * T * bins_pae, 3 * s + 2).reshape(T, T, bins_pae) * np.float32(8.0) - g[:, None, None] * ramp[None, None, :]
+        return pl, pa
+    if P is None:
+        pl, pa = one(seed, best_row)
+    else:
+        pl, pa = (np.stack(v) for v in zip(*[one(seed + 100 * p, best_row + p) for p in range(P)]))
+    return {"p_plddt": torch.from_numpy(pl), "p_pae": torch.from_numpy(pa)}
+
+
+def _lattice(n, origin, seed, spacing=3.0, jitter=0.2):
+    """n points of a cubic lattice (spacing 3, hashed jitter +- 0.2: no two closer than 2.6)"""
+    import numpy as np
+    m = int(np.ceil(n ** (1.0 / 3.0)))
+    idx = np.stack(np.meshgrid(np.arange(m), np.arange(m), np.arange(m), indexing="ij"), -1).reshape(-1, 3)[:n]
+    return (np.asarray(origin, np.float32)[None] + idx.astype(np.float32) * np.float32(spacing)
+            + hashed_uniform(3 * n, seed).reshape(n, 3) * np.float32(2 * jitter))
+
+
+def metrics_case(name, stored=None):
+    """(output, batch, info) of the fixture tests/golden/g18_metrics_<name>.npz (tools/make_golden_metrics.py): output = p_plddt,
+    p_pae (metrics_logits), x_pred [B,A,3]; batch = METRICS_FEAT_KEYS (is_ligand bool, asym_id int32, s_mask / a_mask fp32).
+    With `stored` (the loaded fixture) the features and x_pred come from it and the logits are rebuilt bit for bit.
+    Geometry: every chain on its own jittered lattice 50 A from the others (no contact).  `clash` then moves atoms of chain 1 to
+    0.4 - 0.6 A of atoms of chain 0, exactly one pair each: pose 0 none, pose 1 80 pairs, pose 2 101, pose 3 100, pose 4 ten onto
+    MASKED atoms of chain 0 plus the eight ligand atoms onto chain 1.  info["a_mask_pose"] [5,A] are the per-pose atom masks
+    that turn those counts into the rules (chain 0 has 212 atoms, the main mask a_mask = a_mask_pose[0] hides ten, leaving 202):
+    pose 1 leaves 150 (ratio rule alone: 80 <= 100, 160 > 150), pose 2 the main mask (count rule alone: 101, 202 <= 202),
+    pose 3 leaves 200 (the boundary: 100, ratio exactly 0.5, no clash), pose 4 the main mask."""
+    import numpy as np
+    seed, layout = METRICS_SEEDS[name], METRICS_LAYOUT[name]
+    P = METRICS_STACKED.get(name)
+    if stored is not None:
+        f = {k: torch.from_numpy(np.asarray(stored[k])) for k in METRICS_FEAT_KEYS}
+        A, T = f["a_mask"].shape[0], f["s_mask"].shape[0]
+        return {**metrics_logits(A, T, seed, P, METRICS_BEST_ROW[name]), "x_pred": torch.from_numpy(np.asarray(stored["x_pred"]))}, f, {}
+    chunk, lig, asym, start_atom, pos = [], [], [], [], []
+    for c, (nt, per, is_lig, aid) in enumerate(layout):
+        sizes = [per[t % len(per)] for t in range(nt)]
+        start_atom.append(int(sum(chunk)))
+        chunk += sizes
+        lig += [is_lig] * nt
+        asym += [aid] * nt
+        origin = [(50.0 * c, 0.0, 0.0), (0.0, 50.0 * c, 0.0), (0.0, 0.0, 50.0 * c)][c % 3]
+        pos.append(_lattice(sum(sizes), origin, 7 * seed + c))
+    chunk = np.asarray(chunk)
+    T, A, B = len(chunk), int(chunk.sum()), METRICS_POSES[name]
+    x0 = np.concatenate(pos).astype(np.float32)
+    x = np.stack([x0 + hashed_uniform(3 * A, 11 * seed + b).reshape(A, 3) * np.float32(0.2) for b in range(B)])
+    a_mask, s_mask = np.ones(A, np.float32), np.ones(T, np.float32)
+    info = {}
+    if name in ("small", "frac", "onechain"):
+        s_mask[[1, 4, 8, 13, 17, 22]] = 0.0                  # sum w = 18 < 19: the clip of d0
+        a_mask[[5, 30]] = 0.0
+    if name == "frac":
+        live = s_mask > 0
+        s_mask[live] = (hashed_uniform(T, seed)[live] * np.float32(0.9) + np.float32(0.55))      # (0.1, 1.0)
+        s_mask[0] = 1.0
+    if name == "clash":
+        a0, b0, l0 = start_atom
+        main = a_mask.copy()
+        main[a0 + 202:a0 + 212] = 0.0
+        masks = np.stack([main] * 5)
+        masks[1, a0 + 150:a0 + 202] = 0.0
+        masks[3, a0 + 200:a0 + 202] = 0.0
+        off = hashed_uniform(3 * A, 13 * seed).reshape(A, 3) * np.float32(0.2) + np.asarray([0.5, 0.0, 0.0], np.float32)
+        for b, n in ((1, 80), (2, 101), (3, 100)):
+            x[b, b0:b0 + n] = x[b, a0:a0 + n] + off[:n]
+        x[4, b0:b0 + 10] = x[4, a0 + 202:a0 + 212] + off[:10]
+        x[4, l0:l0 + 8] = x[4, b0 + 20:b0 + 28] + off[:8]
+        a_mask = main
+        info["a_mask_pose"] = masks
+    f = {"s_mask": torch.from_numpy(s_mask), "asym_id": torch.from_numpy(np.asarray(asym, np.int32)), "a_mask": torch.from_numpy(a_mask),
+         "atom_id_to_token_id": torch.from_numpy(np.repeat(np.arange(T), chunk).astype(np.int64)),
+         "is_ligand": torch.from_numpy(np.asarray(lig, bool))}
+    info.update(layout=layout, B=B)
+    return {**metrics_logits(A, T, seed, P, METRICS_BEST_ROW[name]), "x_pred": torch.from_numpy(x.astype(np.float32))}, f, info
+
+
+def metrics_eval(o, f, dtype, skip_self_pairs=False, a_mask=None, max_bin=32.0):
+    """get_metrics restated in numpy at `dtype` (float64: the fixtures' f64_*; float32: a plain fp32 evaluation, whose distance
+    from the former is e32_*).  o: p_plddt [A,nb] / p_pae [T,T,nb] (or with a leading P), x_pred [B,A,3]; returns the reference's
+    keys with leading dim P (has_clash for every pose: [B]), plus rows [P,2], per_alignment [P,2,T], gaps [P,2] (top two of
+    per_alignment_i w_i), closest (eligible inter-chain distance nearest to 1.1) and n_clash [B,n,n] / n_atoms [n]."""
+    import numpy as np
+    pl, pa, x = (np.asarray(o[k]) for k in ("p_plddt", "p_pae", "x_pred"))
+    if pa.ndim == 3:
+        pl, pa = pl[None], pa[None]
+    w = np.asarray(f["s_mask"]).astype(dtype)
+    asym = np.asarray(f["asym_id"])
+    nb = pa.shape[-1]
+    def softmax(l):
+        e = np.exp(l - l.max(-1, keepdims=True))
+        return e / e.sum(-1, keepdims=True)
+    cp = ((np.arange(pl.shape[-1]) + 0.5) / pl.shape[-1]).astype(dtype)
+    atom = (softmax(pl.astype(dtype)) * cp).sum(-1) * dtype(100)
+    centres = _metrics_centres(max_bin, nb).astype(dtype)
+    probs = softmax(pa.astype(dtype))
+    pae = (probs * centres).sum(-1)
+    n = max(int(np.asarray(f["s_mask"]).astype(np.float64).sum()), 19)
+    d0 = dtype(1.24 * (n - 15) ** (1.0 / 3.0) - 1.8)
+    tm = (probs * (dtype(1) / (dtype(1) + centres * centres / (d0 * d0)))).sum(-1)
+    out = {"atom_plddts": atom, "mean_plddt": atom.mean(-1), "pae": pae}
+    rows, pas, gaps, vals = [], [], [], []
+    for m in (np.ones((len(w), len(w)), dtype), (asym[:, None] != asym[None, :]).astype(dtype)):
+        pw = m * (w[None, :] * w[:, None])
+        per = (tm * m * (pw / (dtype(1e-8) + pw.sum(-1, keepdims=True)))).sum(-1)
+        sel = per * w
+        r = sel.argmax(-1)
+        top = np.sort(sel, -1)
+        rows.append(r)
+        pas.append(per)
+        gaps.append(top[:, -1] - top[:, -2])
+        vals.append(np.take_along_axis(per, r[:, None], -1)[:, 0])
+    out["ptm"], out["iptm"] = vals
+    out["rows"], out["per_alignment"], out["gaps"] = np.stack(rows, -1), np.stack(pas, 1), np.stack(gaps, -1)
+    # clash: integer decisions on float64 distances (the fixtures keep every distance CLASH_MARGIN from 1.1)
+    a2t = np.asarray(f["atom_id_to_token_id"])
+    am = np.asarray(f["a_mask"] if a_mask is None else a_mask)
+    el = (am == 1) & (np.asarray(f["is_ligand"]) == 0)[a2t]
+    ca = asym[a2t][el]
+    uniq = np.unique(ca)
+    xe = x[:, el].astype(np.float64)
+    d = np.sqrt(((xe[:, :, None] - xe[:, None]) ** 2).sum(-1))
+    cross = ca[:, None] != ca[None, :]
+    out["closest"] = float(np.abs(d[:, cross] - CLASH_DIST).min()) if cross.any() else float("inf")
+    nat = np.asarray([(ca == u).sum() for u in uniq])
+    ncl = np.asarray([[[(d[b][ca == u][:, ca == v] < CLASH_DIST).sum() for v in uniq] for u in uniq] for b in range(x.shape[0])]).reshape(x.shape[0], len(uniq), len(uniq))
+    has = np.zeros(x.shape[0], np.int64)
+    for b in range(x.shape[0]):
+        for i in range(len(uniq) - 1):
+            for j in range(1, len(uniq)):
+                if skip_self_pairs and not i < j:
+                    continue
+                if ncl[b, i, j] > 100 or 2 * ncl[b, i, j] > min(nat[i], nat[j]):
+                    has[b] = 1
+    out["has_clash"], out["n_clash"], out["n_atoms"] = has, ncl, nat
+    hc = has.astype(dtype) if len(has) == len(vals[0]) else has[:1].astype(dtype)
+    out["ranking_confidence"] = dtype(0.8) * out["iptm"] + dtype(0.2) * out["ptm"] - hc
+    return out
+
+
+def _metrics_centres(max_bin, no_bins):
+    """the reference's bin centres from its own torch fp32 operations (physdock_amd.metrics builds the device table the same way)"""
+    breaks = torch.linspace(0., float(max_bin), no_bins - 1)
+    step = breaks[1] - breaks[0]
+    c = breaks + step / 2
+    return torch.cat([c, (c[-1] + step)[None]]).numpy()
