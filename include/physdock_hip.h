@@ -372,6 +372,17 @@ int pd_confidence_pair_init(const float* z, const float* si, const float* sj, co
                             const long long* centre, float* out, int T, int C, void* stream);
 int pd_pair_symmetrize(const float* z, float* out, int T, int C, void* stream);
 int pd_atom_dist_embed(const float* x, const float* w, const float* b, float* ap, int A, int C, void* stream);
+/* The same passes for a chunk of P poses per launch (additive exports of ABI 11; Engine.confidence_poses).  x holds the poses
+ * x_stride floats apart; outputs are pose-major ([P][T*T][C] / [P][A*A][C]).  Every pose's slice is bit-identical to the
+ * single-pose launcher's output: same thread map, same order of operations.
+ * pd_confidence_pair_init_poses: z, si and sj are read ONCE per launch; per pose only the row of WdT changes
+ * pd_pair_symmetrize_poses     : z, out [P][T*T][C] (out != z)
+ * pd_atom_dist_embed_poses     : ap [P][A*A][C]                                                                             */
+int pd_confidence_pair_init_poses(const float* z, const float* si, const float* sj, const float* WdT, const float* x,
+                                  const long long* centre, float* out, int T, int C, int P, long long x_stride, void* stream);
+int pd_pair_symmetrize_poses(const float* z, float* out, int T, int C, int P, void* stream);
+int pd_atom_dist_embed_poses(const float* x, const float* w, const float* b, float* ap, int A, int C, int P, long long x_stride,
+                             void* stream);
 
 /* ---- feature tensorisation + PDB writer (features.hip) ------------------------
  * The steps either side of the sampler: FeatureLoader.transform (feature_loader.py:970-998) and

@@ -185,6 +185,9 @@ def _declare(L):
     sig("pd_confidence_pair_init", p, p, p, p, p, p, p, i, i, p)
     sig("pd_pair_symmetrize", p, p, i, i, p)
     sig("pd_atom_dist_embed", p, p, p, p, i, i, p)
+    sig("pd_confidence_pair_init_poses", p, p, p, p, p, p, p, i, i, i, ll, p)         # ABI 11, additive (confidence.hip)
+    sig("pd_pair_symmetrize_poses", p, p, i, i, i, p)
+    sig("pd_atom_dist_embed_poses", p, p, p, p, i, i, i, ll, p)
     sig("pd_target_feat", p, p, p, p, i, i, i, p)
     sig("pd_msa_feat", p, p, p, f, p, i, i, i, p)
     sig("pd_outer_mask", p, p, i, p)

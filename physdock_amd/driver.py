@@ -91,7 +91,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
-           sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True) -> dict:
+           sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -100,7 +100,13 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     formatted on the device for the whole batch (pdbio.py).
     `reuse_conditioning`: rounds that see the SAME features (no `batch_msa_feat` re-sampling) share one run of the conditioning
     trunk - the reference recomputes it in every `sample_diffusion` call (model.py:179) with identical inputs and hence identical
-    outputs; here round 0 returns its (a, ap, s, z) and later rounds take them through `conditioning=`.  Bit-identical poses."""
+    outputs; here round 0 returns its (a, ap, s, z) and later rounds take them through `conditioning=`.  Bit-identical poses.
+    `confidence` (a `ConfidenceModule` on the model's device, built for the model's c_s / c_z): the kept poses are also scored
+    without the ground truth - `confidence` = `confidence.score_poses` of the returned `poses` (the aligned ones, in their order) with
+    the trunk's (s, z) of the last sampler call, and `order_confidence` = `ranking.rank_by_confidence` of it, a device LongTensor
+    over the kept poses.  `ranking`, its `order` and `rmsd` are what they are without it."""
+    if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
+        raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
         raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                          "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
@@ -120,6 +126,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(is_lig.sum()))     # redocking.py:195-196
     reuse = bool(reuse_conditioning and getattr(model, "supports_conditioning_reuse", False))
     cond = None
+    conf_sz = None                           # confidence=: (s, z) of the most recent sampler call
     for rnd in range(max_rounds):
         if rnd > 0 and not physics_correction:
             break
@@ -143,10 +150,19 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
                 call.update(conditioning=cond)
             elif physics_correction and rnd + 1 < max_rounds and "batch_msa_feat" not in batch:
                 call.update(return_conditioning=True)
+        want_sz = confidence is not None and call.get("conditioning") is None and not call.get("return_conditioning")
+        if want_sz:
+            call.update(return_conditioning=True)
         with torch.no_grad():
             x_pred = model.sample_diffusion(batch, **call)
         if isinstance(x_pred, tuple):
-            x_pred, cond = x_pred
+            x_pred, got = x_pred
+            if confidence is not None:
+                conf_sz = got[2:]
+            if not want_sz:
+                cond = got
+        elif confidence is not None and call.get("conditioning") is not None:
+            conf_sz = call["conditioning"][2:]
         if rnd + 1 >= max_rounds:            # no later round can take it: the shared conditioning (clones of a [A,c], ap [A,A,c], s,
             cond = None                      # z [T,T,128] - hundreds of MB at large crops, per StreamPool replica) is released here
         # accept / reject (redocking.py:303-317): on the device when a ChiralityReference is given (one kernel, one [B]
@@ -186,11 +202,40 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     if ranking:
         from .ranking import rank_poses
         out["ranking"] = rank_poses(poses, x_gt, w, is_lig)
+    if confidence is not None:
+        out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
         out["receptor_pdb_blocks"] = PdbTemplate(infer_meta_data, receptor_only=True).blocks(aligned)
     return out
+
+
+def conditioning_s_z(sz, T: int):
+    """the trunk's (s [T,c_s], z [T,T,c_z]) at the system's real token count from the last two tensors of a sampler conditioning
+    (s [T',c_s], z [T'*T',c_z] at the padded count T')"""
+    s, z = sz
+    Tp = s.shape[0]
+    return s[:T], z.reshape(Tp, Tp, -1)[:T, :T]
+
+
+def score_kept_poses(confidence, batch, sz, poses) -> dict:
+    """redock(confidence=): {"confidence": ConfidenceModule.score_poses of the kept poses, "order_confidence": their ids best first}.
+    The centre atom of a token is its first atom unless the batch names it (`token_id_to_centre_atom_id`); s_mask / a_mask default
+    to ones.  (The chain index get_metrics caches is then cached in a copy of the batch: one read-back per redock call.)"""
+    from .ranking import rank_by_confidence
+    if sz is None:
+        raise RuntimeError("confidence=: the sampler returned no conditioning to score the poses with")
+    b = dict(batch)
+    if "token_id_to_centre_atom_id" not in b:
+        chunk = batch["token_id_to_chunk_sizes"].long()
+        b["token_id_to_centre_atom_id"] = torch.cumsum(chunk, 0) - chunk
+    for k, ref in (("s_mask", "is_ligand"), ("a_mask", "atom_id_to_token_id")):      # a batch without masks: every token / atom counts
+        if k not in b:
+            b[k] = torch.ones(batch[ref].shape[0], dtype=torch.float32, device=poses.device)
+    s, z = conditioning_s_z(sz, b["token_id_to_centre_atom_id"].shape[0])
+    scores = confidence.score_poses(b, s, z, poses)
+    return {"confidence": scores, "order_confidence": rank_by_confidence(scores)}
 
 
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
@@ -210,9 +255,13 @@ def redock_many(model, systems, *, streams: Optional[int] = None, group: Optiona
     G x num_samples_per_round rows): the systems are dealt out in groups ordered by padded shape (`group_order`), each group's round
     loops run in lockstep - one grouped sampler call per round over its systems still active - with redock's per-system rules
     (accept / reject, adaptive threshold, template pool, conditioning reuse, top-up, ranking).  Systems whose relaxation runs on
-    the host (an RDKit molecule on the host backend, `relax_fn=`) go through `redock` one by one."""
+    the host (an RDKit molecule on the host backend, `relax_fn=`) go through `redock` one by one.
+
+    `confidence=module` (see `redock`) adds `confidence` / `order_confidence` to every result on each of these paths; `pool=` is
+    the `parallel.StreamPool` to run on instead of the model's cached one."""
     items = [(s, {}) if isinstance(s, dict) else (s[0], dict(s[1])) for s in systems]
     pool = common.pop("pool", None)
+    confidence = common.pop("confidence", None)      # popped before every branch (the sequential one included) and handed on by name
     on_gpu = bool(items) and items[0][0]["x_gt"].is_cuda and hasattr(model, "config")
     if group is not None and on_gpu and hasattr(model, "sample_diffusion_many"):
         out: List[Optional[dict]] = [None] * len(items)
@@ -220,21 +269,38 @@ def redock_many(model, systems, *, streams: Optional[int] = None, group: Optiona
         for i, (b, kw) in enumerate(items):
             args = dict(common, **kw)
             if _needs_host_relax(model, b, args.get("ref_mol"), dict(args.get("sampler_kwargs") or {})):
-                out[i] = redock(model, b, **args)
+                out[i] = redock(model, b, **{"confidence": confidence, **args})
             else:
                 grouped.append(i)
         shapes = [tuple(model._prepare_batch(items[i][0])[k].shape[0] for k in ("ref_pos", "target_feat")) for i in grouped]
         for members in group_order(shapes, int(group)):
             idx = [grouped[m] for m in members]
-            for i, r in zip(idx, _redock_group(model, [items[i] for i in idx], common)):
+            for i, r in zip(idx, _redock_group(model, [items[i] for i in idx], common, confidence)):
                 out[i] = r
         return out
     n = streams if streams is not None else (2 if int(common.get("num_samples_per_round", 5)) < 32 else 1)
     if n <= 1 or len(items) <= 1 or not on_gpu:
-        return [redock(model, b, **dict(common, **kw)) for b, kw in items]
+        return [redock(model, b, **{**common, "confidence": confidence, **kw}) for b, kw in items]
     from .parallel import StreamPool
     pool = pool or StreamPool.for_model(model, n=n)      # cached on the model: replicas are built once
-    return pool.map(lambda m, it: redock(m, it[0], **dict(common, **it[1])), items)
+    if confidence is not None:
+        confidence = _SerialConfidence(confidence)
+    return pool.map(lambda m, it: redock(m, it[0], **{**common, "confidence": confidence, **it[1]}), items)
+
+
+class _SerialConfidence:
+    """one ConfidenceModule shared by the host threads / streams of a StreamPool: its engine's workspace buffers serve one call at a
+    time, so a call holds a lock until its stream has drained (the only synchronisation the confidence path adds, and only here)"""
+
+    def __init__(self, module):
+        import threading
+        self.module, self.lock = module, threading.Lock()
+
+    def score_poses(self, *a, **k):
+        with self.lock:
+            r = self.module.score_poses(*a, **k)
+            torch.cuda.current_stream().synchronize()
+            return r
 
 
 def group_order(shapes, group: int) -> List[List[int]]:
@@ -265,7 +331,7 @@ class _RedockState:
     def __init__(self, batch, pbatch, *, ref_mol=None, ref_mol_poses=None, accept_fn=None, chirality=None, physics_correction=False,
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
-                 steps=40, karras_noise_schedule_power=1000):
+                 steps=40, karras_noise_schedule_power=1000, confidence=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -287,6 +353,7 @@ class _RedockState:
         self.use_pocket, self.align_weights, self.ranking, self.seed = use_pocket, align_weights, ranking, seed
         self.infer_meta_data, self.reuse = infer_meta_data, reuse_conditioning
         self.cond, self.done, self.templates = None, False, None
+        self.confidence, self.conf_sz = confidence, None
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -357,6 +424,8 @@ class _RedockState:
         if self.ranking:
             from .ranking import rank_poses
             out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig)
+        if self.confidence is not None:
+            out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
@@ -367,7 +436,7 @@ class _RedockState:
 _MANY_SAMPLER_KEYS = {"seed", "sample_offset", "noise", "use_graph", "mmff_backend", "mmff_iters"}
 
 
-def _redock_group(model, items, common) -> List[dict]:
+def _redock_group(model, items, common, confidence=None) -> List[dict]:
     """redock for the systems of one group, their round loops in lockstep: each round is ONE sample_diffusion_many call over the
     systems still active (same schedule and sample count for all; per-system threshold, template pool, seed, relaxation)"""
     pbs = model._pad_to_group([model._prepare_batch(b) for b, _ in items])
@@ -377,7 +446,7 @@ def _redock_group(model, items, common) -> List[dict]:
         bad = set((args.get("sampler_kwargs") or {})) - _MANY_SAMPLER_KEYS
         if bad:
             raise ValueError(f"redock_many(group=): sampler_kwargs {sorted(bad)} are not supported by grouped sampling")
-        states.append(_RedockState(b, pb, **args))
+        states.append(_RedockState(b, pb, **{"confidence": confidence, **args}))
     for k in ("steps", "karras_noise_schedule_power", "num_samples_per_round", "use_graph", "mmff_backend", "mmff_iters"):
         # one sampler call per round serves the whole group: what it shares must be the same for every system
         vals = {repr(st.kw.get(k)) if k in _MANY_SAMPLER_KEYS else repr(dict(common, **kw).get(k)) for st, (_, kw) in zip(states, items)}
@@ -398,7 +467,7 @@ def _redock_group(model, items, common) -> List[dict]:
                     mmff_gamma_0_factor=[a["factor"] for _, a in active], ode_step_scale_eta=[a["eta"] for _, a in active],
                     ref_mol=[a["ref_mol"] for _, a in active], ref_mol_poses=[a["ref_mol_poses"] for _, a in active],
                     seeds=[a["seed"] for _, a in active], sample_offsets=[a["sample_offset"] for _, a in active],
-                    conditionings=[a["cond"] for _, a in active], return_conditioning=any(a["want_cond"] for _, a in active))
+                    conditionings=[a["cond"] for _, a in active], return_conditioning=confidence is not None or any(a["want_cond"] for _, a in active))
         if any(a["noise"] is not None for _, a in active):
             call.update(noises=[a["noise"] for _, a in active])
         for k in ("use_graph", "mmff_backend", "mmff_iters"):
@@ -408,5 +477,7 @@ def _redock_group(model, items, common) -> List[dict]:
             r = model.sample_diffusion_many([st.pbatch for st, _ in active], **call)
         outs, conds = r if isinstance(r, tuple) else (r, [None] * len(active))
         for (st, a), x, c in zip(active, outs, conds):
+            if confidence is not None and c is not None:
+                st.conf_sz = c[2:]               # (s, z) at the group's padded token count: conditioning_s_z crops them
             st.consume(rnd, x, c if a["want_cond"] else None)
     return [st.result() for st in states]

@@ -93,7 +93,7 @@ class Engine:
         if kw.get("batch", 1) == 1 and kw.get("out_mode", 0) == 0 and M <= 8192 and K >= 256 and not kw.get("a_kmajor"):
             # few rows x long K (token-level projections at a handful of samples): scratch that lets pd_gemm cut K
             ksw = self.ws.get("gemm_ksplit", 9 << 20)
-        ops.gemm(A, W, Y, M, N, K, W3=w3, ksplit_ws=ksw, **kw)
+        return ops.gemm(A, W, Y, M, N, K, W3=w3, ksplit_ws=ksw, **kw)
 
     def trunk_attn_bounds(self, prefix, norm_weight):
         """static |q|, |k|, |v| bounds of a trunk attention (None: keep the bf16 x 6 kernel)"""
@@ -545,6 +545,93 @@ class Engine:
         n_pl = P[pre + ".linear_plddt.weight"].shape[0]
         p_plddt = self.lin(a, pre + ".linear_plddt", A, out=torch.empty(A, n_pl, device=self.device))         # (:86)
         return p_pae.reshape(T, T, n_pae), p_pde.reshape(T, T, n_pde), p_plddt
+
+    def rows_batchable(self, x, wname, out, rows, n):
+        """May the plain Linear `wname` over n stacked groups of `rows` rows run as ONE launch and still give every group the bits
+        of its own launch?  Yes when the library picks the same kernel for both row counts (pd_gemm_variant) and a group consists
+        of whole row tiles of that kernel: pd_gemm sends a ragged row remainder to its general kernel, so a group that ends inside
+        a tile would see its last rows on another kernel than alone.  Long-K launches of few rows may be K-split (Engine.gemm),
+        which depends on the row count: those stay one launch per group."""
+        if n == 1:
+            return True
+        W, b, N, K, ldw = self.P.linear(wname)
+        if K >= 256:
+            return False
+        v1, vn = (self.gemm(x, W, out, m, N, K, lda=K, ldw=ldw, bias=b, query_only=True) for m in (rows, n * rows))
+        tile = 64 if (v1 % 1000) // 100 == 3 else 128
+        return v1 >= 0 and v1 == vn and rows % tile == 0
+
+    def lin_groups(self, x, wname, out, rows, n):
+        """Linear `wname` over x [n * rows, K] -> out [n * rows, N]: one launch where rows_batchable, else one per group"""
+        if self.rows_batchable(x, wname, out, rows, n):
+            self.lin(x, wname, n * rows, out=out)
+            return 1
+        N, K = out.shape[-1], x.shape[-1]
+        for q in range(n):
+            self.lin(off(x, q * rows * K), wname, rows, out=off(out, q * rows * N))
+        return n
+
+    def confidence_poses(self, batch, s_in, z_in, x, dims, chunk, sink, pre="confidence_module"):
+        """ConfidenceModule.forward for every pose of x [P,A,3] (ConfidenceModule.forward_poses / score_poses): per pose the bits of
+        `confidence(batch, s_in, z_in, x[p])`.  The logits of at most `chunk` poses exist at a time, in workspace buffers that are
+        reused from chunk to chunk and from call to call; `sink(p0, n, p_pae [n,T*T,c_pae], p_pde [n,T*T,c_pde], p_plddt
+        [n,A,c_plddt])` consumes each chunk (views of those buffers: it must copy or reduce them before it returns).
+        Once per call: linear_s_i / linear_s_j of s, the transposed pair mask, the packed linear_d table.  Once per chunk: the
+        entry z of all its poses from ONE read of z_in, s_i, s_j (pd_confidence_pair_init_poses), the atom-pair distance
+        embedding (pd_atom_dist_embed_poses), z + z^T, the two pair heads and linear_plddt over the chunk's rows (lin_groups).
+        Per pose: the Pairformer and AtomTransformer stacks, on the trunk's entry points as `confidence` runs them, and the
+        linear_s_a gather (it reads s AFTER the Pairformer, which depends on the pose through z)."""
+        P, ws = self.P, self.ws
+        Ca, Cap, Cs, Cz = dims["c_a"], dims["c_ap"], dims["c_s"], dims["c_z"]
+        T, A, NP = s_in.shape[0], x.shape[1], x.shape[0]
+        self.Ar, self.Tr = batch.get("_A_real", A), batch.get("_T_real", T)
+        z_mask = batch["z_mask"]
+        z_maskT = z_mask.t().contiguous()
+        L = ops._lib.init()
+        sp = ops.stream()
+        si = self.lin(s_in, pre + ".linear_s_i", T)
+        sj = self.lin(s_in, pre + ".linear_s_j", T)
+        WdT = P._c(("conf_WdT", pre), lambda: P[pre + ".linear_d.weight"].t().contiguous())
+        n_pae, n_pde, n_pl = (P[f"{pre}.linear_{k}.weight"].shape[0] for k in ("pae", "pde", "plddt"))
+        chunk = max(1, min(int(chunk), NP))
+        z = ws.get("confp_z", chunk, T * T, Cz)
+        zs = ws.get("confp_zs", chunk, T * T, Cz)
+        s = ws.get("confp_s", chunk, T, Cs)
+        a0 = ws.get("confp_a0", chunk, A, Ca)
+        a = ws.get("confp_a", chunk, A, Ca)
+        ap = ws.get("confp_ap", chunk, A * A, Cap)
+        p_pae = ws.get("confp_pae", chunk, T * T, n_pae)
+        p_pde = ws.get("confp_pde", chunk, T * T, n_pde)
+        p_plddt = ws.get("confp_plddt", chunk, A, n_pl)
+        a2t, ctr = batch["atom_id_to_token_id"], batch["token_id_to_centre_atom_id"]
+        for p0 in range(0, NP, chunk):
+            n = min(chunk, NP - p0)
+            xc = x[p0:p0 + n]
+            ops.check(L.pd_confidence_pair_init_poses(ops.ptr(z_in), ops.ptr(si), ops.ptr(sj), ops.ptr(WdT), ops.ptr(xc), ops.ptr(ctr),
+                                                      ops.ptr(z), T, Cz, n, 3 * A, sp), "confidence_pair_init_poses")     # (:68-72)
+            s[:n].copy_(s_in[None].expand(n, T, Cs))
+            for q in range(n):
+                self.pairformer(pre + ".pairformer", s[q], z[q], T, Cs, Cz, z_mask, z_maskT, dims["no_blocks_heads"])     # (:74)
+            ops.check(L.pd_pair_symmetrize_poses(ops.ptr(z), ops.ptr(zs), T, Cz, n, sp), "pair_symmetrize_poses")         # (:75)
+            self.lin_groups(zs, pre + ".linear_pae", p_pae, T * T, n)                                                      # (:76-77)
+            self.lin_groups(zs, pre + ".linear_pde", p_pde, T * T, n)
+            a0[:n].zero_()
+            for q in range(n):                                                                                             # (:79)
+                ta = self.lin(s[q], pre + ".linear_s_a", T)
+                ops.check(L.pd_gather_rows_add(ops.ptr(a0[q]), ops.ptr(ta), ops.ptr(a2t), A, Ca, sp), "gather_rows_add")
+            ops.check(L.pd_atom_dist_embed_poses(ops.ptr(xc), ops.ptr(P[pre + ".linear_z_a.weight"]), ops.ptr(P[pre + ".linear_z_a.bias"]),
+                                                 ops.ptr(ap), A, Cap, n, 3 * A, sp), "atom_dist_embed_poses")             # (:80)
+            a[:n].copy_(a0[:n])
+            for q in range(n):
+                self.atom_transformer(pre + ".atom_transformer", a[q], ap[q], A, Ca, Cap, batch["ap_mask"], dims["no_blocks_atom"])
+            ops.check(L.pd_axpby(ops.ptr(a), ops.ptr(a0), 1.0, ops.ptr(a), None, 1.0, n * A * Ca, sp), "axpby")           # (:82-84)
+            self.lin_groups(a, pre + ".linear_plddt", p_plddt, A, n)                                                       # (:86)
+            sink(p0, n, p_pae[:n], p_pde[:n], p_plddt[:n])
+
+    @staticmethod
+    def confidence_pose_bytes(T, A, dims, n_pae=64, n_pde=64, n_pl=50):
+        """workspace bytes confidence_poses needs per pose of a chunk (the buffers listed there)"""
+        return 4 * (T * T * (2 * dims["c_z"] + n_pae + n_pde) + T * dims["c_s"] + A * (2 * dims["c_a"] + n_pl) + A * A * dims["c_ap"])
 
     def msa_column_attention(self, prefix, m, S, T, C):
         """m += MSAColumnAttention(m): attention along the MSA-row axis, no bias (attentions.py:117-136)"""

@@ -122,6 +122,17 @@ def _dense_chain(asym_atom):
     return inv.to(torch.int32).contiguous(), int(uniq.shape[0])
 
 
+def _chain_index(batch):
+    """(dense chain index [A] int32, per-atom polymer flag [A] fp32, number of chains) of a batch dict, computed on the first call
+    (one read-back, see the module docstring) and cached in the dict"""
+    cached = batch.get(_CACHE_KEY)
+    if cached is None:                                       # once per system: torch.unique reads the chain count back
+        idx = batch["atom_id_to_token_id"].long()
+        chain, n_chain = _dense_chain(batch["asym_id"][idx])
+        cached = batch[_CACHE_KEY] = (chain, (batch["is_ligand"] == 0)[idx].float().contiguous(), n_chain)
+    return cached
+
+
 def _poses(x_pred):
     x = _f(x_pred)
     if x.dim() == 2:
@@ -216,12 +227,7 @@ def get_metrics(output, batch, *, all_poses=False, skip_self_pairs=False):
             raise ValueError(f"stacked logits of {P} poses need x_pred with {P} rows, got {x.shape[0]}")
     elif not all_poses:
         x = x[:1]
-    cached = batch.get(_CACHE_KEY)
-    if cached is None:                                       # once per system: torch.unique reads the chain count back
-        idx = a2t.long()
-        chain, n_chain = _dense_chain(asym[idx])
-        cached = batch[_CACHE_KEY] = (chain, (is_lig == 0)[idx].float().contiguous(), n_chain)
-    chain, poly, n_chain = cached
+    chain, poly, n_chain = _chain_index(batch)
     atom, mean = _plddt(lp)
     r = _pae_tm(la, _f(s_mask), _i32(asym), 32.0)
     has, rank = _clash(x, _f(a_mask), chain, poly, n_chain, skip_self_pairs, r["ptm"], r["iptm"])

@@ -131,12 +131,13 @@ def gemm(A, W, Y, M, N, K, *, lda=None, ldw=None, ldy=None, batch=1, sA=0, sW=0,
          hn_split=32, hn_eps=0.0, act=ACT_NONE, glu=0, rowscale=None, maskadd=None, maskval=0.0,
          mul=None, ldmul=0, mul_rows_per_group=0, mul_gstride=0, out_scale=1.0, res=None, ldres=0,
          res_row_mod=0, sRes=0, out_mode=OUT_ROWMAJOR, T1=0, T2=0, frag_transpose=False, W3=None, ksplit_ws=None, A3=None,
-         W2=None, a_amax=None, A2=None, Y2=None, y2_amax=None, y2_col0=0, stats_inline=None):
+         W2=None, a_amax=None, A2=None, Y2=None, y2_amax=None, y2_col0=0, stats_inline=None, query_only=False):
     """Y = epilogue(prologue(A) @ W^T); see include/physdock_hip.h pd_gemm_args.
     A/W/Y and the optional operands may be tensors or raw device addresses (ints).
     stats_inline=(mode, eps) with stats = an (uninitialised) [M, 2] scratch tensor: the row statistics of A are the launch's own
     business - computed inside the kernel when pd_gemm would run it on the fp32 streaming kernel anyway (few samples, the trunk's
-    small tracks: one launch less), by a pd_rowstats launch into `stats` first otherwise."""
+    small tracks: one launch less), by a pd_rowstats launch into `stats` first otherwise.
+    query_only=True launches nothing and returns the kernel pd_gemm would pick for these arguments (pd_gemm_variant)."""
     def P(x):
         return x if (x is None or isinstance(x, int)) else ptr(x)
     n_out = N // 2 if glu else N
@@ -178,6 +179,10 @@ def gemm(A, W, Y, M, N, K, *, lda=None, ldw=None, ldy=None, batch=1, sA=0, sW=0,
     a.out_mode, a.T1, a.T2, a.frag_transpose = out_mode, T1, T2, int(frag_transpose)
     if ksplit_ws is not None and KSPLIT_GEMM:
         a.ksplit_ws, a.ksplit_ws_bytes = ptr(ksplit_ws), ksplit_ws.numel() * 4
+    if query_only:
+        if stats_inline is not None:
+            raise ValueError("query_only does not cover stats_inline launches")
+        return _lib.init().pd_gemm_variant(C.byref(a))
     if stats_inline is not None:
         mode_, eps_ = stats_inline
         key = (M, N, K, a.lda, int(glu), hn_w is not None, mul is not None, res is not None, pro_rows_per_group > 0, out_mode, act, pro_act,

@@ -2,7 +2,7 @@
 
 Device side: align every accepted pose into the ground-truth frame (pocket-weighted Kabsch, redocking.py:341-342),
 ligand RMSD to the ground truth (:382), the pairwise ligand-RMSD matrix (:389-390) and the template re-selection
-metric (:326-335).  Host side: the K-means(5) + medoid choice on that (n x n, n <= ~100) matrix exactly as the
+metric (:326-335); without a ground truth, the order by the confidence head's scores (rank_by_confidence).  Host side: the K-means(5) + medoid choice on that (n x n, n <= ~100) matrix exactly as the
 reference does it with scikit-learn (:392-416); when scikit-learn is missing a deterministic Lloyd iteration with
 farthest-point seeding is used instead (documented divergence: the cluster labels then differ from sklearn's).
 """
@@ -75,3 +75,14 @@ def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Te
     else:
         ids = list(range(n))
     return {"order": ids, "rmsd": [float(rh[i]) for i in ids], "x_aligned": x_al, "dist": D, "rmsd_all": r}
+
+
+def rank_by_confidence(scores) -> torch.Tensor:
+    """Pose ids, best first, by the ground-truth-free scores of `ConfidenceModule.score_poses` (or of `get_metrics` on stacked
+    logits): descending ranking_confidence, ties by descending mean_plddt, then by ascending pose id.  LongTensor [P] on the
+    scores' device: two stable sorts there, nothing is read back."""
+    rc, pl = scores["ranking_confidence"].reshape(-1), scores["mean_plddt"].reshape(-1)
+    if rc.shape != pl.shape:
+        raise ValueError(f"ranking_confidence {tuple(rc.shape)} and mean_plddt {tuple(pl.shape)} differ in the number of poses")
+    by_plddt = torch.sort(pl, descending=True, stable=True).indices          # stable: equal pLDDT keeps ascending pose id
+    return by_plddt[torch.sort(rc[by_plddt], descending=True, stable=True).indices]

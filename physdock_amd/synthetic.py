@@ -803,3 +803,64 @@ def _metrics_centres(max_bin, no_bins):
     step = breaks[1] - breaks[0]
     c = breaks + step / 2
     return torch.cat([c, (c[-1] + step)[None]]).numpy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# G19: the confidence head over several poses of one system (ConfidenceModule.forward_poses / score_poses)
+CONF_POSES_CASES = {"small": dict(n=(4, 5, 32, 8), seed=11, poses=5), "ragged": dict(n=(17, 5, 6, 8), seed=4, poses=3)}
+CONF_POSES_FEAT_KEYS = ("s_mask", "asym_id", "a_mask", "atom_id_to_token_id", "is_ligand")
+
+
+def confidence_poses_case(name):
+    """(config block, batch, inputs) of a G19 fixture: a synthetic system (small: T 36 / A 52; ragged: T 23 / A 91, neither a
+    multiple of 4), trunk-like s / z and P poses around x_gt that differ where the confidence head looks - 0: lightly noised;
+    1: the ligand rotated by 90 degrees about its centroid and shifted; last: the second protein chain pushed onto the first
+    (0.3 A from its atoms: a clear chain clash); the others (with three poses: pose 1 as well): the whole complex dilated, so that
+    centre distances reach the far bins, with the ligand shifted.  The metrics' chain features are set here (the protein split into two chains, then the
+    ligand), since the confidence head itself reads none of them."""
+    c = CONF_POSES_CASES[name]
+    from .configs import small_config
+    cm = dict(small_config().model.confidence_module)
+    batch = dict(make_batch(*c["n"], seed=c["seed"]))
+    inp = confidence_inputs(batch, cm["c_s"], cm["c_z"], seed=5 + c["seed"], n_pose=1)
+    batch["token_id_to_centre_atom_id"] = inp["token_id_to_centre_atom_id"]
+    n_prot, apr, n_lig = c["n"][0], c["n"][1], c["n"][2]
+    T, A = n_prot + n_lig, n_prot * apr + n_lig
+    half = n_prot // 2
+    batch["asym_id"] = torch.tensor([0] * half + [1] * (n_prot - half) + [2] * n_lig, dtype=torch.int32)
+    batch["is_ligand"] = torch.tensor([False] * n_prot + [True] * n_lig)
+    batch["s_mask"], batch["a_mask"] = torch.ones(T), torch.ones(A)
+    g = torch.Generator(device="cpu")
+    g.manual_seed(103 + c["seed"])
+    x0 = batch["x_gt"].float()
+    lig = torch.arange(A) >= n_prot * apr
+    ch0, ch1 = torch.arange(0, half * apr), torch.arange(half * apr, n_prot * apr)
+    poses = []
+    for p in range(c["poses"]):
+        x = x0 + 0.3 * torch.randn(A, 3, generator=g)
+        if p == c["poses"] - 1:
+            n = min(len(ch0), len(ch1))
+            x[ch1[:n]] = x[ch0[:n]] + torch.tensor([0.3, 0.0, 0.0])
+        else:
+            if p == 1:
+                cen = x[lig].mean(0)
+                rot = torch.tensor([[0.0, -1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, 1.0]])
+                x[lig] = (x[lig] - cen) @ rot.t() + cen + torch.tensor([4.0, -2.0, 1.0])
+            if p >= 2 or (p == 1 and c["poses"] <= 3):
+                x = (x - x.mean(0)) * (1.0 + 0.5 * max(p, 2)) + x.mean(0)
+                x[lig] += torch.tensor([0.0, 3.0 * p, -2.0])
+        poses.append(x)
+    inp["x_pred"] = torch.stack(poses, 0)
+    return cm, batch, inp
+
+
+CONF_POSES_WD_SCALE = 12.0
+
+
+def confidence_poses_weights(cm):
+    """the G12 weights (seed 3) with linear_d - the only weight that sees the pose on the pair track - scaled up, so that the poses'
+    scores lie well apart (seeded weights of unit scale leave the random z in charge and every pose with nearly the same pTM)"""
+    from .params import confidence_param_shapes, seeded_state_dict
+    sd = seeded_state_dict(confidence_param_shapes(**cm), seed=3)
+    sd["linear_d.weight"] = sd["linear_d.weight"] * CONF_POSES_WD_SCALE
+    return sd
