@@ -160,6 +160,8 @@ def test_grouped_pool_unpool_precond_match_per_group_launches():
         b1 = ba[gi * B:(gi + 1) * B].clone()
         ops.check(L.pd_unpool_add(ops.ptr(b1), ops.ptr(us[gi * B:(gi + 1) * B]), ops.ptr(a2t[gi]), B, A, T, Ca, sp), "unpool")
         assert torch.equal(bg[gi * B:(gi + 1) * B], b1)
+        # and the pair of launches against something outside themselves: the same fp32 add on the CPU
+        assert torch.equal(b1.cpu(), ba[gi * B:(gi + 1) * B].cpu() + us[gi * B:(gi + 1) * B].cpu()[:, a2t[gi].cpu()])
     # precond
     x = torch.randn(G * B, A, 3, generator=g).cuda()
     Wx, bx = torch.randn(Ca, 3, generator=g).cuda(), torch.randn(Ca, generator=g).cuda()

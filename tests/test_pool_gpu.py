@@ -69,6 +69,17 @@ def test_fused_downscale_pool_vs_float64_and_two_launches(B, chunks_kind, N):
     print(f"downscale + pool {chunks_kind} B={B} T={T} A={A_real} tpb={tpb}: max error vs float64 fused {e_fused:.2e}, two launches {e_two:.2e} (mean |pooled| {mag:.2f})")
     # (inputs of wide dynamic range: both forms sit at the fp32 rounding of sums of ~10 terms of magnitude ~10)
     assert e_fused <= 1.2 * e_two + 1e-6 and e_fused <= 1e-4 * max(1.0, mag)
+    # the yardstick itself: the two-launch form's error against float64 is, element by element, what pd_segment_pool may add to
+    # the pooling of the GEMM's output as it stands (the derived bound of tests/trunk_glue_ref.py on that very input) plus the
+    # GEMM's own error |ud - u| carried through the same pooling (a mean with non-negative weights: the triangle inequality)
+    import trunk_glue_ref as tr
+    ud64 = ud.cpu().double().reshape(B, A, N)
+    pool_bound = tr.segment_pool_bound(ud64, ts, s)
+    r_two = tr.bound_ratio(out2.cpu(), ref, pool_bound + tr.segment_pool64((ud64 - u).abs(), ts))
+    print(f"two launches: worst |error| / (pool bound + pooled GEMM error) {r_two:.3f}")
+    assert r_two <= 1.0, r_two
+    # and pd_segment_pool alone: against the float64 pooling of the GEMM's output, under the derived bound with no GEMM term
+    tr.assert_within_bound("segment_pool", f"{chunks_kind} B={B}", out2.cpu(), tr.segment_pool64(ud64, ts, s), pool_bound)
 
 
 def test_unsupported_shapes_are_refused_not_mangled():
