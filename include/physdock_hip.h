@@ -441,6 +441,14 @@ int pd_pose_dist(const float* poses, float* D, int Cn, int L, void* stream);
  * every pose to ref: the device half of the ranking step (redocking.py:357-423)                  */
 int pd_pairwise_rmsd(const float* x, const int* idx, const float* ref, float* D, float* rmsd_ref, int n, int A, int L,
                      void* stream);
+/* symmetry-corrected form of pd_pairwise_rmsd (sym_rmsd.hip; ABI 11, additive): perms_t [L][M] is a table of M permutations of
+ * the L ligand atoms, atom-major (perms_t[a*M + m] = image of atom a under row m; row 0 the identity by convention).  For i < j
+ *   D[i,j] = D[j,i] = sqrt( min_m (1/L) sum_a |x_i[idx[a]] - x_j[idx[perms[m][a]]]|^2 ),   D[i,i] = 0,
+ * rmsd_ref[i] the same against ref [A,3] and best_perm_ref[i] the smallest m that attains the fp32 minimum (ref, and
+ * best_perm_ref on its own, may be NULL).  Each sum runs over a in ascending order in one thread and the minimum is exact.
+ * L <= 1024, M <= 65535, n <= 65535 (else PD_ERR_UNSUPPORTED).                                                              */
+int pd_sym_rmsd(const float* x, const int* idx, const float* ref, const unsigned short* perms_t, float* D, float* rmsd_ref,
+                int* best_perm_ref, int n, int A, int L, int M, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

@@ -18,3 +18,4 @@ from .loss import PhysDockLoss  # noqa: F401  (reference models/loss.py:576-625,
 from .loss import ConfidenceLoss, cal_lddt, pae_loss, pde_loss, plddt_loss  # noqa: F401  (reference models/loss.py:320-532; csrc/confidence_loss.hip)
 from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_clash, get_metrics,  # noqa: F401
                       predicted_tm_score)  # (reference data/tools/get_metrics.py; csrc/metrics.hip)
+from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-corrected ligand RMSD for the ranking step; csrc/sym_rmsd.hip)

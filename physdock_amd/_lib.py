@@ -235,12 +235,13 @@ def _declare(L):
     sig("pd_metrics_plddt", p, p, p, i, i, i, p)
     sig("pd_metrics_pae_tm", p, p, p, p, p, p, p, p, p, p, i, i, i, p)
     sig("pd_metrics_clash", p, p, p, p, p, p, p, i, p, p, i, i, i, i, p)
+    sig("pd_sym_rmsd", p, p, p, p, p, p, p, i, i, i, i, p)                               # ABI 11, additive (sym_rmsd.hip)
 
 
 def ptr(t):
     if t is None:
         return None
-    assert t.is_cuda and t.dtype in (torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8, torch.bfloat16, torch.float16), (t.device, t.dtype)
+    assert t.is_cuda and t.dtype in (torch.float32, torch.float64, torch.int32, torch.int64, torch.int16, torch.uint8, torch.bfloat16, torch.float16), (t.device, t.dtype)
     return t.data_ptr()
 
 

@@ -91,7 +91,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
-           sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None) -> dict:
+           sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
+           ligand_symmetry=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -104,7 +105,9 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `confidence` (a `ConfidenceModule` on the model's device, built for the model's c_s / c_z): the kept poses are also scored
     without the ground truth - `confidence` = `confidence.score_poses` of the returned `poses` (the aligned ones, in their order) with
     the trunk's (s, z) of the last sampler call, and `order_confidence` = `ranking.rank_by_confidence` of it, a device LongTensor
-    over the kept poses.  `ranking`, its `order` and `rmsd` are what they are without it."""
+    over the kept poses.  `ranking`, its `order` and `rmsd` are what they are without it.
+    `ligand_symmetry` (a `symmetry.LigandSymmetry` of the ligand's atoms in pose order): `ranking` is built from the
+    symmetry-corrected ligand RMSD (`rank_poses(..., symmetry=)`); sampling, accept / reject and the confidence scores do not see it."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -201,7 +204,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     out = {"poses": aligned, "accepted": n_accepted, "rounds": log, "gamma_factor": factor, "ranking": None}
     if ranking:
         from .ranking import rank_poses
-        out["ranking"] = rank_poses(poses, x_gt, w, is_lig)
+        out["ranking"] = rank_poses(poses, x_gt, w, is_lig, symmetry=ligand_symmetry)
     if confidence is not None:
         out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
     if infer_meta_data is not None:
@@ -241,7 +244,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -331,7 +334,7 @@ class _RedockState:
     def __init__(self, batch, pbatch, *, ref_mol=None, ref_mol_poses=None, accept_fn=None, chirality=None, physics_correction=False,
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
-                 steps=40, karras_noise_schedule_power=1000, confidence=None):
+                 steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -354,6 +357,7 @@ class _RedockState:
         self.infer_meta_data, self.reuse = infer_meta_data, reuse_conditioning
         self.cond, self.done, self.templates = None, False, None
         self.confidence, self.conf_sz = confidence, None
+        self.ligand_symmetry = ligand_symmetry
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -423,7 +427,7 @@ class _RedockState:
         out = {"poses": aligned, "accepted": n_accepted, "rounds": self.log, "gamma_factor": self.factor, "ranking": None}
         if self.ranking:
             from .ranking import rank_poses
-            out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig)
+            out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig, symmetry=self.ligand_symmetry)
         if self.confidence is not None:
             out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
         if self.infer_meta_data is not None:

@@ -15,17 +15,32 @@ from . import ops
 from .model import weighted_rigid_align
 
 
-def pairwise_ligand_rmsd(x_aligned: torch.Tensor, ligand_idx: torch.Tensor, x_gt: torch.Tensor | None = None):
-    """x_aligned [n,A,3] (device), ligand_idx int32 [L] -> (D [n,n], rmsd_to_gt [n] or None)"""
+def pairwise_ligand_rmsd(x_aligned: torch.Tensor, ligand_idx: torch.Tensor, x_gt: torch.Tensor | None = None, symmetry=None,
+                         return_perm: bool = False):
+    """x_aligned [n,A,3] (device), ligand_idx int32 [L] -> (D [n,n], rmsd_to_gt [n] or None).
+    `symmetry` (a `symmetry.LigandSymmetry` over the L ligand atoms in the order of ligand_idx): every value is the minimum over
+    the ligand's automorphisms (kernel pd_sym_rmsd) instead of the index-wise RMSD; `return_perm=True` then adds, as a third
+    element, the table row that attains the minimum against x_gt (int32 [n], None without x_gt)."""
     L_ = ops._lib.init()
     n, A = x_aligned.shape[0], x_aligned.shape[1]
     x = x_aligned.float().contiguous()
     D = torch.empty(n, n, device=x.device)
     r = torch.empty(n, device=x.device) if x_gt is not None else None
-    ops.check(L_.pd_pairwise_rmsd(ops.ptr(x), ops.ptr(ligand_idx), ops.ptr(x_gt.float().contiguous()) if x_gt is not None else None,
-                                  ops.ptr(D), ops.ptr(r) if r is not None else None, n, A, int(ligand_idx.numel()), ops.stream()),
-              "pd_pairwise_rmsd")
-    return D, r
+    if symmetry is None:
+        if return_perm:
+            raise ValueError("return_perm needs symmetry=")
+        ops.check(L_.pd_pairwise_rmsd(ops.ptr(x), ops.ptr(ligand_idx), ops.ptr(x_gt.float().contiguous()) if x_gt is not None else None,
+                                      ops.ptr(D), ops.ptr(r) if r is not None else None, n, A, int(ligand_idx.numel()), ops.stream()),
+                  "pd_pairwise_rmsd")
+        return D, r
+    if symmetry.n_atoms != int(ligand_idx.numel()):
+        raise ValueError(f"symmetry is a table over {symmetry.n_atoms} atoms, ligand_idx holds {int(ligand_idx.numel())}")
+    best = torch.empty(n, dtype=torch.int32, device=x.device) if (return_perm and x_gt is not None) else None
+    ops.check(L_.pd_sym_rmsd(ops.ptr(x), ops.ptr(ligand_idx), ops.ptr(x_gt.float().contiguous()) if x_gt is not None else None,
+                             ops.ptr(symmetry.table(x.device)), ops.ptr(D), ops.ptr(r) if r is not None else None,
+                             ops.ptr(best) if best is not None else None, n, A, symmetry.n_atoms, symmetry.n_perms, ops.stream()),
+              "pd_sym_rmsd")
+    return (D, r, best) if return_perm else (D, r)
 
 
 def get_representatives(distance_matrix: np.ndarray, num_clusters: int = 5):
@@ -56,12 +71,15 @@ def get_representatives(distance_matrix: np.ndarray, num_clusters: int = 5):
 
 
 def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Tensor, is_ligand_atom: torch.Tensor,
-               num_clusters: int = 5):
+               num_clusters: int = 5, symmetry=None):
     """Accepted poses [n,A,3] -> dict(order=ranked pose ids (global medoid first, redocking.py:410-418),
-    rmsd=ligand RMSD to x_gt of the ranked poses, x_aligned, dist)."""
+    rmsd=ligand RMSD to x_gt of the ranked poses, x_aligned, dist).
+    With `symmetry` (symmetry.LigandSymmetry) dist, rmsd_all, rmsd and order are built from the symmetry-corrected RMSD, and
+    the dict also holds rmsd_plain_all (the index-wise values the reference reports) and symmetry_complete (False: the
+    automorphism table was cut, the corrected values are upper bounds)."""
     x_al = weighted_rigid_align(x_gt[None].expand(x_pred.shape[0], -1, -1).contiguous(), x_pred, align_weights)
     lig = torch.nonzero(is_ligand_atom.to(x_pred.device) > 0).flatten().to(torch.int32)
-    D, r = pairwise_ligand_rmsd(x_al, lig, x_gt)
+    D, r = pairwise_ligand_rmsd(x_al, lig, x_gt, symmetry=symmetry)
     Dh, rh = D.cpu().numpy().astype(np.float64), r.cpu().numpy()
     n = len(Dh)
     if n > num_clusters:
@@ -74,7 +92,11 @@ def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Te
             ids = [first] + ids[:num_clusters - 1]
     else:
         ids = list(range(n))
-    return {"order": ids, "rmsd": [float(rh[i]) for i in ids], "x_aligned": x_al, "dist": D, "rmsd_all": r}
+    out = {"order": ids, "rmsd": [float(rh[i]) for i in ids], "x_aligned": x_al, "dist": D, "rmsd_all": r}
+    if symmetry is not None:
+        out["rmsd_plain_all"] = pairwise_ligand_rmsd(x_al, lig, x_gt)[1]
+        out["symmetry_complete"] = bool(symmetry.complete)
+    return out
 
 
 def rank_by_confidence(scores) -> torch.Tensor:
