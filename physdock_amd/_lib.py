@@ -161,7 +161,6 @@ def _declare(L):
     sig("pd_pair_bias_split", p, p, p, p, p, f, f, p, i, i, f, p, f, p)
     sig("pd_attention", C.POINTER(AttnArgs), p)
     sig("pd_attention_variant", C.POINTER(AttnArgs))
-    sig("pd_attention_tail", C.POINTER(AttnArgs), C.POINTER(C.c_int))
     sig("pd_attention_bias_prescale_log2", f, f, f)
     sig("pd_graph_begin", p)
     sig("pd_graph_end", p, C.POINTER(C.c_void_p))

@@ -272,21 +272,13 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const pd_attn_args p)
 
 // number of key chunks pd_attention would use (1 = no split): only when the launch leaves most of the chip idle, the
 // key range is long enough and the caller supplied a workspace of nsplit * nbatch * nq * (32 + 2) * nheads floats
-#ifndef PD_ATTN_MIN_WAVES
-#define PD_ATTN_MIN_WAVES 128      // (round 5: 1024 -> 128; per call at 1 / 2 / 4 / 7 samples 87.8 / 94.2 / 103.9 / 122.5 -> 85.0 / 91.6 / 101.2 / 119.6 ms: a 256-key launch of 32 blocks is latency-bound on either pipe and the fp16-format kernels have the shorter chain)
-#endif
-#ifndef PD_ATTN_NOSPLIT_BLOCKS
-#define PD_ATTN_NOSPLIT_BLOCKS 320     // 128-query blocks from which a launch is not key-split (5 samples x 4 heads x 2048 atoms: 109.6 -> 106.2 ms per call, 7 samples 127 -> 122; at 256 blocks the split still wins)
-#endif
+constexpr int ATTN_MIN_WAVES = 128;      // query waves from which the split-operand kernels take a launch (round 5: 1024 -> 128; per call at 1 / 2 / 4 / 7 samples 87.8 / 94.2 / 103.9 / 122.5 -> 85.0 / 91.6 / 101.2 / 119.6 ms: a 256-key launch of 32 blocks is latency-bound on either pipe and the fp16-format kernels have the shorter chain)
+constexpr int ATTN_NOSPLIT_BLOCKS = 320;     // 128-query blocks from which a launch is not key-split (5 samples x 4 heads x 2048 atoms: 109.6 -> 106.2 ms per call, 7 samples 127 -> 122; at 256 blocks the split still wins)
 static int attn_nsplit(const pd_attn_args* a) {
-#ifdef PD_LAB
-    static const int on = [] { const char* e = getenv("PD_ATTN_SPLIT"); return e ? atoi(e) : 1; }();
-    if (!on) return 1;
-#endif
     if (!a->ws) return 1;
     const long long blocks = (long long)a->nbatch * a->nheads * ((a->nq + 127) / 128);
     const int nit = (a->nk + KT - 1) / KT;
-    if (blocks >= PD_ATTN_NOSPLIT_BLOCKS || nit < 8) return 1;
+    if (blocks >= ATTN_NOSPLIT_BLOCKS || nit < 8) return 1;
     long long s = 1024 / blocks;
     s = s < nit / 4 ? s : nit / 4;
     s = s < 8 ? s : 8;
@@ -307,49 +299,13 @@ PD_EXPORT int pd_attention_variant(const pd_attn_args* a) {
     if (!a) return PD_ERR_ARG;
     // the bf16 split-operand kernel pays off when the launch fills the chip (>= one 32-query wave per SIMD); smaller launches
     // are latency-bound and stay on the fp32-MFMA kernel (with its key-split option)
-    if (!a->fp32_mfma && attn_nsplit(a) <= 1 && (long long)a->nbatch * a->nheads * ((a->nq + 31) / 32) >= PD_ATTN_MIN_WAVES)
+    if (!a->fp32_mfma && attn_nsplit(a) <= 1 && (long long)a->nbatch * a->nheads * ((a->nq + 31) / 32) >= ATTN_MIN_WAVES)
         return (a->f16x3 ? (pd_attention_pipe_ok(a) ? 3000 : 2000) : 1000) + (a->nq > 128 ? 8 : 4);      // 2000 +: two-part fp16 operands (attn_f16.hip); 3000 +: pipelined (attn_pipe.hip)
-#ifdef PD_LAB
-    static const int wide = [] { const char* e = getenv("PD_ATTN_WIDE"); return e ? atoi(e) : 1; }();
-#else
-    constexpr int wide = 1;
-#endif
     // 8-wave blocks pay off (+2 %) when they still fill the chip twice over; short query ranges / few batches keep 4 waves
     const int ns = attn_nsplit(a);
     if (ns > 1)                                                        // split launch: 4-wave blocks, ns key chunks;
         return 4 + 100 * ns + ((a->f16x3 && !a->fp32_mfma && !a->O2 && !a->K2) ? 2000 : 0);      // 2000 +: on the fp16-parts kernel
-    return (wide && a->nq >= 512 && (long long)a->nbatch * a->nheads * ((a->nq + 255) / 256) >= 1024) ? 8 : 4;
-}
-
-// Tail round of a pipelined launch (see the header): samples of a last round of 256-query blocks that would fill at most half of the
-// 512 block slots (two blocks per CU).  Their attention runs key-split on attn_parts_kernel<4, 2, ., true> + attn_combine_kernel.
-#ifndef PD_ATTN_TAIL
-#define PD_ATTN_TAIL 0      // measured: no gain (round 5, NOTES.md: a quarter-full last round costs ~0.15 of a round, not one) - lab knob
-#endif
-static int attn_tail(const pd_attn_args* a, int* nsplit) {
-    if (!PD_ATTN_TAIL || !a->ws || a->nq <= 128) return 0;
-    if (a->group_samples > 0 || a->nk_group) return 0;           // (its sub-launch renumbers the samples: grouped launches stay whole)
-    const int bps = a->nheads * ((a->nq + 255) / 256);            // blocks per sample
-    if (bps > 256 || 512 % bps) return 0;
-    const int per = 512 / bps;                                    // samples per full round
-    const int bt = a->nbatch % per;
-    if (a->nbatch < per || bt == 0 || bt * bps > 256) return 0;
-    const int nit = (a->nk + KT - 1) / KT;
-    int s = 512 / (bt * bps);
-    s = s < 4 ? s : 4;
-    s = s < nit / 4 ? s : nit / 4;
-    while (s > 1 && a->ws_bytes < 4ll * s * bt * a->nq * a->nheads * 34) --s;
-    if (s < 2) return 0;
-    *nsplit = s;
-    return bt;
-}
-
-PD_EXPORT int pd_attention_tail(const pd_attn_args* a, int* nsplit) {
-    int ns = 0;
-    if (!a || pd_attention_variant(a) < 3000) return 0;
-    const int bt = attn_tail(a, &ns);
-    if (nsplit) *nsplit = bt ? ns : 0;
-    return bt;
+    return (a->nq >= 512 && (long long)a->nbatch * a->nheads * ((a->nq + 255) / 256) >= 1024) ? 8 : 4;
 }
 
 PD_EXPORT int pd_attention(const pd_attn_args* a, void* stream) {
@@ -378,36 +334,7 @@ PD_EXPORT int pd_attention(const pd_attn_args* a, void* stream) {
         hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s);
         return pd_check_launch();
     }
-    if (variant >= 3000) {
-        int ns = 0;
-        const int bt = attn_tail(a, &ns);
-        if (bt == 0) return pd_attention_pipe_try(a, stream, 0);
-        if (((uintptr_t)a->ws & 15) != 0) return PD_ERR_UNSUPPORTED;
-        // full rounds on the pipelined kernel, the samples of the last one key-split: same buffers, disjoint sample ranges
-        const int n1 = a->nbatch - bt;
-        const long long C = (long long)a->nheads * 32, rows = (long long)a->nbatch * a->nq;
-        pd_attn_args m = *a;
-        m.nbatch = n1;
-        m.o2_rows = a->O2 ? rows : 0;
-        int r = pd_attention_pipe_try(&m, stream, 0);
-        if (r != PD_OK) return r;
-        pd_attn_args t = *a;
-        t.nbatch = bt; t.nsplit = ns; t.o2_rows = a->O2 ? rows : 0;
-        t.Q = a->Q + n1 * a->q_bs;
-        if (a->K) t.K = a->K + n1 * a->k_bs;
-        if (a->V) t.V = a->V + n1 * a->v_bs;
-        if (a->O) t.O = a->O + n1 * a->o_bs;
-        if (a->O2) t.O2 = reinterpret_cast<unsigned short*>(a->O2) + n1 * a->nq * C;
-        if (a->K2) {
-            t.K2 = reinterpret_cast<const unsigned short*>(a->K2) + n1 * a->kv2_bs;
-            t.V2 = reinterpret_cast<const unsigned short*>(a->V2) + n1 * a->kv2_bs;
-        }
-        r = pd_attention_f16_split(&t, stream, 0);
-        if (r != PD_OK) return r;
-        const long long total = (long long)bt * a->nq * a->nheads * 8;
-        hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t);
-        return pd_check_launch();
-    }
+    if (variant >= 3000) return pd_attention_pipe_try(a, stream, 0);
     if (variant >= 1000) return pd_attention_split_try(a, stream, 0);
     if (variant > 100) {
         if (((uintptr_t)a->ws & 15) != 0) return PD_ERR_UNSUPPORTED;

@@ -178,13 +178,8 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
                 k0[0] = kb[0]; k1[0] = kb[1]; k0[NP - 1] = kb[2]; k1[NP - 1] = kb[3];
                 v0[0] = vb[0]; v1[0] = vb[1]; v0[NP - 1] = vb[2]; v1[NP - 1] = vb[3];
             } else if constexpr (NP == 2) {
-#if defined(PD_ATTN_ABL) && PD_ATTN_ABL == 1      // lab ablation (wrong results): K / V staged without scale + split VALU work
-                k0[0] = __float_as_uint(rk[i][0]); k0[1] = __float_as_uint(rk[i][1]); k1[0] = __float_as_uint(rk[i][2]); k1[1] = __float_as_uint(rk[i][3]);
-                v0[0] = __float_as_uint(rv[i][0]); v0[1] = __float_as_uint(rv[i][1]); v1[0] = __float_as_uint(rv[i][2]); v1[1] = __float_as_uint(rv[i][3]);
-#else
                 PT::split(rk[i][0] * sk, rk[i][1] * sk, k0); PT::split(rk[i][2] * sk, rk[i][3] * sk, k1);
                 PT::split(rv[i][0] * sv, rv[i][1] * sv, v0); PT::split(rv[i][2] * sv, rv[i][3] * sv, v1);
-#endif
             } else {
                 PT::split(rk[i][0], rk[i][1], k0); PT::split(rk[i][2], rk[i][3], k1);
                 PT::split(rv[i][0], rv[i][1], v0); PT::split(rv[i][2], rv[i][3], v1);
@@ -234,8 +229,8 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
         if constexpr (NP == 2) {                           // undo the operand scales (exact), then the bias
             if (bias_wave) {
                 if constexpr (SPLIT) {
-                    // the key-split form also serves the tail round of a pipelined launch (pd_attention_tail), whose bias tiles were
-                    // produced times the product of the q and k operand scales: times c_s that is the plain bias again, exactly
+                    // bias tiles produced for the pipelined kernel (pd_attn_args.bias_prescale > 0) arrive times the product of the q and
+                    // k operand scales: times c_s that is the plain bias again, exactly
                     if (p.bias_prescale > 0.f) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) bf[g] *= c_s;
@@ -260,30 +255,14 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
 #pragma unroll
         for (int r = 1; r < 16; ++r) mloc = fmaxf(mloc, s[r]);
         mloc = pd_xhalf_max(mloc);
-#if defined(PD_ATTN_LAZY)      // lab experiment: the reference maximum moves only when some row's maximum exceeds it by more than
-        // PD_ATTN_LAZY (log2 units); p is carried times 2^12 so that 2^PD_ATTN_LAZY of head room exists below the fp16 maximum
-        float alpha = 1.0f;
-        if (__builtin_amdgcn_ballot_w64(mloc > m_run + (float)PD_ATTN_LAZY) != 0ull) {
-            const float m_new = fmaxf(m_run, mloc);
-            alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-            m_run = m_new;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[r] *= alpha;
-        }
-        const float m_new = m_run;
-        const float m_exp = NP == 2 ? m_new - 12.0f : m_new;
-#else
         const float m_new = fmaxf(m_run, mloc);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
 #pragma unroll
-#if !(defined(PD_ATTN_ABL) && PD_ATTN_ABL == 2)   // lab ablation 2 (wrong results): no rescale of the accumulator
         for (int r = 0; r < 16; ++r) o[r] *= alpha;      // (a wave-uniform "no maximum moved" skip measured -20 %: it splits the schedule)
-#endif
         // fp16 parts: p is carried times 2^14 (inside the exponent), so that its low part stays a normal fp16 number down
         // to p = 2^-16; the sum l carries the same factor and it cancels in o / l
         const float m_exp = NP == 2 ? m_new - 14.0f : m_new;
-#endif
         float psum = 0.f;
         const unsigned short* vbase = sV + l31 * VP + sub * 32 + 8 * hh;
         // one k-step (8 of the lane's 16 keys) at a time: exp, split, the MFMAs - the probabilities of the second half are
@@ -398,7 +377,7 @@ void launch(const pd_attn_args* a, hipStream_t stream) {
 // to a->ws; the caller runs attn_combine_kernel afterwards.  init_only: 1 raise the dynamic-LDS limit.
 extern "C" int pd_attention_f16_split(const pd_attn_args* a, void* stream, int init_only) {
     auto k = attn_parts_kernel<4, 2, false, true>;
-    auto kpre = attn_parts_kernel<4, 2, true, true>;          // K / V pre-split by the projection (the tail round of a DiT launch)
+    auto kpre = attn_parts_kernel<4, 2, true, true>;          // K / V pre-split by the projection
     if (init_only == 1)
         return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<2>()) == hipSuccess &&
                        hipFuncSetAttribute(reinterpret_cast<const void*>(kpre), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<2>()) == hipSuccess

@@ -45,38 +45,14 @@ __device__ unsigned long long* g_pipe_trace = nullptr;
 #define PD_PSTAMP(slot) do { } while (0)
 #endif
 
-// lab ablations (timing only, wrong results): 1 no block barrier in the main loop, 2 exp2 -> identity, 4 no MFMAs in the phases,
-// 8 no softmax VALU in the phases, 16 static s_setprio 1 for the second half of the block's waves, 32 no bias fetch in the
-// phases, 64 no K / V staging in the main loop
-#ifdef PD_PIPE_ABL
-constexpr int ABL = PD_PIPE_ABL;
-#else
-constexpr int ABL = 0;
-#endif
-
-// Lazy running maximum: the reference maximum of a row moves only when some row of the wave exceeds it by more than PD_PIPE_LAZY
+// Lazy running maximum: the reference maximum of a row moves only when some row of the wave exceeds it by more than LAZY
 // (log2 units) - a wave-uniform, rarely taken branch holds the exp2 of the correction and the 17 multiplications of the
-// accumulator / row-sum rescale; probabilities may then reach 2^PD_PIPE_LAZY, so they are carried times 2^(14 - PD_PIPE_LAZY).
+// accumulator / row-sum rescale; probabilities may then reach 2^LAZY, so they are carried times 2^(14 - LAZY).
 // 0: the plain update (maximum, correction factor and rescale in every sub-tile).
-#ifndef PD_PIPE_LAZY
-#define PD_PIPE_LAZY 3
-#endif
-constexpr int LAZY = PD_PIPE_LAZY;
-#ifndef PD_PIPE_XCD
-#define PD_PIPE_XCD 0
-#endif
-constexpr bool XCDMAP = PD_PIPE_XCD != 0;
+constexpr int LAZY = 3;
 constexpr float PSH = 14.0f - (float)LAZY;
 
 __device__ __forceinline__ f32x16 mma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-// MFMA of a pipelined phase (ablation 4 removes it)
-__device__ __forceinline__ f32x16 pmma(frag a, frag b, f32x16 c) {
-    if constexpr (ABL & 4) {
-        c[0] += __builtin_bit_cast(f32x4, a)[0] * 0.f + __builtin_bit_cast(f32x4, b)[0] * 0.f;      // keep the operands alive
-        return c;
-    }
-    return mma(a, b, c);
-}
 
 // position of key k (0..31 inside a sub-tile) in a V^T row (attn_f16.hip)
 __device__ __forceinline__ int vpos(int k) {
@@ -93,34 +69,14 @@ __device__ __forceinline__ void lds_barrier() {
 
 __device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
-// PRE: K and V arrive already scaled and split (pd_attn_args.K2 / V2); HASBIAS: bias fragments multiplied by bias_prescale;
-// RES (round 6): ALL key tiles of the block resident - launches with at most RES_TILES x 64 keys (token DiT attention, MSA row / pair-biased
-// attention of the trunk: 256 keys) request every K / V tile in the prologue, stage them into four LDS tiles (78 KB: still two blocks per
-// CU) and pass ONE block barrier; the main loop then has no staging, no requests but the bias tiles, and no barrier.  A four-tile block
-// of the streaming form spends two thirds of its life outside the pipelined phases (profiles/r05_attn_pipe_block_life_token_shape.txt).
-// Built, correct, and no faster (see PD_PIPE_RES below): kept as a lab form.
-constexpr int RES_TILES = 4;
-template <int NW, bool PRE, bool HASBIAS, bool RES = false>
+// PRE: K and V arrive already scaled and split (pd_attn_args.K2 / V2); HASBIAS: bias fragments multiplied by bias_prescale
+template <int NW, bool PRE, bool HASBIAS>
 __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW == 8 ? 4 : 2, 4))) void attn_pipe_kernel(const pd_attn_args p_) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, hh = lane >> 5;
-    int b = blockIdx.x, h = blockIdx.z, qb = blockIdx.y;
-    if constexpr (XCDMAP) {
-        // Workgroups go to the eight XCDs round-robin in dispatch order (x fastest).  With the plain (sample, query block, head)
-        // grid XCD k gets the samples b = k mod 8 of EVERY (head, query block): each of the eight L2s fetches the whole bias.
-        // Here an XCD owns P / 8 (head, query block) pairs - for the atom shape four query blocks of one head - for all samples:
-        // it fetches 1 / 8 of the bias per round of co-resident samples, and a (sample, head) K / V pair goes to two L2s.
-        const int nqb = gridDim.y, P = nqb * gridDim.z;
-        if ((P & 7) == 0) {
-            const int L = blockIdx.x + gridDim.x * (blockIdx.y + nqb * blockIdx.z);
-            const int ppx = P >> 3, slot = L >> 3;
-            const int pair = (L & 7) * ppx + slot % ppx;
-            b = slot / ppx; h = pair / nqb; qb = pair % nqb;
-        }
-    }
-    // (after the XCD remapping: the group follows the sample the block really works on)
+    const int b = blockIdx.x, h = blockIdx.z, qb = blockIdx.y;
     const pd_attn_args p = pd_attn_group(p_, b);           // grouped launches (ABI 10): this block's bias set and key count
     const int q0 = qb * (32 * NW) + wave * 32;
     const int query = q0 + l31;
@@ -179,6 +135,8 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
         voff_g[i] = (int)((srow + RPP * i) * vss) + 16 * sc;
     }
     const int ktile_b = (int)(KT * kss), vtile_b = (int)(KT * vss);      // bytes per 64-key tile
+    // (the registers travel as parameters, not captures, and gload / sstore below only forward them: without the indirection hipcc orders
+    // two v_mov_b64 of the four-wave pre-split kernels differently - NOTES.md "Retired lab knobs")
     auto gload_to = [&](f32x4 (&rk)[NST], f32x4 (&rv)[NST], int tile) {
 #pragma unroll
         for (int i = 0; i < NST; ++i) {
@@ -260,16 +218,10 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
     // p = 2^14 exp2(s - m) of four elements, in place; the factor 2^14 keeps the low fp16 part normal down to p = 2^-16
     auto fe4 = [&](f32x16& s, int r0, float mneg) {
 #pragma unroll
-        for (int r = r0; r < r0 + 4; ++r) s[r] = (ABL & 2) ? __builtin_fmaf(s[r], c_s, mneg) : __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c_s, mneg));
+        for (int r = r0; r < r0 + 4; ++r) s[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c_s, mneg));
     };
     auto split8 = [&](const f32x16& s, int r0, frag (&pf)[2]) {       // eight probabilities -> (hi, lo) B fragments of one k-step
         u32x4 fh, fl;
-        if constexpr (ABL & 8) {
-#pragma unroll
-            for (int e2 = 0; e2 < 4; ++e2) { fh[e2] = __float_as_uint(s[r0 + 2 * e2]); fl[e2] = __float_as_uint(s[r0 + 2 * e2 + 1]); }
-            pf[0] = __builtin_bit_cast(frag, fh); pf[1] = __builtin_bit_cast(frag, fl);
-            return;
-        }
 #pragma unroll
         for (int e2 = 0; e2 < 4; ++e2) {
             const pd_parts2 t = pd_split2h(s[r0 + 2 * e2], s[r0 + 2 * e2 + 1]);
@@ -286,7 +238,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
     auto phase = [&](f32x16& cur, f32x16& nxt, float& mloc, frag (&kf0)[2], int kn, int vc, int kn2, int bt) {
         frag kf1[2], vf0[2], vf1[2], pf0[2], pf1[2];
         // slot 1
-        nxt = pmma(kf0[0], qf[0][1], first(nxt));                       // k_hi . q_lo (C = the bias tile, or zero)
+        nxt = mma(kf0[0], qf[0][1], first(nxt));                       // k_hi . q_lo (C = the bias tile, or zero)
         PD_SB();
         kf1[0] = kfrag(kn, 1, 0); kf1[1] = kfrag(kn, 1, 1);
         float alpha = 1.0f;
@@ -307,70 +259,71 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
             mneg_run = __builtin_fmaf(-m_new, c_s, PSH);
         }
         const float mneg = mneg_run;
-        if constexpr (!(ABL & 8)) fe4(cur, 0, mneg);
+        fe4(cur, 0, mneg);
         PD_SB();
         // slot 2
-        nxt = pmma(kf0[1], qf[0][0], nxt);                              // k_lo . q_hi
+        nxt = mma(kf0[1], qf[0][0], nxt);                              // k_lo . q_hi
         PD_SB();
-        if constexpr (!(ABL & 8)) fe4(cur, 4, mneg);
+        fe4(cur, 4, mneg);
         float ps0 = (cur[0] + cur[1]) + (cur[2] + cur[3]);
         PD_SB();
         // slot 3
-        nxt = pmma(kf0[0], qf[0][0], nxt);                              // k_hi . q_hi
+        nxt = mma(kf0[0], qf[0][0], nxt);                              // k_hi . q_hi
         PD_SB();
         vf0[0] = vfrag(vc, 0, 0); vf0[1] = vfrag(vc, 0, 1);
         split8(cur, 0, pf0);
         PD_SB();
         // slot 4
-        nxt = pmma(kf1[0], qf[1][1], nxt);
+        nxt = mma(kf1[0], qf[1][1], nxt);
         PD_SB();
-        if constexpr (!(ABL & 8)) { fe4(cur, 8, mneg); fe4(cur, 12, mneg); }
+        fe4(cur, 8, mneg); fe4(cur, 12, mneg);
         PD_SB();
         // slot 5
-        nxt = pmma(kf1[1], qf[1][0], nxt);
+        nxt = mma(kf1[1], qf[1][0], nxt);
         PD_SB();
+        // (with LAZY > 0 this loop and the one in slot 6 are empty, and still pin where hipcc places the row sums: NOTES.md "Retired lab knobs")
 #pragma unroll
-        for (int r = 0; r < 8; ++r) if constexpr (!(ABL & 8) && LAZY == 0) o[r] *= alpha;
+        for (int r = 0; r < 8; ++r) if constexpr (LAZY == 0) o[r] *= alpha;
         float ps1 = (cur[4] + cur[5]) + (cur[6] + cur[7]);
         ps0 += (cur[8] + cur[9]) + (cur[10] + cur[11]);
         PD_SB();
         // slot 6
-        nxt = pmma(kf1[0], qf[1][0], nxt);
+        nxt = mma(kf1[0], qf[1][0], nxt);
         PD_SB();
 #pragma unroll
-        for (int r = 8; r < 16; ++r) if constexpr (!(ABL & 8) && LAZY == 0) o[r] *= alpha;
+        for (int r = 8; r < 16; ++r) if constexpr (LAZY == 0) o[r] *= alpha;
         ps1 += (cur[12] + cur[13]) + (cur[14] + cur[15]);
         PD_SB();
         // slot 7: the last use of `cur` - the bias tile of sub-tile j+2 is fetched into it right behind
-        o = pmma(vf0[0], pf0[1], o);                                    // v_hi . p_lo
+        o = mma(vf0[0], pf0[1], o);                                    // v_hi . p_lo
         PD_SB();
         vf1[0] = vfrag(vc, 1, 0); vf1[1] = vfrag(vc, 1, 1);
         split8(cur, 8, pf1);
         PD_SB();
-        if constexpr (!(ABL & 32)) load_bias(cur, bt);
+        load_bias(cur, bt);
         PD_SB();
         // slot 8
-        o = pmma(vf0[1], pf0[0], o);                                    // v_lo . p_hi
+        o = mma(vf0[1], pf0[0], o);                                    // v_lo . p_hi
         PD_SB();
         if constexpr (LAZY > 0) l_run += ps0 + ps1; else l_run = __builtin_fmaf(l_run, alpha, ps0 + ps1);
         PD_SB();
         // slot 9: K fragments of sub-tile j+2's first k-step
-        o = pmma(vf0[0], pf0[0], o);                                    // v_hi . p_hi
+        o = mma(vf0[0], pf0[0], o);                                    // v_hi . p_hi
         PD_SB();
         kf0[0] = kfrag(kn2, 0, 0); kf0[1] = kfrag(kn2, 0, 1);
         PD_SB();
         // slots 10 - 12: row maximum of the NEXT sub-tile's scores under the last three P.V MFMAs
-        o = pmma(vf1[0], pf1[1], o);
+        o = mma(vf1[0], pf1[1], o);
         PD_SB();
         float m0 = max3(nxt[0], nxt[1], nxt[2]);
         m0 = max3(m0, nxt[3], nxt[4]); m0 = max3(m0, nxt[5], nxt[6]); m0 = max3(m0, nxt[7], nxt[8]);
         PD_SB();
-        o = pmma(vf1[1], pf1[0], o);
+        o = mma(vf1[1], pf1[0], o);
         PD_SB();
         m0 = max3(m0, nxt[9], nxt[10]); m0 = max3(m0, nxt[11], nxt[12]); m0 = max3(m0, nxt[13], nxt[14]);
         m0 = __builtin_fmaxf(m0, nxt[15]);
         PD_SB();
-        o = pmma(vf1[0], pf1[0], o);
+        o = mma(vf1[0], pf1[0], o);
         PD_SB();
         mloc = pd_xhalf_max(m0);
         PD_SB();
@@ -420,12 +373,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
 
     // ---- prologue: every independent request first (K / V tile 0, bias tiles 0 / 1 into the two score accumulators, the lane's
     // query row) - their latencies overlap instead of adding up, which is most of a short launch (256 keys: 4 tiles per block)
-    f32x4 rkr[RES ? RES_TILES - 1 : 1][NST], rvr[RES ? RES_TILES - 1 : 1][NST];      // RES: tiles 1 .. 3 (tile 0 in rk / rv)
     gload(0);
-    if constexpr (RES) {
-#pragma unroll
-        for (int t = 1; t < RES_TILES; ++t) gload_to(rkr[t - 1], rvr[t - 1], t);      // (tiles beyond the last key read as zero)
-    }
     load_bias(sA, 0);
     load_bias(sB, 1);
     f32x4 qraw[2][2];
@@ -457,12 +405,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
     PD_PSTAMP(2);                                          // Q arrived and split
     sstore(0);
     PD_PSTAMP(3);                                          // K / V tile 0 arrived and staged
-    if constexpr (RES) {
-#pragma unroll
-        for (int t = 1; t < RES_TILES; ++t) sstore_from(rkr[t - 1], rvr[t - 1], t * STAGE);
-    } else {
-        gload(1);
-    }
+    gload(1);
     lds_barrier();
     PD_PSTAMP(4);                                          // first barrier passed
     int s_cur = 0, s_nxt = STAGE, s_nn = 2 * STAGE;
@@ -475,26 +418,22 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
     }
 
     PD_PSTAMP(5);                                          // first score tile + row maximum
-    if constexpr (ABL & 16) { if (wave >= NW / 2) __builtin_amdgcn_s_setprio(1); }
     if (wave_active) {
         for (int it = 0; it < nit - 1; ++it) {
-            if constexpr (!RES) {
-                if constexpr (!(ABL & 64)) sstore(s_nxt);      // tile it + 1 (requested one iteration ago)
-                if constexpr (!(ABL & 1)) lds_barrier();
-                if constexpr (!(ABL & 64)) gload(it + 2);      // tile it + 2 (rows beyond the last key read as zero)
-            }
+            sstore(s_nxt);                                 // tile it + 1 (requested one iteration ago)
+            lds_barrier();
+            gload(it + 2);                                 // tile it + 2 (rows beyond the last key read as zero)
             PD_SB();
             // sub-tile 2 it (cur = sA): next scores = sub-tile 2 it + 1 (same tile, second half)
             phase(sA, sB, mloc, kf0, s_cur + 32 * KP, s_cur, s_nxt, 2 * it + 2);
             // sub-tile 2 it + 1 (cur = sB): next scores = first half of tile it + 1
             phase(sB, sA, mloc, kf0, s_nxt, s_cur + 32, s_nxt + 32 * KP, 2 * it + 3);
-            if constexpr (RES) { s_cur = s_nxt; s_nxt += STAGE; }          // resident tiles sit at it x STAGE
-            else { const int t = s_cur; s_cur = s_nxt; s_nxt = s_nn; s_nn = t; }
+            const int t = s_cur; s_cur = s_nxt; s_nxt = s_nn; s_nn = t;
 #ifdef PD_LAB
             if (it < 6) PD_PSTAMP(6 + it);                 // end of main-loop iteration it
 #endif
         }
-    } else if constexpr (!RES) {                           // a wave without queries (ragged last block) only stages
+    } else {                                               // a wave without queries (ragged last block) only stages
         for (int it = 0; it < nit - 1; ++it) {
             sstore(s_nxt);
             lds_barrier();
@@ -548,38 +487,16 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(NW =
 }
 
 constexpr int LDS_BYTES = NSTAGE * STAGE * 2;
-constexpr int LDS_BYTES_RES = RES_TILES * STAGE * 2;
 
 template <int NW, bool PRE, bool HASBIAS>
 bool raise_lds() {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(attn_pipe_kernel<NW, PRE, HASBIAS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               LDS_BYTES) == hipSuccess &&
-           (NW != 8 || hipFuncSetAttribute(reinterpret_cast<const void*>(attn_pipe_kernel<8, PRE, HASBIAS, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_RES) == hipSuccess);
+                               LDS_BYTES) == hipSuccess;
 }
 
-// lab: 1 = launches of at most 256 keys take the resident form.  Measured and OFF (profiles/r06_ab_pipe_resident.txt): token DiT attention
-// 44.4 vs 44.5 us, triangle shape 42.4 vs 43.9 us, 64-sample call 402.4 / 401.9 vs 401.7 / 402.7 ms - the per-tile barrier and staging
-// are not what a four-tile launch waits for
-#ifndef PD_PIPE_RES
-#define PD_PIPE_RES 0
-#endif
-
-// Short key ranges (<= PD_PIPE_NW4_MAXNK keys: token / triangle / MSA attention at 256 - 512 tokens) run on FOUR-wave blocks of 128
-// queries: a block lives for only four to eight key tiles, most of it prologue and tail, and twice as many independent blocks per CU
-// (four resident instead of two) fill each other's gaps; the K / V tiles are staged by both query blocks of a (sample, head).
-#ifndef PD_PIPE_NW4_MAXNK
-#define PD_PIPE_NW4_MAXNK 0
-#endif
 template <bool PRE, bool HASBIAS>
 void launch(const pd_attn_args* a, hipStream_t stream) {
-    if (a->nq > 128 && a->nk <= PD_PIPE_NW4_MAXNK) {
-        dim3 grid(a->nbatch, (a->nq + 127) / 128, a->nheads);
-        hipLaunchKernelGGL((attn_pipe_kernel<4, PRE, HASBIAS>), grid, dim3(256), LDS_BYTES, stream, *a);
-    } else if (a->nq > 128 && PD_PIPE_RES && a->nk <= RES_TILES * KT && a->nk > KT) {
-        dim3 grid(a->nbatch, (a->nq + 255) / 256, a->nheads);       // every key tile resident: one barrier, no staging in the loop
-        hipLaunchKernelGGL((attn_pipe_kernel<8, PRE, HASBIAS, true>), grid, dim3(512), LDS_BYTES_RES, stream, *a);
-    } else if (a->nq > 128) {
+    if (a->nq > 128) {
         dim3 grid(a->nbatch, (a->nq + 255) / 256, a->nheads);
         hipLaunchKernelGGL((attn_pipe_kernel<8, PRE, HASBIAS>), grid, dim3(512), LDS_BYTES, stream, *a);
     } else {

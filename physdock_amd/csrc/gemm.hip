@@ -28,17 +28,14 @@
 
 namespace {
 
-#ifndef PD_BK
-#define PD_BK 32
-#endif
-constexpr int BK = PD_BK;     // k-slice depth (32 or 16)
+constexpr int BK = 32;        // k-slice depth (32 or 16)
 constexpr int LDK = BK + 4;   // padded row (floats): 144 B / 80 B, keeps ds_read_b128 conflict-free
 constexpr int CH = BK / 4;    // 16-byte chunks per staged row
 constexpr int RPP = 256 / CH; // rows staged per pass of the 256 threads
 constexpr int NT = 256;
 constexpr int PADM = 4;
 
-#ifdef PD_LAB      // lab build only (tools/gemm_trace.py): in-kernel phase trace buffer + host-side tuning overrides
+#ifdef PD_LAB      // lab build only (tools/gemm_trace.py): in-kernel phase trace buffer
 __device__ unsigned long long* g_gemm_trace = nullptr;
 bool g_gemm_trace_on = false;
 #define PD_TRACE_PTR g_gemm_trace
@@ -608,12 +605,6 @@ static int select_variant(pd_gemm_args& p, int& cfg, bool& akm, bool& wkm, bool&
     else if (p.N <= 64) cfg = 1;
     else cfg = 0;
     if (pro == 2 && cfg != 0 && cfg != 3) cfg = 0;
-#ifdef PD_LAB
-    if (const char* f = getenv("PD_GEMM_CFG")) {      // tuning override: force a tile configuration where legal
-        const int c = atoi(f);
-        if (c >= 0 && c <= 3 && !akm && !wkm && !p.glu && vec && pro != 2) cfg = c;
-    }
-#endif
     return cfg * 100 + (akm ? (wkm ? 2 : 1) : 0) * 10 + pro + (vec ? 0 : 1000);
 }
 
@@ -649,8 +640,7 @@ static int stream_tile(int cfg, const pd_gemm_args& p) {
 
 static bool use_stream() {
 #ifdef PD_LAB
-    static const int on = [] { const char* e = getenv("PD_GEMM_STREAM"); return e ? atoi(e) : 1; }();
-    return on != 0 && !g_gemm_trace_on;          // the phase trace lives in the general kernel
+    return !g_gemm_trace_on;                     // the phase trace lives in the general kernel
 #else
     return true;
 #endif

@@ -28,42 +28,25 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef PD_F16_MIN_TILES
-#define PD_F16_MIN_TILES 256
-#endif
-#ifndef PD_F16_MIN_TILES_SMALL
-#define PD_F16_MIN_TILES_SMALL 160
-#endif
-#ifndef PD_F16_MIN_TILES_SMALL_LONGK
-#define PD_F16_MIN_TILES_SMALL_LONGK 96
-#endif
-// lab ablations of the direct-W main loop (timing only, wrong results): 1 every block stages the A rows of tile 0 (L2-hot operand),
-// 2 every wave loads the W fragments of column block 0 / k-step 0, 4 no block barrier inside the slice loop, 8 no A requests in the loop,
-// 16 the A fragments are read from LDS once per tile instead of once per k-step (no LDS reads in the loop), 32 no LDS staging stores,
-// 64 no W fragment requests in the loop
-#ifdef PD_F16_ABL
-constexpr int F16_ABL = PD_F16_ABL;
-#else
-constexpr int F16_ABL = 0;
-#endif
+constexpr int F16_MIN_TILES = 256, F16_MIN_TILES_SMALL = 160, F16_MIN_TILES_SMALL_LONGK = 96;
 #ifdef PD_LAB      // lab build only (tools/gemm_f16_trace.py): in-kernel phase trace of the direct-W main loop
 __device__ unsigned long long* g_f16_trace = nullptr;
-#define PD_F16_TRACE_PTR g_f16_trace
+#define PD_TRACE_F16_PTR g_f16_trace
 #else
-#define PD_F16_TRACE_PTR ((unsigned long long*)nullptr)
+#define PD_TRACE_F16_PTR ((unsigned long long*)nullptr)
 #endif
 constexpr int NPARTS = 2;            // operand parts: (hi, lo) fp16
 constexpr int PITCH = 24;            // LDS-W tiles: 16 k per row, 48 bytes apart
 constexpr int PITCH2 = 40;           // DW tiles: 32 k per row, 80 bytes apart (conflict-free ds_read_b128 fragments)
 
-template <int BM_, int BN_, int WM_, int NWAVES_, bool DW_, int BPC_ = 0>
+template <int BM_, int BN_, int WM_, int NWAVES_, bool DW_>
 struct FTile {
     static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = NWAVES_ / WM_, NT = 64 * NWAVES_;
     static constexpr int TM = BM / (32 * WM), TN = BN / (32 * WN);
     static constexpr bool DW = DW_;      // direct W: the B fragments go from global memory straight into MFMA registers
     static constexpr int STAGE = DW ? NPARTS * BM * PITCH2 : NPARTS * (BM + BN) * PITCH;      // fp16 elements per stage
     static constexpr int LDS_BYTES = 2 * STAGE * 2;
-    static constexpr int BLOCKS_PER_CU = BPC_ ? BPC_ : (NWAVES_ == 8 ? 2 : 4);
+    static constexpr int BLOCKS_PER_CU = NWAVES_ == 8 ? 2 : 4;
     static constexpr int WAVES_PER_SIMD = NWAVES_ * BLOCKS_PER_CU / 4;
     static constexpr int GRID = 256 * BLOCKS_PER_CU;
 };
@@ -127,7 +110,6 @@ void gemm_f16_kernel(const pd_gemm_args p) {
     f16x8 rw[NPARTS][NW];
 
     auto gload = [&](int bm0, int bn0, int k0) {
-        if constexpr (F16_ABL & 1) bm0 = 0;
         const int r = bm0 + a_row;                // full tiles only: always < M
         if constexpr (AS) {
             const _Float16* ap2 = A2 + (long long)r * (nk * 32) + k0 + 8 * a_q;
@@ -156,8 +138,6 @@ void gemm_f16_kernel(const pd_gemm_args p) {
     // DW: this wave's B fragments of 16-k step `ks` of column block bn0, straight into MFMA operand registers
     f16x8 wf[2][TN][NPARTS];
     auto wfrag = [&](int buf, int bn0, int ks) {
-        if constexpr (F16_ABL & 2) { bn0 = 0; ks = 0; }
-        if constexpr (F16_ABL & 64) { if (ks > 1) return; }      // no B requests inside the slice loop
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const f16x8* base = W2 + ((long long)((bn0 + wn * (32 * TN) + j * 32) >> 5) * nks + ks) * 64 + lane;
@@ -279,7 +259,6 @@ void gemm_f16_kernel(const pd_gemm_args p) {
         };
         // ---- DW tiles: the whole 32-k slice in ra goes to LDS stage s; fragments of k-step ks come from there and from wf[ks]
         auto stage2 = [&](int s, int k0) {
-            if constexpr (F16_ABL & 32) { if (k0 > 0) return; }
             _Float16* base = lds + s * TL::STAGE + a_row * PITCH2;
             if constexpr (AS) {
 #pragma unroll
@@ -299,32 +278,14 @@ void gemm_f16_kernel(const pd_gemm_args p) {
                     *reinterpret_cast<f16x4*>(base + BM * PITCH2 + o) = pl;
                 }
         };
-        f16x8 fa_abl[TM][NPARTS];
-        bool fa_abl_have = false;
         auto mma2 = [&](int s, int ks) {
             f16x8 fa[TM][NPARTS];
             const _Float16* base = lds + s * TL::STAGE + (wm * (32 * TM) + l31) * PITCH2 + 16 * ks + 8 * hh;
-            if (!(F16_ABL & 16) || !fa_abl_have) {
 #pragma unroll
-                for (int part = 0; part < NPARTS; ++part)
+            for (int part = 0; part < NPARTS; ++part)
 #pragma unroll
-                    for (int i = 0; i < TM; ++i)
-                        fa[i][part] = *reinterpret_cast<const f16x8*>(base + part * BM * PITCH2 + i * 32 * PITCH2);
-            }
-            if constexpr (F16_ABL & 16) {
-                if (!fa_abl_have) {
-#pragma unroll
-                    for (int part = 0; part < NPARTS; ++part)
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) fa_abl[i][part] = fa[i][part];
-                    fa_abl_have = true;
-                } else {
-#pragma unroll
-                    for (int part = 0; part < NPARTS; ++part)
-#pragma unroll
-                        for (int i = 0; i < TM; ++i) fa[i][part] = fa_abl[i][part];
-                }
-            }
+                for (int i = 0; i < TM; ++i)
+                    fa[i][part] = *reinterpret_cast<const f16x8*>(base + part * BM * PITCH2 + i * 32 * PITCH2);
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -347,8 +308,8 @@ void gemm_f16_kernel(const pd_gemm_args p) {
         lds_barrier();                            // every wave has finished the previous tile's last stage
         if constexpr (DW) {
             unsigned long long* dbg = nullptr;
-            if (PD_F16_TRACE_PTR && lane == 0 && blockIdx.x < 64 && tile < t_step)
-                dbg = PD_F16_TRACE_PTR + ((long long)blockIdx.x * 8 + wave) * (6 * 64);
+            if (PD_TRACE_F16_PTR && lane == 0 && blockIdx.x < 64 && tile < t_step)
+                dbg = PD_TRACE_F16_PTR + ((long long)blockIdx.x * 8 + wave) * (6 * 64);
 #define PD_STAMP(slot) if (dbg && kt < 64) dbg[kt * 6 + slot] = __builtin_amdgcn_s_memtime()
             stage2(0, 0);
             lds_barrier();
@@ -359,7 +320,7 @@ void gemm_f16_kernel(const pd_gemm_args p) {
                 constexpr bool more = decltype(more_c)::value;
                 const int st = kt & 1;
                 PD_STAMP(0);
-                if constexpr (more && !(F16_ABL & 8)) { gload(bm0, bn0, (kt + 1) * 32); __builtin_amdgcn_sched_barrier(0); }   // requests stay where they are written
+                if constexpr (more) { gload(bm0, bn0, (kt + 1) * 32); __builtin_amdgcn_sched_barrier(0); }   // requests stay where they are written
                 mma2(st, 0);
                 PD_STAMP(1);
                 // every B buffer is re-requested right after its last use
@@ -374,7 +335,7 @@ void gemm_f16_kernel(const pd_gemm_args p) {
                     // the other stage was last read in the previous iteration, which every wave left through its barrier
                     stage2(st ^ 1, (kt + 1) * 32);
                     PD_STAMP(4);
-                    if constexpr (!(F16_ABL & 4)) lds_barrier();
+                    lds_barrier();
                     PD_STAMP(5);
                 }
             };
@@ -453,11 +414,7 @@ template <int PRO, int EPI, int BM>
 __global__ __launch_bounds__(4 * BM) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void gemm_f16_rows_kernel(const pd_gemm_args p) {
     constexpr int TM = 2, TN = 1, PART = BM * RLP, NKS = 8, PF = 3, KC = 128;
-#ifdef PD_F16_ROWS_NO_XPF      // lab: the next column tile's first W fragments requested after, not before, this tile's epilogue
-    constexpr bool XPF = false;
-#else
-    constexpr bool XPF = true;
-#endif
+    constexpr bool XPF = true;       // the next column tile's first W fragments are requested before, not after, this tile's epilogue
     static_assert(NKS % (PF + 1) == 0, "the fragment ring must be back at buffer 0 when a column tile ends");
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -769,239 +726,8 @@ void gemm_f16_wrows_kernel(const pd_gemm_args p) {
 }
 
 
-// ---- wide rows, 64 x 64 wave units with a K-SPLIT TAIL (round 5): the head-norm / plain / gate-residual projections on the unit shape
-// that took the SwiGLU projection from 0.33 to 0.44 of the pipe (an A fragment pair feeds two column blocks, a W fragment pair two row
-// blocks: 12 MFMAs per 16-k step, per four ds_read_b128 and four 16-byte W requests - the 64 x 32 items issue the same requests per SIX).
-// N = 1536 is 24 such units for sixteen waves - one and a half rounds, which is why round 4 left q | k | v on 64 x 32 items.  Here every
-// wave takes full units while whole rounds of sixteen last and the remaining EIGHT units are shared by wave pairs (w, w + 8): each wave
-// contracts one K half (256) of the pair's unit, the partial tiles meet in LDS - in the A tile's space, which is dead once every wave has
-// left its main loop - and each wave of a pair finishes one 32-column half of the unit (sum of two numbers: order-free, bit-reproducible).
-// Every wave issues the same MFMA count (N = 1536: 576, N = 512: 192).  Units: N / 64 = 16 f + {0, 8}.
-template <int PRO, int EPI>
-__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
-void gemm_f16_wrows_ks_kernel(const pd_gemm_args p) {
-    constexpr int BM = 64, KC = 512, PART = BM * WLP, NKS = KC / 16, NWV = 16, RPP = 4 * NWV;
-    extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31, hh = lane >> 5;
-    const float a_s = pd_pow2_scale(*p.a_amax);
-    const float inv_a_s = 1.0f / a_s;
-    const int ntiles = p.M / BM, ncb = p.N >> 5, nunits = ncb >> 1;
-    const int nfull = (nunits >> 4) << 4;                            // units taken whole, sixteen per round
-    const bool tail = nunits > nfull;                                // eight more, one per wave pair
-    const int wpart = ncb * NKS * 1024;
-    const auto rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.W2), 0, 2 * wpart, 0x00020000);
-    const int loff = lane * 16;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int row0 = tile * BM;
-        if constexpr (PRO == 3) {
-            const int q = tid & 15;
-#pragma unroll 1
-            for (int r = tid >> 4; r < BM; r += RPP) {
-                const _Float16* a2 = reinterpret_cast<const _Float16*>(p.A2) + (long long)(row0 + r) * KC;
-                f16x8 c[NPARTS][4];
-#pragma unroll
-                for (int part = 0; part < NPARTS; ++part)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) c[part][i] = *reinterpret_cast<const f16x8*>(a2 + (long long)part * p.M * KC + 8 * (q + 16 * i));
-#pragma unroll
-                for (int part = 0; part < NPARTS; ++part)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) *reinterpret_cast<f16x8*>(lds + part * PART + r * WLP + 8 * (q + 16 * i)) = c[part][i];
-            }
-        } else {   // sixteen threads (one DPP row) per row: statistics, LayerNorm / RMSNorm, modulation, operand scale, split - once
-            const int q = tid & 15;
-#pragma unroll 1
-            for (int r = tid >> 4; r < BM; r += RPP) {
-                const int m = row0 + r;
-                const float* xr = p.A + (long long)m * p.lda;
-                const int goff = PRO == 2 ? (m / p.pro_rows_per_group) * p.pro_gstride : 0;
-                f32x4 v[8];
-                float s1 = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    v[i] = *reinterpret_cast<const f32x4*>(xr + 4 * (q + 16 * i));
-                    s1 += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-                }
-                auto row16 = [](float x) {
-                    x += pd_dpp<0xB1>(x); x += pd_dpp<0x4E>(x); x += pd_dpp<0x141>(x); x += pd_dpp<0x140>(x);
-                    return x;
-                };
-                s1 = row16(s1);
-                float mean = p.stats_inline == 2 ? s1 * (1.0f / KC) : 0.f;
-                float sq = 0.f;
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { const float d = v[i][e] - mean; sq += d * d; }
-                sq = row16(sq);
-                const float rstd = rsqrtf(sq * (1.0f / KC) + p.stats_eps) * a_s;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const int c = 4 * (q + 16 * i);
-                    const f32x4 gw = *reinterpret_cast<const f32x4*>(p.pro_w + goff + c), gb = *reinterpret_cast<const f32x4*>(p.pro_b + goff + c);
-                    float t[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) t[e] = (v[i][e] - mean) * rstd * gw[e] + gb[e] * a_s;
-                    const pd_parts2 p0 = pd_split2h(t[0], t[1]), p1 = pd_split2h(t[2], t[3]);
-                    *reinterpret_cast<u32x2*>(lds + r * WLP + c) = u32x2{p0.h, p1.h};
-                    *reinterpret_cast<u32x2*>(lds + PART + r * WLP + c) = u32x2{p0.l, p1.l};
-                }
-            }
-        }
-        lds_barrier();
-        const _Float16* abase = lds + l31 * WLP + 8 * hh;
-        f16x8 wf[2][2][NPARTS];                                          // [ring buffer][column block of the unit][part]
-        auto wload = [&](int cu, int buf, int ks) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int so = ((cu * 2 + j) * NKS + ks) * 1024;
-                wf[buf][j][0] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, loff, so, 0));
-                wf[buf][j][1] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(rs_w, loff, so + wpart, 0));
-            }
-        };
-        f32x16 acc[2][2];
-        auto zero = [&]() {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        };
-        auto kstep = [&](int buf, int ks) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const f16x8 a0 = *reinterpret_cast<const f16x8*>(abase + 32 * i * WLP + 16 * ks);
-                const f16x8 a1 = *reinterpret_cast<const f16x8*>(abase + PART + 32 * i * WLP + 16 * ks);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    f32x16 t = acc[i][j];
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, wf[buf][j][1], t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, wf[buf][j][0], t, 0, 0, 0);
-                    t = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, wf[buf][j][0], t, 0, 0, 0);
-                    acc[i][j] = t;
-                }
-            }
-        };
-        // k-steps ks0 .. ks0 + n (n even) of unit cu against the resident rows; buffer 0 holds step ks0 on entry; the last step's request
-        // is the FIRST step of the wave's next segment (ncu, nks0), if any - the ring runs on across units
-        auto contract = [&](int cu, int ks0, int n, bool more, int ncu, int nks0) {
-#pragma unroll 1
-            for (int ks = ks0; ks < ks0 + n; ks += 2) {
-                wload(cu, 1, ks + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(0, ks);
-                if (ks + 2 < ks0 + n) wload(cu, 0, ks + 2);
-                else if (more) wload(ncu, 0, nks0);
-                __builtin_amdgcn_sched_barrier(0);
-                kstep(1, ks + 1);
-            }
-        };
-        auto consts = [&](int col0, int nj, float (&c0)[2], float (&c1)[2], float (&cs)[2]) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int n0 = col0 + 32 * j + l31;
-                const bool on = j < nj;
-                c0[j] = (on && p.bias) ? p.bias[n0] : 0.f;
-                c1[j] = 1.f;
-                if constexpr (EPI == EPI_HN) c1[j] = on ? p.hn_w[(n0 / p.hn_split) * 32 + l31] : 1.f;
-                if constexpr (EPI == EPI_GATERES)
-                    c1[j] = (on && p.mul) ? p.mul[(long long)(row0 / p.mul_rows_per_group) * p.mul_gstride + n0] : 1.f;
-                cs[j] = on ? p.w_inv[n0] * inv_a_s : 0.f;
-            }
-        };
-        const int pr = wave & 7, kh = wave >> 3;                          // tail: pair and K half
-        const int tcu = nfull + pr;
-        int cu = wave;
-        if (cu < nfull) wload(cu, 0, 0);
-        else if (tail) wload(tcu, 0, kh * (NKS / 2));
-        for (; cu < nfull; cu += NWV) {
-            zero();
-            const bool more_full = cu + NWV < nfull;
-            contract(cu, 0, NKS, more_full || tail, more_full ? cu + NWV : tcu, more_full ? 0 : kh * (NKS / 2));
-            float c0[2], c1[2], cs[2];
-            consts(cu * 64, 2, c0, c1, cs);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] *= cs[j];
-            epilogue<EPI, 2, 2>(p, acc, c0, c1, row0, cu * 64, 0, 0, l31, hh);
-        }
-        if (tail) {
-            zero();
-            contract(tcu, kh * (NKS / 2), NKS / 2, false, 0, 0);
-        }
-        lds_barrier();                               // every wave has left its main loop: the A tile's space is free
-        if (tail) {
-            // the partial tile of the column block the PARTNER finishes goes to this wave's 8 KB slot: [row block][register quad][lane]
-            // (kh as a compile-time constant: a run-time index into the accumulator array would move it to scratch memory)
-            auto exchange = [&](auto khc) {
-                constexpr int KH = decltype(khc)::value;
-                float* xch = reinterpret_cast<float*>(lds) + wave * 2048;
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x16& t = acc[i][1 - KH];
-                        *reinterpret_cast<f32x4*>(xch + ((i * 4 + g) * 64 + lane) * 4) = f32x4{t[4 * g], t[4 * g + 1], t[4 * g + 2], t[4 * g + 3]};
-                    }
-                lds_barrier();
-                const float* xin = reinterpret_cast<const float*>(lds) + (wave ^ 8) * 2048;
-                float c0[2], c1[2], cs[2];
-                consts(tcu * 64 + 32 * KH, 1, c0, c1, cs);
-                f32x16 fin[2][1];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 o = *reinterpret_cast<const f32x4*>(xin + ((i * 4 + g) * 64 + lane) * 4);
-                        const f32x16& t = acc[i][KH];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) fin[i][0][4 * g + e] = (t[4 * g + e] + o[e]) * cs[0];
-                    }
-                const float d0[1] = {c0[0]}, d1[1] = {c1[0]};
-                epilogue<EPI, 2, 1>(p, fin, d0, d1, row0, tcu * 64 + 32 * KH, 0, 0, l31, hh);
-            };
-            if (kh == 0) exchange(std::integral_constant<int, 0>{}); else exchange(std::integral_constant<int, 1>{});
-            lds_barrier();                           // the slots are read: the next tile's rows may overwrite them
-        }
-    }
-}
-
-template <int PRO, int EPI>
-int run_f16_wrows_ks(int op, const pd_gemm_args* p, hipStream_t s) {
-    auto k = gemm_f16_wrows_ks_kernel<PRO, EPI>;
-    if (op == 1)
-        return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, WROWS_LDS_BYTES) == hipSuccess
-                   ? PD_OK : PD_ERR_LAUNCH;
-    const int ntiles = p->M / 64;
-    hipLaunchKernelGGL(k, dim3((unsigned)(ntiles < 256 ? ntiles : 256)), dim3(1024), WROWS_LDS_BYTES, s, *p);
-    return pd_check_launch();
-}
-
-// the K-split-tail kernel takes a launch when the row tiles fill the chip by themselves and N is 16 f + {0, 8} units of 64 columns
-#ifndef PD_F16_WROWS_KS
-#define PD_F16_WROWS_KS 0      // measured slower (round 5: q | k | v 104 -> 127 us, linear_o 35 -> 49 us, 157.9 -> 147.5 poses/s): lab knob
-#endif
-inline bool wrows_ks_shape(const pd_gemm_args* p) {
-    const int units = p->N / 64;
-    return PD_F16_WROWS_KS && p->N % 64 == 0 && (units % 16 == 0 || units % 16 == 8) && p->M / 64 >= 256;
-}
-
-// lab knobs of the column split: most blocks per row tile, fewest work items a block may be left with
-#ifndef PD_F16_WROWS_MAX_SPLIT
-#define PD_F16_WROWS_MAX_SPLIT 4
-#endif
-#ifndef PD_F16_WROWS_MIN_ITEMS
-#define PD_F16_WROWS_MIN_ITEMS 8
-#endif
-#ifndef PD_F16_WROWS_ROUNDS
-#define PD_F16_WROWS_ROUNDS 1      // lab: 0 = the round-5 split rule (256 / ntiles) for 129 - 255 row tiles
-#endif
+// the column split: most blocks per row tile, fewest work items a block may be left with
+constexpr int F16_WROWS_MAX_SPLIT = 4, F16_WROWS_MIN_ITEMS = 8;
 template <int PRO, int EPI, int TM, int TN, int GK = 4, int NWV = 16>
 int run_f16_wrows(int op, const pd_gemm_args* p, hipStream_t s) {
     auto k = gemm_f16_wrows_kernel<PRO, EPI, TM, TN, GK, NWV>;
@@ -1015,17 +741,17 @@ int run_f16_wrows(int op, const pd_gemm_args* p, hipStream_t s) {
     //  143 ms; up to 16 blocks with >= 2 items 89 / 100 / 110 / 113 / 135 / 145 ms: the deep split below 32 row tiles only)
     const bool few = ntiles < 32;
     int nsplit = (PRO != 3 && ntiles < 256) ? 256 / ntiles : 1;
-    const int max_split = few ? 4 * PD_F16_WROWS_MAX_SPLIT : PD_F16_WROWS_MAX_SPLIT;
+    const int max_split = few ? 4 * F16_WROWS_MAX_SPLIT : F16_WROWS_MAX_SPLIT;
     nsplit = nsplit > max_split ? max_split : nsplit;
-    while (nsplit > 1 && nitems / nsplit < (few ? PD_F16_WROWS_MIN_ITEMS / 4 : PD_F16_WROWS_MIN_ITEMS)) --nsplit;
+    while (nsplit > 1 && nitems / nsplit < (few ? F16_WROWS_MIN_ITEMS / 4 : F16_WROWS_MIN_ITEMS)) --nsplit;
     // Round 6 (the sample-count cliffs): between 129 and 255 row tiles (33 - 63 samples of 256 tokens) 256 / ntiles is 1 and
     // every block walks ALL columns while up to half the CUs idle - 36 samples ran the SwiGLU projection in 92 us against 68 us at 32.  One
     // block per CU means whole rounds: s blocks per row tile cost ceil(ntiles s / 256) rounds of (staging + 1 / s of the columns), staging
     // ~ 15 % of a full tile (fitted: with 8 % the model picked s = 4 for 48 samples, measured 326.8 -> 333.8 ms per call; 36 / 40 samples
     // take s = 3: 291.1 -> 277.8 / 299.4 -> 288.9 ms, profiles/r06_ab_wrows_rounds.txt); take the cheapest s (the smallest on a tie).
-    if (PRO != 3 && ntiles > 128 && ntiles < 256 && PD_F16_WROWS_ROUNDS) {
+    if (PRO != 3 && ntiles > 128 && ntiles < 256) {
         float best = 1e9f;
-        for (int sp = 1; sp <= 6 && nitems / sp >= PD_F16_WROWS_MIN_ITEMS; ++sp) {
+        for (int sp = 1; sp <= 6 && nitems / sp >= F16_WROWS_MIN_ITEMS; ++sp) {
             const float c = (float)((ntiles * sp + 255) / 256) * (0.15f + 1.0f / (float)sp);
             if (c < best - 1e-4f) { best = c; nsplit = sp; }
         }
@@ -1035,32 +761,6 @@ int run_f16_wrows(int op, const pd_gemm_args* p, hipStream_t s) {
 }
 
 int dispatch_f16_wrows(int op, int pro, int epi, const pd_gemm_args* p, hipStream_t s) {
-#ifdef PD_F16_WROWS_12
-    // lab: head-norm / plain epilogues with N a multiple of 768 (q | k | v: 1536 = 24 units of 64 columns) on TWELVE waves (three per
-    // SIMD) x two 64 x 64 units each.  Measured 88.9 - 91.9 us against 92.6 - 94.9 us for sixteen waves x three 64 x 32 items, bench
-    // unchanged: what the larger unit gains per wave (+ 25 % MFMA throughput) the fourth wave per SIMD gave anyway.  Off.
-    if ((pro == 1 || pro == 2) && (epi == EPI_HN || epi == EPI_PLAIN) && (op == 1 || p->N % 768 == 0)) {
-        int r = PD_ERR_UNSUPPORTED;
-        if (pro == 1 && epi == EPI_HN) r = run_f16_wrows<1, EPI_HN, 2, 2, 2, 12>(op, p, s);
-        if (pro == 2 && epi == EPI_HN) r = run_f16_wrows<2, EPI_HN, 2, 2, 2, 12>(op, p, s);
-        if (pro == 1 && epi == EPI_PLAIN) r = run_f16_wrows<1, EPI_PLAIN, 2, 2, 2, 12>(op, p, s);
-        if (pro == 2 && epi == EPI_PLAIN) r = run_f16_wrows<2, EPI_PLAIN, 2, 2, 2, 12>(op, p, s);
-        if (op != 1 || r != PD_OK) return r;
-    }
-#endif
-#if PD_F16_WROWS_KS
-    if (op == 1 || wrows_ks_shape(p)) {       // 64 x 64 units with a K-split tail (chip-filling launches; set-up covers every form)
-        int r = PD_ERR_UNSUPPORTED;
-        if (pro == 1 && epi == EPI_HN) r = run_f16_wrows_ks<1, EPI_HN>(op, p, s);
-        if (pro == 2 && epi == EPI_HN) r = run_f16_wrows_ks<2, EPI_HN>(op, p, s);
-        if (pro == 1 && epi == EPI_PLAIN) r = run_f16_wrows_ks<1, EPI_PLAIN>(op, p, s);
-        if (pro == 2 && epi == EPI_PLAIN) r = run_f16_wrows_ks<2, EPI_PLAIN>(op, p, s);
-        if (pro == 3 && epi == EPI_GATERES) r = run_f16_wrows_ks<3, EPI_GATERES>(op, p, s);
-        if (pro == 3 && epi == EPI_PLAIN) r = run_f16_wrows_ks<3, EPI_PLAIN>(op, p, s);
-        if (op != 1 && r != PD_ERR_UNSUPPORTED) return r;
-        if (op == 1 && r != PD_OK && r != PD_ERR_UNSUPPORTED) return r;
-    }
-#endif
     if (pro == 1 && epi == EPI_HN) return run_f16_wrows<1, EPI_HN, 2, 1>(op, p, s);
     if (pro == 2 && epi == EPI_HN) return run_f16_wrows<2, EPI_HN, 2, 1>(op, p, s);
     if (pro == 1 && epi == EPI_PLAIN) return run_f16_wrows<1, EPI_PLAIN, 2, 1>(op, p, s);
@@ -1069,10 +769,6 @@ int dispatch_f16_wrows(int op, int pro, int epi, const pd_gemm_args* p, hipStrea
     if (pro == 3 && epi == EPI_PLAIN) return run_f16_wrows<3, EPI_PLAIN, 2, 1>(op, p, s);
     if (pro == 0 && epi == EPI_GATERES) return run_f16_wrows<0, EPI_GATERES, 2, 1>(op, p, s);
     if (pro == 0 && epi == EPI_PLAIN) return run_f16_wrows<0, EPI_PLAIN, 2, 1>(op, p, s);
-#ifdef PD_F16_WROWS_GLU12      // lab: 32 x 64 wave tiles, four-deep fragment ring (163 vs 128 us at 64 samples)
-    if (pro == 1 && epi == EPI_GLU) return run_f16_wrows<1, EPI_GLU, 1, 2>(op, p, s);
-    if (pro == 2 && epi == EPI_GLU) return run_f16_wrows<2, EPI_GLU, 1, 2>(op, p, s);
-#endif
     // SwiGLU: 64 x 64 wave tiles (a W fragment pair feeds two row blocks, an A fragment two column blocks: 24 MFMAs per 16-k step
     // and wave), two-deep fragment ring (64 accumulator registers leave room for no more; four waves per SIMD cover the L2 latency)
     if (pro == 1 && epi == EPI_GLU) return run_f16_wrows<1, EPI_GLU, 2, 2, 2>(op, p, s);
@@ -1204,28 +900,9 @@ int dispatch_f16_wchunk(int op, int epi, const pd_gemm_args* p, hipStream_t s) {
     return PD_ERR_UNSUPPORTED;
 }
 
-#ifndef PD_F16_WCHUNK
-#define PD_F16_WCHUNK 1                // lab: 0 = those launches stay on the tile kernel
-#endif
-
-#ifndef PD_F16_WROWS_A2
-#define PD_F16_WROWS_A2 1              // lab: 0 = pre-split A stays on the tile kernel
-#endif
-#ifndef PD_F16_WROWS_PLAIN
-#define PD_F16_WROWS_PLAIN 1            // lab: 0 = plain fp32 rows (K = 512, few samples) stay on the fp32 streaming kernel
-#endif
-#ifndef PD_F16_WROWS_PLAIN_MAX_TILES
-#define PD_F16_WROWS_PLAIN_MAX_TILES 39  // up to 9 samples of 256 tokens (from 40 tiles on the 64 x 128 tile kernel takes the launch)
-#endif
-#ifndef PD_F16_WROWS_TINY
-#define PD_F16_WROWS_TINY 1             // lab: 0 = launches below the tile kernels' thresholds never reach the wide-rows kernels
-#endif
-#ifndef PD_F16_WROWS_MIN_TILES_SPLIT
-#define PD_F16_WROWS_MIN_TILES_SPLIT 4    // norm-prologue forms (blocks may share a row tile): from one sample of 256 tokens on
-#endif
-#ifndef PD_F16_WROWS_MIN_TILES
-#define PD_F16_WROWS_MIN_TILES 128     // 64-row tiles, one block per CU: from half the chip on (32 samples of 256 tokens: 72 -> 66 us + the split pass; 48: 105 -> 74; 20: 49 -> 61, stays on the tile kernel)
-#endif
+constexpr int F16_WROWS_PLAIN_MAX_TILES = 39;  // up to 9 samples of 256 tokens (from 40 tiles on the 64 x 128 tile kernel takes the launch)
+constexpr int F16_WROWS_MIN_TILES_SPLIT = 4;   // norm-prologue forms (blocks may share a row tile): from one sample of 256 tokens on
+constexpr int F16_WROWS_MIN_TILES = 128;       // 64-row tiles, one block per CU: from half the chip on (32 samples of 256 tokens: 72 -> 66 us + the split pass; 48: 105 -> 74; 20: 49 -> 61, stays on the tile kernel)
 
 template <int PRO, int EPI, int BM>
 int run_f16_rows(int op, const pd_gemm_args* p, hipStream_t s) {
@@ -1249,43 +926,21 @@ int dispatch_f16_rows(int op, int pro, int epi, const pd_gemm_args* p, hipStream
     return PD_ERR_UNSUPPORTED;
 }
 
-#ifndef PD_F16_ROWS_MIN_TILES
-#define PD_F16_ROWS_MIN_TILES 512      // 128-row tiles from here on (two per block slot) ...
-#endif
-#ifndef PD_F16_ROWS_GIVEN_STATS
-#define PD_F16_ROWS_GIVEN_STATS 1      // also for launches that bring their statistics (lab: 0 = those stay on the tile kernel)
-#endif
-#ifndef PD_F16_ROWS_MIN_TILES64
-#define PD_F16_ROWS_MIN_TILES64 320    // ... else 64-row tiles if there are this many (10 samples of 2048 atoms)
-#endif
+constexpr int F16_ROWS_MIN_TILES = 512;      // 128-row tiles from here on (two per block slot) ...
+constexpr int F16_ROWS_MIN_TILES64 = 320;    // ... else 64-row tiles if there are this many (10 samples of 2048 atoms)
 
 using F128 = FTile<128, 128, 2, 8, true>;    // 2 x 4 waves of 64 x 32, direct W
 using F128G = FTile<128, 128, 4, 8, false>;  // 4 x 2 waves of 32 x 64 (GLU: a wave owns both columns of a pair), W through LDS
-#ifdef PD_F16_GLU_LDSW
-using F128GD = F128G;
-#else
 // ... direct W: with two parts and a pre-split A the two B fragment buffers fit (124 VGPRs, no spill; with the in-kernel norm
 // prologue they spill 4-8 registers, so those cases keep W in LDS): token SwiGLU projection 196 -> 190 us
 using F128GD = FTile<128, 128, 4, 8, true>;
-#endif
 
 // 64 x 128 tiles on four waves (1 x 4, 64 x 32 each: the register profile of the 128 x 128 tile), four blocks per CU: launches whose 128 x 128 tile count leaves CUs idle (the
 // token projections at ~8-30 samples: w2 / linear_o at 20 samples = 160 tiles of 128 x 128, 320 of these)
 using F64 = FTile<64, 128, 1, 4, true>;
 
-// lab: 256 x 128 tiles, 2 x 4 waves of 128 x 32 (each W fragment feeds four row blocks: half the W requests per MFMA)
-#ifndef PD_F16_T256_BPC
-#define PD_F16_T256_BPC 1
-#endif
-using F256 = FTile<256, 128, 2, 8, true, PD_F16_T256_BPC>;
-
 int dispatch_f16(int op, int pro, int epi, const pd_gemm_args* p, hipStream_t s, bool small) {
 #define PD_FCASE(P, E, TL) if (pro == P && epi == E) return run_f16<P, E, TL>(op, p, s);
-#ifdef PD_F16_T256
-    if (!small && (op == 1 || p->M % 256 == 0)) {
-        PD_FCASE(0, EPI_PLAIN, F256) PD_FCASE(3, EPI_PLAIN, F256)
-    }
-#endif
     if (small) {
         PD_FCASE(0, EPI_PLAIN, F64) PD_FCASE(1, EPI_PLAIN, F64) PD_FCASE(3, EPI_PLAIN, F64)
         PD_FCASE(1, EPI_HN, F64) PD_FCASE(2, EPI_HN, F64) PD_FCASE(3, EPI_HN, F64)
@@ -1336,16 +991,16 @@ extern "C" int pd_gemm_f16_try(const pd_gemm_args* args, int pro, int tile, void
     // 128 x 128 tiles when they fill the chip, else 64 x 128 tiles if there are enough of THOSE; smaller launches are latency-bound
     // (k-split fp32 kernel).  The caller's tile (its 64 x 64 choice below 192 row/column blocks) only says the rows come in 64s.
     const long long t128 = p.M % 128 == 0 ? (long long)(p.M / 128) * (p.N / 128) : 0, t64 = (long long)(p.M / 64) * (p.N / 128);
-    // (the tile kernels' own threshold; the wide-rows kernels below share a row tile among several blocks and take fewer: PD_F16_TINY)
+    // (the tile kernels' own threshold; the wide-rows kernels below share a row tile among several blocks and take fewer)
     // (long K - the token w2, K = 1408 - is worth the 64 x 128 tile from 96 tiles on: 31 us at 10 samples of 256 tokens against 39 us for the
     //  K-split fp32 pair at 6 - 7 samples and 49 us for the bf16 x 6 64 x 64 tile that took 8 - 9; tools/w2_paths.py, round 5)
-    const bool tiny = t128 < PD_F16_MIN_TILES && t64 < (p.K >= 1024 ? PD_F16_MIN_TILES_SMALL_LONGK : PD_F16_MIN_TILES_SMALL);
+    const bool tiny = t128 < F16_MIN_TILES && t64 < (p.K >= 1024 ? F16_MIN_TILES_SMALL_LONGK : F16_MIN_TILES_SMALL);
     // plain fp32 rows with K = 512 at a handful of samples (linear_o behind an attention that writes fp32: one launch whose blocks share
     // the row tiles, instead of the K-split pair of the fp32 streaming kernel: 7 + 7 us)
-    const bool plain512 = PD_F16_WROWS_PLAIN && p.K == 512 && !p.A2 && pro == 0 && !p.stats && !p.stats_inline && p.pro_act == PD_ACT_NONE &&
-                          p.M / 64 >= PD_F16_WROWS_MIN_TILES_SPLIT && p.M / 64 <= PD_F16_WROWS_PLAIN_MAX_TILES && t128 < PD_F16_MIN_TILES;
-    if (tiny && !(PD_F16_WROWS_TINY && p.K == 512 && !p.A2 && !p.stats && (p.stats_inline || plain512))) return PD_ERR_UNSUPPORTED;
-    const bool small = t128 < PD_F16_MIN_TILES;
+    const bool plain512 = p.K == 512 && !p.A2 && pro == 0 && !p.stats && !p.stats_inline && p.pro_act == PD_ACT_NONE &&
+                          p.M / 64 >= F16_WROWS_MIN_TILES_SPLIT && p.M / 64 <= F16_WROWS_PLAIN_MAX_TILES && t128 < F16_MIN_TILES;
+    if (tiny && !(p.K == 512 && !p.A2 && !p.stats && (p.stats_inline || plain512))) return PD_ERR_UNSUPPORTED;
+    const bool small = t128 < F16_MIN_TILES;
     if (p.rowscale_acc || (p.rowscale && !glut) || p.maskadd || p.out_scale != 1.f) return PD_ERR_UNSUPPORTED;
     int epi;
     if (glut) epi = small ? -1 : EPI_GLUT;
@@ -1365,25 +1020,25 @@ extern "C" int pd_gemm_f16_try(const pd_gemm_args* args, int pro, int tile, void
     // row statistics computed by the kernel itself (pd_gemm_args.stats_inline): the rows kernel (K = 128, whole 128-row tiles,
     // enough of them for two blocks per CU), or nothing
     // ... or that the caller supplies (K = 128 with a norm prologue: the rows kernel reads the rows once for all column tiles)
-    const bool rows_big = p.M % 128 == 0 && p.M / 128 >= PD_F16_ROWS_MIN_TILES;
+    const bool rows_big = p.M % 128 == 0 && p.M / 128 >= F16_ROWS_MIN_TILES;
     const bool rows_ok = p.K == 128 && !p.A2 && (pro == 1 || pro == 2) && p.pro_act == PD_ACT_NONE && p.act == PD_ACT_NONE &&
-                         (rows_big || p.M / 64 >= PD_F16_ROWS_MIN_TILES64) && (epi == EPI_HN || epi == EPI_PLAIN) &&
+                         (rows_big || p.M / 64 >= F16_ROWS_MIN_TILES64) && (epi == EPI_HN || epi == EPI_PLAIN) &&
                          (p.stats || p.stats_inline == 1 || p.stats_inline == 2) && p.lda % 4 == 0 && ((uintptr_t)p.A & 15) == 0 &&
                          (((uintptr_t)p.pro_w | (uintptr_t)p.pro_b) & 15) == 0 && p.pro_gstride % 4 == 0 &&
                          (pro != 2 || p.pro_rows_per_group > 0) && (long long)(p.N / 32) * 8 * 1024 * 2 < 0x7fffffffll;
     // K = 512: the wide-rows kernel (64-row tiles on sixteen waves; only with inline statistics: callers that pre-split A keep that path)
     const bool wrows_ok = p.K == 512 && !p.A2 && !p.stats && (pro == 1 || pro == 2) && p.pro_act == PD_ACT_NONE && p.act == PD_ACT_NONE &&
-                          p.M % 64 == 0 && p.M / 64 >= PD_F16_WROWS_MIN_TILES_SPLIT && (epi == EPI_HN || epi == EPI_PLAIN || (epi == EPI_GLU && p.N % 64 == 0)) &&
+                          p.M % 64 == 0 && p.M / 64 >= F16_WROWS_MIN_TILES_SPLIT && (epi == EPI_HN || epi == EPI_PLAIN || (epi == EPI_GLU && p.N % 64 == 0)) &&
                           (p.stats_inline == 1 || p.stats_inline == 2) && p.lda % 4 == 0 && ((uintptr_t)p.A & 15) == 0 &&
                           (((uintptr_t)p.pro_w | (uintptr_t)p.pro_b) & 15) == 0 && p.pro_gstride % 4 == 0 &&
                           (pro != 2 || p.pro_rows_per_group > 0) && (long long)(p.N / 32) * 32 * 1024 * 2 < 0x7fffffffll;
     // ... or with A already split (K = 512: linear_o behind the attention kernel's split output), plain / gate + residual epilogue
-    const bool wrows_a2 = PD_F16_WROWS_A2 && p.K == 512 && p.A2 && pro == 3 && p.act == PD_ACT_NONE && p.M / 64 >= PD_F16_WROWS_MIN_TILES && p.M % 64 == 0 &&
+    const bool wrows_a2 = p.K == 512 && p.A2 && pro == 3 && p.act == PD_ACT_NONE && p.M / 64 >= F16_WROWS_MIN_TILES && p.M % 64 == 0 &&
                           (epi == EPI_PLAIN || (epi == EPI_GATERES && (!p.mul || p.mul_rows_per_group % 64 == 0))) &&
                           (long long)(p.N / 32) * 32 * 1024 * 2 < 0x7fffffffll;
     // N = 512 with a long K and fp32 rows (the token w2): one accumulator tile per wave, K in double-buffered chunks
-    const bool wchunk_ok = PD_F16_WCHUNK && p.N == 512 && p.K > 512 && p.K % 64 == 0 && !p.A2 && !p.stats && !p.stats_inline && pro == 0 &&
-                           p.pro_act == PD_ACT_NONE && p.act == PD_ACT_NONE && p.M % 64 == 0 && p.M / 64 >= PD_F16_WROWS_MIN_TILES &&
+    const bool wchunk_ok = p.N == 512 && p.K > 512 && p.K % 64 == 0 && !p.A2 && !p.stats && !p.stats_inline && pro == 0 &&
+                           p.pro_act == PD_ACT_NONE && p.act == PD_ACT_NONE && p.M % 64 == 0 && p.M / 64 >= F16_WROWS_MIN_TILES &&
                            p.lda % 4 == 0 && ((uintptr_t)p.A & 15) == 0 &&
                            (epi == EPI_PLAIN || (epi == EPI_GATERES && (!p.mul || p.mul_rows_per_group % 64 == 0))) &&
                            (long long)16 * (p.K / 16) * 1024 * 2 < 0x7fffffffll;
@@ -1405,7 +1060,7 @@ extern "C" int pd_gemm_f16_try(const pd_gemm_args* args, int pro, int tile, void
         return dispatch_f16_wrows(0, pro, epi, &p, (hipStream_t)stream);
     }
     if (tiny) return PD_ERR_UNSUPPORTED;
-    if ((!p.stats && p.stats_inline) || (rows_ok && PD_F16_ROWS_GIVEN_STATS)) {
+    if ((!p.stats && p.stats_inline) || rows_ok) {
         const bool big = rows_big;
         if (!rows_ok) return PD_ERR_UNSUPPORTED;
         if (init_only == 2) {

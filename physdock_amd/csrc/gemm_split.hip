@@ -33,19 +33,8 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#ifndef PD_SPLIT_MIN_TILES
-#define PD_SPLIT_MIN_TILES 256
-#endif
-#ifndef PD_SPLIT_MIN_TILES_SMALL
-#define PD_SPLIT_MIN_TILES_SMALL 256
-#endif
-#if defined(PD_ABL) && PD_ABL == 6
-#define NPARTS_IS_3 0
-constexpr int NPARTS = 2;            // ablation: two operand parts / three products (timing estimate of a 2-part format; wrong results)
-#else
-#define NPARTS_IS_3 1
+constexpr int SPLIT_MIN_TILES = 256, SPLIT_MIN_TILES_SMALL = 256;
 constexpr int NPARTS = 3;
-#endif
 constexpr int KS = 16;               // k per LDS stage = one v_mfma_f32_32x32x16_bf16 step
 constexpr int PITCH = 24;            // bf16 per LDS row (48 bytes)
 constexpr int PITCH2 = 40;           // DW tiles: 32 k per row, 80 bytes apart (20 r mod 64 hits 16 distinct 4-bank groups: conflict-free b128 reads)
@@ -131,9 +120,6 @@ void gemm_split_kernel(const pd_gemm_args p) {
     bf16x8 rw[3][NW];                            // [part][i]: NW == 2 -> chunk w_q + 2 i (half i); NW == 1 -> chunk w_q (half w_q >> 1)
 
     auto gload = [&](int bm0, int bn0, int k0) {
-#if defined(PD_ABL) && (PD_ABL == 1 || PD_ABL == 5)
-        if (k0 != 0) return;                      // ablation: no A traffic inside a tile
-#endif
         const int r = bm0 + a_row;                // full tiles only: always < M
         if constexpr (AS) {
             const __bf16* ap3 = A3 + (long long)r * (nk * 32) + k0 + 8 * a_q;
@@ -162,9 +148,6 @@ void gemm_split_kernel(const pd_gemm_args p) {
     auto wfrag = [&](int buf, int bn0, int ks) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-#if defined(PD_ABL) && (PD_ABL == 2 || PD_ABL == 5)
-            ks = 0;                               // ablation: B operands always the same (L1-resident) block
-#endif
             const bf16x8* base = W3 + ((long long)((bn0 + wn * (32 * TN) + j * 32) >> 5) * nks + ks) * 64 + lane;
 #pragma unroll
             for (int part = 0; part < NPARTS; ++part) wf[buf][j][part] = base[part * wpart];
@@ -274,11 +257,9 @@ void gemm_split_kernel(const pd_gemm_args p) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     f32x16 c = acc[i][j];
-#if NPARTS_IS_3
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fw[j][2], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], fw[j][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fw[j][1], c, 0, 0, 0);
-#endif
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fw[j][1], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], fw[j][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], fw[j][0], c, 0, 0, 0);
@@ -315,11 +296,7 @@ void gemm_split_kernel(const pd_gemm_args p) {
                     }
                     if (kc >= p.K) v = f32x4{0.f, 0.f, 0.f, 0.f};
                     bf16x4 ph, pm, pl;
-#if defined(PD_ABL) && (PD_ABL == 3 || PD_ABL == 5)
-                    ph = pm = pl = __builtin_bit_cast(bf16x4, f32x2{ra[h][i][0], ra[h][i][1]});      // ablation: no prologue / split VALU
-#else
                     split4(v, ph, pm, pl);
-#endif
                     const int o = 16 * h + 4 * c;
                     *reinterpret_cast<bf16x4*>(base + o) = ph;
                     *reinterpret_cast<bf16x4*>(base + BM * PITCH2 + o) = pm;
@@ -339,11 +316,9 @@ void gemm_split_kernel(const pd_gemm_args p) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     f32x16 c = acc[i][j];
-#if NPARTS_IS_3
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], wf[ks][j][2], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][2], wf[ks][j][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], wf[ks][j][1], c, 0, 0, 0);
-#endif
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], wf[ks][j][1], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][1], wf[ks][j][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][0], wf[ks][j][0], c, 0, 0, 0);
@@ -373,9 +348,7 @@ void gemm_split_kernel(const pd_gemm_args p) {
                     wfrag(1, bn0, 2 * kt + 3);
                     // the other stage was last read in the previous iteration, which every wave left through its barrier
                     stage2(st ^ 1, (kt + 1) * 32);
-#if !defined(PD_ABL) || (PD_ABL != 4 && PD_ABL != 5)
                     lds_barrier();
-#endif
                 }
             }
         } else {
@@ -422,7 +395,6 @@ int run_split(int op, const pd_gemm_args* p, hipStream_t s) {
 
 using S128 = STile<128, 128, 2, 8, true>;  // 2 x 4 waves of 64 x 32
 using S128G = STile<128, 128, 4, 8, false>; // 4 x 2 waves of 32 x 64 (GLU): two B fragments per wave do not fit the register budget directly (the 4-wave 64 x 64 direct layout: same GEMM rate, -2 % end to end)
-using S128W4 = STile<128, 128, 2, 4>;      // 2 x 2 waves of 64 x 64
 using S64 = STile<64, 64, 2, 4, true>;
 using S12864 = STile<128, 64, 4, 4, true>;
 
@@ -437,9 +409,6 @@ int dispatch_split(int op, int pro, int epi, int tile, const pd_gemm_args* p, hi
     PD_SCASE(1, EPI_HN, 64, S64) PD_SCASE(2, EPI_HN, 64, S64)
     PD_SCASE(0, EPI_GATERES, 64, S64) PD_SCASE(0, EPI_TGATERES, 64, S64)
     PD_SCASE(1, EPI_GLU, 12864, S12864) PD_SCASE(2, EPI_GLU, 12864, S12864)
-#ifdef PD_LAB      // experiments: 32 x 64 wave tiles with a plain epilogue; the 4-wave 64 x 64 layout with a GLU epilogue
-    PD_SCASE(1, EPI_PLAIN, 1284, S128G) PD_SCASE(1, EPI_GLU, 1282, S128W4)
-#endif
 #undef PD_SCASE
     return PD_ERR_UNSUPPORTED;
 }
@@ -466,13 +435,6 @@ extern "C" int pd_gemm_split_try(const pd_gemm_args* args, int pro, int tile, vo
         if (pro != 0 || p.pro_act != PD_ACT_NONE || p.K % 32 != 0 || ((uintptr_t)p.A3 & 15) || tile != 128) return PD_ERR_UNSUPPORTED;
         pro = 3;
     }
-#ifdef PD_LAB
-    if (const char* f = getenv("PD_SPLIT_TILE")) { if (tile == 128) tile = atoi(f); }
-    if (tile == 1284 || tile == 1282) {
-        if (init_only == 2) return p.glu ? EPI_GLU : EPI_PLAIN;
-        return dispatch_split(0, pro, p.glu ? EPI_GLU : EPI_PLAIN, tile, &p, (hipStream_t)stream);
-    }
-#endif
     if (tile != 128 && tile != 64 && tile != 12864) return PD_ERR_UNSUPPORTED;
     const int tbm = tile == 64 ? 64 : 128, tbn = tile == 128 ? 128 : 64;
     const bool glut = p.out_mode == PD_OUT_TRANSPOSED && p.glu && !p.hn_w && !p.mul && !p.res && !p.act && !p.rowscale_acc &&
@@ -482,7 +444,7 @@ extern "C" int pd_gemm_split_try(const pd_gemm_args* args, int pro, int tile, vo
     if (p.M % tbm != 0 || p.N % tbn != 0) return PD_ERR_UNSUPPORTED;
     // Launches that do not fill the chip are latency-bound (two block barriers per 32-k slice here, one in gemm_stream.hip):
     // measured at 1-4 samples the fp32 kernel is faster on every DiT shape, from ~256 tiles on the split kernel wins.
-    if ((long long)(p.M / tbm) * (p.N / tbn) < (tile == 128 ? PD_SPLIT_MIN_TILES : PD_SPLIT_MIN_TILES_SMALL)) return PD_ERR_UNSUPPORTED;
+    if ((long long)(p.M / tbm) * (p.N / tbn) < (tile == 128 ? SPLIT_MIN_TILES : SPLIT_MIN_TILES_SMALL)) return PD_ERR_UNSUPPORTED;
     if (p.rowscale_acc || (p.rowscale && !glut) || p.maskadd || p.out_scale != 1.f) return PD_ERR_UNSUPPORTED;
     int epi;
     if (glut) epi = EPI_GLUT;

@@ -22,19 +22,12 @@
 #include "common.h"
 #include "physdock_hip.h"
 
-#ifdef PD_STREAM_SAMETILE
-#define PD_LT(x) ((x) & 0)          // experiment: every tile re-reads tile 0 (all loads hit L2 / TLB)
-#else
-#define PD_LT(x) (x)
-#endif
 
 #include "gemm_tile_common.h"
 
 namespace {
 
-#ifndef PD_KSPLIT_MAX_BYTES
-#define PD_KSPLIT_MAX_BYTES (12 << 20)
-#endif
+constexpr int KSPLIT_MAX_BYTES = 12 << 20;
 constexpr int BK = 32, LDK = BK + 4, NT = 256;
 
 // Block tile BM x BN, 4 waves laid out WM x WN, each wave TM x TN MFMA fragments of 32 x 32:
@@ -139,8 +132,8 @@ __global__ __launch_bounds__(NT, TL::BLOCKS_PER_CU) void gemm_stream_kernel(cons
     int bm0, bn0;
     coords(tile, bm0, bn0);
     if (!reduce_only) {
-        la.load(p.A, p.lda, PD_LT(bm0), p.M, kt_beg * BK, p.K, tid);
-        lw.load(p.W, p.ldw, PD_LT(bn0), p.N, kt_beg * BK, p.K, tid);
+        la.load(p.A, p.lda, bm0, p.M, kt_beg * BK, p.K, tid);
+        lw.load(p.W, p.ldw, bn0, p.N, kt_beg * BK, p.K, tid);
     }
 
     for (; tile < t_end; tile += t_step) {
@@ -248,8 +241,8 @@ __global__ __launch_bounds__(NT, TL::BLOCKS_PER_CU) void gemm_stream_kernel(cons
             const int cur = (kt - kt_beg) & 1;
             const bool more = kt + 1 < kt_end;
             if (more) {
-                la.load(p.A, p.lda, PD_LT(bm0), p.M, (kt + 1) * BK, p.K, tid);
-                lw.load(p.W, p.ldw, PD_LT(bn0), p.N, (kt + 1) * BK, p.K, tid);
+                la.load(p.A, p.lda, bm0, p.M, (kt + 1) * BK, p.K, tid);
+                lw.load(p.W, p.ldw, bn0, p.N, (kt + 1) * BK, p.K, tid);
             }
             const float* a = sA + cur * A_TILE;
             const float* w = sW + cur * W_TILE;
@@ -281,8 +274,8 @@ __global__ __launch_bounds__(NT, TL::BLOCKS_PER_CU) void gemm_stream_kernel(cons
         const int cur_bm0 = bm0, cur_bn0 = bn0;
         if (tile + t_step < t_end) {
             coords(tile + t_step, bm0, bn0);
-            la.load(p.A, p.lda, PD_LT(bm0), p.M, 0, p.K, tid);
-            lw.load(p.W, p.ldw, PD_LT(bn0), p.N, 0, p.K, tid);
+            la.load(p.A, p.lda, bm0, p.M, 0, p.K, tid);
+            lw.load(p.W, p.ldw, bn0, p.N, 0, p.K, tid);
         }
 
         if (ks > 1) {
@@ -407,7 +400,7 @@ extern "C" int pd_gemm_stream_try(const pd_gemm_args* args, int pro, int tile, v
         long long ks = nk / 4;
         if (ks > 8) ks = 8;
         if (ks > 512 / ntiles) ks = 512 / ntiles;
-        while (ks >= 2 && ntiles * ks * tbm * tbn * 4 > PD_KSPLIT_MAX_BYTES) --ks;      // the partial sums are written and read back: keep them L2-sized
+        while (ks >= 2 && ntiles * ks * tbm * tbn * 4 > KSPLIT_MAX_BYTES) --ks;      // the partial sums are written and read back: keep them L2-sized
         const long long need = ntiles * ks * tbm * tbn * 4;
         if (ks >= 2 && ntiles < 192 && need <= p.ksplit_ws_bytes) q.ksplit = (int)ks;
     }

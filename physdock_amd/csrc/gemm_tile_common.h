@@ -5,11 +5,6 @@
 #include "common.h"
 #include "physdock_hip.h"
 
-#ifdef PD_STREAM_NOEMIT
-#define PD_ST(dst, val) do { const float v_ = (val); if (v_ == 123.456f) (dst) = v_; } while (0)   // experiment: no stores
-#else
-#define PD_ST(dst, val) (dst) = (val)
-#endif
 
 namespace {
 
@@ -56,11 +51,11 @@ __device__ __forceinline__ void epilogue(const pd_gemm_args& p, const f32x16 (&a
             if (p.glu == 1) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], pd_silu_r(acc[i][0][r] + c0[0]) * (acc[i][TN - 1][r] + c0[TN - 1]));
+                    (Yo + pd_frag_row(r, 0) * ldy)[yoff] = pd_silu_r(acc[i][0][r] + c0[0]) * (acc[i][TN - 1][r] + c0[TN - 1]);
             } else {
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], (acc[i][0][r] + c0[0]) * pd_sigmoid_r(acc[i][TN - 1][r] + c0[TN - 1]));
+                    (Yo + pd_frag_row(r, 0) * ldy)[yoff] = (acc[i][0][r] + c0[0]) * pd_sigmoid_r(acc[i][TN - 1][r] + c0[TN - 1]);
             }
         } else {
 #pragma unroll
@@ -87,7 +82,7 @@ __device__ __forceinline__ void epilogue(const pd_gemm_args& p, const f32x16 (&a
 #pragma unroll
                     for (int r = 0; r < 16; ++r) rv[r] = (Ro + pd_frag_row(r, 0) * ldres)[roff];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], gv[r] + rv[r]);
+                    for (int r = 0; r < 16; ++r) (Yo + pd_frag_row(r, 0) * ldy)[yoff] = gv[r] + rv[r];
                     __builtin_amdgcn_sched_barrier(0);      // keep the 16/32 loads of one fragment from piling up with the next
                 } else if constexpr (EPI == EPI_HN) {
                     // pd_gemm_args.Y2: this fragment (one head's 32 columns of k or v) goes to the attention kernel already scaled
@@ -136,21 +131,21 @@ __device__ __forceinline__ void epilogue(const pd_gemm_args& p, const f32x16 (&a
                         }
                     } else {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], ov[r]);
+                        for (int r = 0; r < 16; ++r) (Yo + pd_frag_row(r, 0) * ldy)[yoff] = ov[r];
                     }
                 } else {
                     if (p.act == PD_ACT_SILU) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
-                            PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], pd_silu_r(acc[i][j][r] + c0[j]));
+                            (Yo + pd_frag_row(r, 0) * ldy)[yoff] = pd_silu_r(acc[i][j][r] + c0[j]);
                     } else if (p.act == PD_ACT_NONE) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
-                            PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], acc[i][j][r] + c0[j]);
+                            (Yo + pd_frag_row(r, 0) * ldy)[yoff] = acc[i][j][r] + c0[j];
                     } else {
 #pragma unroll
                         for (int r = 0; r < 16; ++r)
-                            PD_ST((Yo + pd_frag_row(r, 0) * ldy)[yoff], pd_act(acc[i][j][r] + c0[j], p.act));
+                            (Yo + pd_frag_row(r, 0) * ldy)[yoff] = pd_act(acc[i][j][r] + c0[j], p.act);
                     }
                 }
             }

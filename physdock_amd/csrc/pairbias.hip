@@ -14,15 +14,7 @@
 #include "common.h"
 #include "physdock_hip.h"
 
-#ifndef PD_PB_UB
-#define PD_PB_UB 8
-#endif
-#ifndef PD_PB_TR
-#define PD_PB_TR 8
-#endif
-#ifndef PD_PB_TR4
-#define PD_PB_TR4 32
-#endif
+constexpr int PB_UB = 8, PB_TR = 8, PB_TR4 = 32;
 
 namespace {
 
@@ -77,7 +69,7 @@ __global__ __launch_bounds__(256) void pair_bias_kernel(const float* __restrict_
             i = (int)tq + (int)dq;
             j = (int)(rr - dq * (unsigned)T2);
         };
-        constexpr int UB = NI < PD_PB_UB ? NI : PD_PB_UB;          // rows in flight per lane: UB independent 16-byte loads before any use
+        constexpr int UB = NI < PB_UB ? NI : PB_UB;          // rows in flight per lane: UB independent 16-byte loads before any use
         for (int q0 = 0; q0 < NI; q0 += UB) {
             f32x4 vv[UB];
 #pragma unroll
@@ -195,7 +187,7 @@ PD_EXPORT int pd_pair_bias(const float* x, const float* Wf, const float* c2, flo
     if (out_scale == 0.f) out_scale = 1.f;
     hipStream_t s = (hipStream_t)stream;
 #define PD_PB(LPR, HH) if (C == 4 * LPR && H == HH) \
-        return launch<LPR, HH, (LPR == 32 ? PD_PB_TR : PD_PB_TR4)>(x, Wf, c2, stats_out, maskadd, maskval, out_scale, frag, M, T1, T2, frag_transpose, mode, eps, s);
+        return launch<LPR, HH, (LPR == 32 ? PB_TR : PB_TR4)>(x, Wf, c2, stats_out, maskadd, maskval, out_scale, frag, M, T1, T2, frag_transpose, mode, eps, s);
     PD_PB(32, 4) PD_PB(32, 8) PD_PB(32, 16) PD_PB(4, 4) PD_PB(4, 24)
 #undef PD_PB
     return PD_ERR_UNSUPPORTED;
@@ -222,6 +214,6 @@ PD_EXPORT int pd_pair_bias_split(const float* x, const float* Wf, const float* c
     const unsigned sb = (unsigned)(268 - e) << 23;
     float z2_scale;
     memcpy(&z2_scale, &sb, 4);
-    return launch<32, 4, PD_PB_TR>(x, Wf, c2, stats_out, maskadd, maskval, out_scale, frag, (long long)T * T, T, T, frag_transpose, 0, eps,
+    return launch<32, 4, PB_TR>(x, Wf, c2, stats_out, maskadd, maskval, out_scale, frag, (long long)T * T, T, T, frag_transpose, 0, eps,
                                    (hipStream_t)stream, reinterpret_cast<unsigned short*>(z2), z2_scale);
 }

@@ -18,9 +18,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int C_ = 128;                 // channels = K of the up-projection = N of the down-projection
-#ifndef PD_TRANSITION_BM
-#define PD_TRANSITION_BM 64
-#endif
+constexpr int TRANSITION_BM = 64;      // rows per block
 constexpr int CH = 128;                 // hidden columns per chunk
 constexpr int LP = 136;                 // LDS row pitch in fp16 (272 bytes: 17 x 16)
 // rows per block tile: 128 rows on eight waves, one block per CU - or 64 rows on four waves, TWO blocks per CU: the same wave
@@ -190,34 +188,11 @@ void transition_f16_kernel(const pd_transition_args p) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     unsigned short* hs = reinterpret_cast<unsigned short*>(sH) + (64 * wm1 + 32 * i + 4 * hh) * LP + hid;
-#ifndef PD_TR_SILU
-#define PD_TR_SILU 0      // 0: IEEE division (shipped: measured fastest), 1: v_rcp_f32 in place, 2: v_rcp_f32 with the 16 gates of a fragment first, 3: v_rcp_f32 + a Newton step
-#endif
-#if PD_TR_SILU == 2
-                    float gate[16];
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) gate[r] = __builtin_amdgcn_rcpf(1.0f + __expf(-acc1[i][0][r] * ca));
-#endif
+                    // (SiLU by IEEE division: the v_rcp_f32 forms - in place, the 16 gates of a fragment first, with a Newton step - measured slower)
 #pragma unroll
                     for (int r = 0; r < 16; r += 2) {
-#if PD_TR_SILU == 0
                         const float h0 = pd_silu(acc1[i][0][r] * ca) * (acc1[i][1][r] * cb) * h_s;
                         const float h1 = pd_silu(acc1[i][0][r + 1] * ca) * (acc1[i][1][r + 1] * cb) * h_s;
-#elif PD_TR_SILU == 1
-                        const float h0 = pd_silu_r(acc1[i][0][r] * ca) * (acc1[i][1][r] * cb) * h_s;
-                        const float h1 = pd_silu_r(acc1[i][0][r + 1] * ca) * (acc1[i][1][r + 1] * cb) * h_s;
-#elif PD_TR_SILU == 2
-                        const float h0 = (acc1[i][0][r] * ca) * gate[r] * (acc1[i][1][r] * cb) * h_s;
-                        const float h1 = (acc1[i][0][r + 1] * ca) * gate[r + 1] * (acc1[i][1][r + 1] * cb) * h_s;
-#else       // 3: reciprocal + one Newton step (four instructions instead of the division's ten, 0.5 ulp)
-                        auto silu_n = [](float x) {
-                            const float d = 1.0f + __expf(-x);
-                            const float r0 = __builtin_amdgcn_rcpf(d);
-                            return x * __builtin_fmaf(__builtin_fmaf(-d, r0, 1.0f), r0, r0);
-                        };
-                        const float h0 = silu_n(acc1[i][0][r] * ca) * (acc1[i][1][r] * cb) * h_s;
-                        const float h1 = silu_n(acc1[i][0][r + 1] * ca) * (acc1[i][1][r + 1] * cb) * h_s;
-#endif
                         const pd_parts2 s2 = pd_split2h(h0, h1);
                         const int ro = ((r & 3) + 8 * (r >> 2)) * LP;      // row of register r (the lane half's 4 hh is in hs)
                         hs[ro] = (unsigned short)s2.h;
@@ -293,11 +268,9 @@ void transition_f16_kernel(const pd_transition_args p) {
 
 // x [M][128] updated in place; see include/physdock_hip.h pd_transition_args.  PD_ERR_UNSUPPORTED for other shapes (the caller
 // then runs the three-launch form).  init: M <= 0 with args == nullptr raises the dynamic-LDS limit.
-#ifndef PD_TRANSITION_MIN128
-#define PD_TRANSITION_MIN128 16       // (round 5: 256 -> 16; same-box ms per call at 2 / 4 / 8 / 12 samples 94.4 / 104.9 / 140.0 / 144.1 -> 92.5 / 102.4 / 136.4 / 138.8)
-#endif
+constexpr int TRANSITION_MIN128 = 16;       // 128-row tiles from which the fused transition takes a launch (round 5: 256 -> 16; same-box ms per call at 2 / 4 / 8 / 12 samples 94.4 / 104.9 / 140.0 / 144.1 -> 92.5 / 102.4 / 136.4 / 138.8)
 PD_EXPORT int pd_transition_f16(const pd_transition_args* a, void* stream) {
-    constexpr int BM = PD_TRANSITION_BM;
+    constexpr int BM = TRANSITION_BM;
     typedef TT<BM> T;
     auto k = transition_f16_kernel<3, BM>;
     if (!a) {
@@ -307,7 +280,7 @@ PD_EXPORT int pd_transition_f16(const pd_transition_args* a, void* stream) {
     if (!a->x || !a->shift || !a->scale1p || !a->gate || !a->W13 || !a->w13_inv || !a->W2 || !a->w2_inv || !a->y_amax || !a->h_amax)
         return PD_ERR_ARG;
     if (a->C != C_ || a->hidden != 3 * CH || a->M <= 0 || a->M % BM != 0) return PD_ERR_UNSUPPORTED;
-    if (a->M / 128 < PD_TRANSITION_MIN128) return PD_ERR_UNSUPPORTED;   // (below 2 048 rows the launches are latency-bound either way)
+    if (a->M / 128 < TRANSITION_MIN128) return PD_ERR_UNSUPPORTED;   // (below 2 048 rows the launches are latency-bound either way)
     if (a->rows_per_group > 0 && a->gstride % 4 != 0) return PD_ERR_UNSUPPORTED;
     if (((uintptr_t)a->x | (uintptr_t)a->shift | (uintptr_t)a->scale1p | (uintptr_t)a->W13 | (uintptr_t)a->W2) & 15) return PD_ERR_UNSUPPORTED;
     const int ntiles = a->M / BM, grid = 256 * T::BLOCKS_PER_CU;

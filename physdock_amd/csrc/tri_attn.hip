@@ -31,58 +31,25 @@ constexpr int KT = 64, KP = 40, VP = 72;        // attn_pipe.hip's tile layouts
 constexpr int K_PART = KT * KP, V_PART = 32 * VP;
 constexpr int STAGE = 2 * (K_PART + V_PART);
 constexpr int NTILE = 4;                        // 256 keys
-// PD_TRI_WLDS: where the head's 96 weight rows (48 KB of two-part fp16 fragments) come from during the projection.
-//   0 (form 2): every wave requests its weight fragments - and the low parts of its rows of z once per output tile - from L2: 0.9 MB of
-//     requests per block on the CU's vector-memory path, which is what the projection phase waits for (profiles/r06_tri_attn_forms.txt).
-//   1 (form 4): the weights are staged ONCE per block in LDS - in the space of the K / V tiles, which are not written before every wave
-//     has left the projection (the projected k / v tiles wait, packed, in 32 registers; one more block barrier) - so LDS stays at 78 KB =
-//     two blocks per CU, and the projection runs k-step-major over THREE accumulators (q, k, v), which streams both parts of the wave's
-//     rows of z through a three-deep ring exactly once: 0.43 MB of requests per block.  Every accumulator sees the same MFMA sequence as
-//     in form 0: results bit-identical.  (Form 3 of round 6 - weights in LDS BEHIND the K / V tiles, 126 KB = one block per CU - was slower
-//     than form 2: the attention phase at two waves per SIMD takes 45 us instead of 32.)
-#ifndef PD_TRI_WLDS
-#define PD_TRI_WLDS 1
-#endif
-constexpr bool WLDS = PD_TRI_WLDS != 0;
-#ifndef PD_TRI_ZD
-#define PD_TRI_ZD 2
-#endif
-constexpr int ZD = PD_TRI_ZD;                    // form 4: k-steps of the wave's rows of z in flight ahead of the MFMAs
+// Where the head's 96 weight rows (48 KB of two-part fp16 fragments) come from during the projection ("form 4" of round 6): the weights are
+// staged ONCE per block in LDS - in the space of the K / V tiles, which are not written before every wave has left the projection (the
+// projected k / v tiles wait, packed, in 32 registers; one more block barrier) - so LDS stays at 78 KB = two blocks per CU, and the
+// projection runs k-step-major over THREE accumulators (q, k, v), which streams both parts of the wave's rows of z through a three-deep ring
+// exactly once: 0.43 MB of requests per block.  (Form 2 - every wave requests its weight fragments, and the low parts of its rows of z once
+// per output tile, from L2: 0.9 MB of requests per block on the CU's vector-memory path, which is what its projection phase waited for,
+// profiles/r06_tri_attn_forms.txt - gave bit-identical results, slower.  Form 3 - weights in LDS BEHIND the K / V tiles, 126 KB = one block
+// per CU - was slower than form 2: the attention phase at two waves per SIMD takes 45 us instead of 32.)
+constexpr int ZD = 2;                            // k-steps of the wave's rows of z in flight ahead of the MFMAs
 constexpr int W_HALVES = 3 * 2 * NKS * 64 * 8;              // q, k, v tiles x 2 parts x 8 k-steps x 64 lanes x 8 halves = 48 KB
 static_assert(W_HALVES <= NTILE * STAGE, "the staged weights live in the K / V tiles' space");
-// PD_TRI_ROWS2 = 1 (lab): a block of SIXTEEN waves owns TWO pair rows of one head (waves 0 - 7 row 2 ip, waves 8 - 15 row 2 ip + 1): one
-// weight stage per two rows (in the first row's K / V space), and the two rows' waves walk the same bias tiles at the same time.  156 KB
-// of LDS: one block per CU, the same four waves per SIMD.
-#ifndef PD_TRI_ROWS2
-#define PD_TRI_ROWS2 0
-#endif
-constexpr int RPB = (PD_TRI_ROWS2 != 0 && WLDS) ? 2 : 1;    // pair rows per block
-constexpr int NTHR = 512 * RPB;
-constexpr int LDS_BYTES = RPB * NTILE * STAGE * 2;
+constexpr int NTHR = 512;
+constexpr int LDS_BYTES = NTILE * STAGE * 2;
 constexpr int LAZY = 3;
 constexpr float PSH = 14.0f - (float)LAZY;
 
 #define PD_SB() __builtin_amdgcn_sched_barrier(0)
 
-// lab ablations (timing only, wrong results; tools/abl_tri_attn.sh): 1 no attention phase, 2 weight fragments not loaded, 4 no
-// projection MFMAs, 8 no bias fetches, 16 rows of z not loaded, 32 no output stores
-#ifdef PD_TRI_ABL
-constexpr int ABL = PD_TRI_ABL;
-#else
-constexpr int ABL = 0;
-#endif
-
 __device__ __forceinline__ f32x16 mma(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-// MFMA of the projection (ablation 4 removes it)
-__device__ __forceinline__ f32x16 jmma(frag a, frag b, f32x16 c) {
-#ifdef PD_TRI_ABL
-    if (PD_TRI_ABL & 4) {
-        c[0] += __builtin_bit_cast(f32x4, a)[0] * 0.f + __builtin_bit_cast(f32x4, b)[0] * 0.f;
-        return c;
-    }
-#endif
-    return mma(a, b, c);
-}
 __device__ __forceinline__ float max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
 __device__ __forceinline__ void lds_barrier() {
@@ -92,18 +59,18 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 
-__global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const pd_tri_attn_args p) {
+__global__ __launch_bounds__(NTHR, 4) void tri_attn_kernel(const pd_tri_attn_args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds_all[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave_b = __builtin_amdgcn_readfirstlane(tid >> 6);       // wave of the block
-    const int wave = wave_b & 7, grp = wave_b >> 3;                      // wave of its pair row, pair row of the block
-    unsigned short* const lds = lds_all + grp * (NTILE * STAGE);         // the row's K / V tiles (the weights: lds_all, i.e. row 0's)
+    const int wave_b = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // grp is 0 in a block of eight waves, which hipcc cannot know: the wave index is masked and grp offsets the LDS base and the pair row,
+    // as in the retired two-rows-per-block form.  Dropping the arithmetic changes the register allocation of the whole kernel (NOTES.md
+    // "Retired lab knobs"), so it stays until the kernel is next re-measured.
+    const int wave = wave_b & 7, grp = wave_b >> 3;
+    unsigned short* const lds = lds_all + grp * (NTILE * STAGE);         // the K / V tiles (the staged weights: lds_all)
     const int l31 = lane & 31, hh = lane >> 5;
     int i = blockIdx.x, h = blockIdx.y;
-#ifndef PD_TRI_XCD
-#define PD_TRI_XCD 1
-#endif
-    if (PD_TRI_XCD && (gridDim.x & 7) == 0) {
+    if ((gridDim.x & 7) == 0) {
         // Workgroups go to the eight XCDs round-robin in dispatch order.  With the plain (row, head) grid the four heads of a pair row are
         // 256 dispatches apart: same XCD, but two of them a whole round later - the row's 128 KB of split z come from HBM twice.  Here the
         // four heads of a row are consecutive dispatches of ONE XCD: one fetch per row, the other three blocks hit that XCD's L2.
@@ -112,15 +79,7 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
         i = 8 * (slot >> 2) + (L & 7);
         h = slot & 3;
     }
-    i = RPB * i + grp;                                                  // (RPB = 2: the grid's x counts row PAIRS)
-#ifdef PD_TRI_SKEW
-    // lab: the two blocks resident on a CU are the linear ids L and L + 256 (round-robin over 8 XCDs x 32 CUs): delay every second group of
-    // 256 by PD_TRI_SKEW x 8 128 cycles so that one block projects (latency-bound) while the other attends (issue-bound)
-    if (((blockIdx.x + gridDim.x * blockIdx.y) >> 8) & 1) {
-#pragma unroll
-        for (int k = 0; k < PD_TRI_SKEW; ++k) __builtin_amdgcn_s_sleep(127);
-    }
-#endif
+    i += grp;
     const int T = p.T, nk = p.Treal;
     const long long bs = p.transpose ? CZ : (long long)T * CZ;          // floats between the batch rows i
     const long long ss = p.transpose ? (long long)T * CZ : CZ;          // floats between the sequence rows of one batch row
@@ -145,8 +104,6 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
     // (a wave without rows - T < 256 - reads the rows of wave 0: in bounds, projected, stored into tiles no query reads as keys < nk)
     const frag* zbase = reinterpret_cast<const frag*>(p.z2) + ((long long)i * ntile + (wave_active ? wave : 0)) * (NKS * 2 * 64) + lane;
     auto zfrag_g = [&](int s, int part) {
-        if constexpr (ABL & 16) return __builtin_bit_cast(frag, part ? u32x4{0x1c001c00u, 0x1c009c00u, 0x18001c00u, 0x1c001400u}
-                                                                      : u32x4{0x3c003c00u, 0x3c00bc00u, 0x38003c00u, 0x3c003400u});
         return zbase[(2 * s + part) * 64];
     };
     frag qf[2][2];                                                      // the wave's Q fragments (as attn_pipe.hip)
@@ -221,11 +178,6 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
     const auto rs_bias = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias_base), 0, nkt32 * 4096, 0x00020000);
     const int boff = lane * 16;
     auto load_bias = [&](f32x16& s, int kt32) {
-        if constexpr (ABL & 8) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-            return;
-        }
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_bias, boff, kt32 * 4096 + g * 1024, 0));
@@ -236,110 +188,59 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
     float* const op = row < T ? p.o + (long long)i * bs + (long long)row * ss + h * 32 + 4 * hh : nullptr;
     f32x16 o, sA, sB;
     // ---- 2. projection: weight fragments [2 parts][12 tiles][8 k-steps][64 lanes][8] (packing.split2_f16 of the [3 C][C] matrix)
-    if constexpr (WLDS) {
-        // 3 072 weight fragments of 16 bytes, six per thread: thread t takes fragments t, t + 512, ... of the head's slice, read in the
-        // order they are stored in (coalesced kilobytes): LDS [3 tiles q, k, v][2 parts][8 k-steps][64 lanes][8].  The weights (L2 hits)
-        // are requested FIRST and the first two k-steps of the wave's rows (HBM for the first head of a row) behind them: requests
-        // return in order, so the LDS stores wait for the weights only and the rows travel while the block stages and meets
-        frag zr[ZD + 1][2];
-        {
-            frag tmp[6 / RPB];
+    // 3 072 weight fragments of 16 bytes, six per thread: thread t takes fragments t, t + 512, ... of the head's slice, read in the
+    // order they are stored in (coalesced kilobytes): LDS [3 tiles q, k, v][2 parts][8 k-steps][64 lanes][8].  The weights (L2 hits)
+    // are requested FIRST and the first two k-steps of the wave's rows (HBM for the first head of a row) behind them: requests
+    // return in order, so the LDS stores wait for the weights only and the rows travel while the block stages and meets
+    frag zr[ZD + 1][2];
+    {
+        frag tmp[6];
 #pragma unroll
-            for (int j = 0; j < 6 / RPB; ++j) {
-                const int f = tid + NTHR * j;                           // (tile3 * 2 + part) * 512 + s * 64 + lane'
-                const int tp = f >> 9, sl = f & 511;
-                const int t3 = tp >> 1, part = tp & 1;
-                tmp[j] = (ABL & 2) ? __builtin_bit_cast(frag, u32x4{0x2c002c00u + (unsigned)j, 0xac002c00u, 0x28002c00u, 0x2c00a400u})      // (not zeros: a matrix pipe fed zeros draws less power and clocks higher)
-                                : reinterpret_cast<const frag*>(p.W2)[((part * 12 + 4 * t3 + h) * NKS) * 64 + sl];
-            }
-            PD_SB();
-#pragma unroll
-            for (int d = 0; d < ZD; ++d) { zr[d][0] = zfrag_g(d, 0); zr[d][1] = zfrag_g(d, 1); }
-            PD_SB();
-#pragma unroll
-            for (int j = 0; j < 6 / RPB; ++j) *reinterpret_cast<frag*>(lds_all + (tid + NTHR * j) * 8) = tmp[j];
+        for (int j = 0; j < 6; ++j) {
+            const int f = tid + NTHR * j;                           // (tile3 * 2 + part) * 512 + s * 64 + lane'
+            const int tp = f >> 9, sl = f & 511;
+            const int t3 = tp >> 1, part = tp & 1;
+            tmp[j] = reinterpret_cast<const frag*>(p.W2)[((part * 12 + 4 * t3 + h) * NKS) * 64 + sl];
         }
-        lds_barrier();                                                  // A: the weights are staged
-        auto wl = [&](int t3, int s, int part) { return *reinterpret_cast<const frag*>(lds_all + ((((t3 * 2 + part) * NKS + s) * 64 + lane) * 8)); };
-        f32x16 aq, ak, av;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { aq[r] = 0.f; ak[r] = 0.f; av[r] = 0.f; }
-#pragma unroll
-        for (int s = 0; s < NKS; ++s) {
-            const int c = s % (ZD + 1), n = (s + ZD) % (ZD + 1);
-            if (s + ZD < NKS) { zr[n][0] = zfrag_g(s + ZD, 0); zr[n][1] = zfrag_g(s + ZD, 1); }
-            PD_SB();
-            const frag wqh = wl(0, s, 0), wql = wl(0, s, 1), wkh = wl(1, s, 0), wkl = wl(1, s, 1), wvh = wl(2, s, 0), wvl = wl(2, s, 1);
-            aq = jmma(wqh, zr[c][1], aq);
-            aq = jmma(wql, zr[c][0], aq);
-            aq = jmma(wqh, zr[c][0], aq);
-            ak = jmma(wkh, zr[c][1], ak);
-            ak = jmma(wkl, zr[c][0], ak);
-            ak = jmma(wkh, zr[c][0], ak);
-            av = jmma(zr[c][1], wvh, av);
-            av = jmma(zr[c][0], wvl, av);
-            av = jmma(zr[c][0], wvh, av);
-            PD_SB();
-        }
-        make_q(aq);
-        u32x2 kh[4], kl[4], vh[4], vl[4];
-        pack(ak, fk, kh, kl);
-        pack(av, fv, vh, vl);
         PD_SB();
-        load_bias(sA, 0);                                               // the first two bias tiles travel while the block meets twice
-        load_bias(sB, 1);
-        lds_barrier();                                                  // B: every wave has left the projection: the weights are dead
-        store_k(kh, kl);
-        store_v(vh, vl);
-    } else {
-        frag zh[NKS];                                                   // high parts of all eight k-steps
 #pragma unroll
-        for (int s = 0; s < NKS; ++s) zh[s] = zfrag_g(s, 0);
-        const frag* wbase = reinterpret_cast<const frag*>(p.W2) + lane;
-        auto wfrag = [&](int tile, int s, int part) {
-            if constexpr (ABL & 2) return __builtin_bit_cast(frag, u32x4{0x3c003c00u + tile, 0x3c003c00u + s, 0x3c003c00u + part, 0x3c003c00u});
-            return wbase[((part * 12 + tile) * NKS + s) * 64];
-        };
-        // one 32-row output tile of the projection: 24 MFMAs, the weight fragments of k-step s + 1 requested in front of the MFMAs of
-        // k-step s and no further ahead (sched_barrier: the row fragments already hold 64 registers).  transposed: rows of the
-        // accumulator = output channels (A = weights, B = rows of z); else rows = rows of z
-        auto project = [&](int wtile, bool transposed) {
-            f32x16 acc;
+        for (int d = 0; d < ZD; ++d) { zr[d][0] = zfrag_g(d, 0); zr[d][1] = zfrag_g(d, 1); }
+        PD_SB();
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-            // fragments of k-steps s + 1 and s + 2 are in flight while the MFMAs of k-step s issue (L2 round trips of ~1 us against 96 matrix
-            // cycles per k-step; the sched_barriers keep hipcc from hoisting all sixteen requests - 64 registers - to the top)
-            frag wh[3], wl[3], zl[3];
-#pragma unroll
-            for (int d = 0; d < 2; ++d) { wh[d] = wfrag(wtile, d, 0); wl[d] = wfrag(wtile, d, 1); zl[d] = zfrag_g(d, 1); }
-#pragma unroll
-            for (int s = 0; s < NKS; ++s) {
-                const int c = s % 3, n = (s + 2) % 3;
-                if (s + 2 < NKS) { wh[n] = wfrag(wtile, s + 2, 0); wl[n] = wfrag(wtile, s + 2, 1); zl[n] = zfrag_g(s + 2, 1); }
-                PD_SB();
-                if (transposed) {
-                    acc = jmma(wh[c], zl[c], acc);
-                    acc = jmma(wl[c], zh[s], acc);
-                    acc = jmma(wh[c], zh[s], acc);
-                } else {
-                    acc = jmma(zl[c], wh[c], acc);
-                    acc = jmma(zh[s], wl[c], acc);
-                    acc = jmma(zh[s], wh[c], acc);
-                }
-                PD_SB();
-            }
-            return acc;
-        };
-        u32x2 ph[4], pl[4];
-        make_q(project(h, true));
-        pack(project(4 + h, true), fk, ph, pl);
-        store_k(ph, pl);
-        pack(project(8 + h, false), fv, ph, pl);
-        store_v(ph, pl);
-        PD_SB();                                                        // (not above the projection: its fragments hold the registers)
-        load_bias(sA, 0);
-        load_bias(sB, 1);
+        for (int j = 0; j < 6; ++j) *reinterpret_cast<frag*>(lds_all + (tid + NTHR * j) * 8) = tmp[j];
     }
+    lds_barrier();                                                  // A: the weights are staged
+    auto wl = [&](int t3, int s, int part) { return *reinterpret_cast<const frag*>(lds_all + ((((t3 * 2 + part) * NKS + s) * 64 + lane) * 8)); };
+    f32x16 aq, ak, av;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { aq[r] = 0.f; ak[r] = 0.f; av[r] = 0.f; }
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+        const int c = s % (ZD + 1), n = (s + ZD) % (ZD + 1);
+        if (s + ZD < NKS) { zr[n][0] = zfrag_g(s + ZD, 0); zr[n][1] = zfrag_g(s + ZD, 1); }
+        PD_SB();
+        const frag wqh = wl(0, s, 0), wql = wl(0, s, 1), wkh = wl(1, s, 0), wkl = wl(1, s, 1), wvh = wl(2, s, 0), wvl = wl(2, s, 1);
+        aq = mma(wqh, zr[c][1], aq);
+        aq = mma(wql, zr[c][0], aq);
+        aq = mma(wqh, zr[c][0], aq);
+        ak = mma(wkh, zr[c][1], ak);
+        ak = mma(wkl, zr[c][0], ak);
+        ak = mma(wkh, zr[c][0], ak);
+        av = mma(zr[c][1], wvh, av);
+        av = mma(zr[c][0], wvl, av);
+        av = mma(zr[c][0], wvh, av);
+        PD_SB();
+    }
+    make_q(aq);
+    u32x2 kh[4], kl[4], vh[4], vl[4];
+    pack(ak, fk, kh, kl);
+    pack(av, fv, vh, vl);
+    PD_SB();
+    load_bias(sA, 0);                                               // the first two bias tiles travel while the block meets twice
+    load_bias(sB, 1);
+    lds_barrier();                                                  // B: every wave has left the projection: the weights are dead
+    store_k(kh, kl);
+    store_v(vh, vl);
 
     // ---- 3. attention over the resident tiles (the wave program of attn_pipe.hip)
 #pragma unroll
@@ -491,7 +392,7 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
         l_run = l_run * alpha + ps;
     };
 
-    if (wave_active && !(ABL & 1)) {
+    if (wave_active) {
         float mloc;
         frag kf0[2];
         scores(sA, kbase(0));
@@ -510,10 +411,10 @@ __global__ __launch_bounds__(NTHR, RPB == 2 ? 1 : 4) void tri_attn_kernel(const 
         }
     }
 
-    // ---- 4. output, in accumulator order.  (The stores cost ~5 of 54 us - ablation 32 - and it is their bytes, not their shape: turning the
+    // ---- 4. output, in accumulator order.  (The stores cost ~5 of 54 us and it is their bytes, not their shape: turning the
     // wave's tile row-major through LDS so that eight lanes write one row's 128 bytes - 4 x fewer, whole-line requests, one more block
     // barrier - measured 56.3 / 59.4 us against 57.0 / 58.6 us, profiles/r06_tri_attn_form4.txt.)
-    if (op && (!(ABL & 32) || l_run == 12345.f)) {                      // (ablation 32: no output stores)
+    if (op) {
         const float inv = inv_sv / pd_xhalf_sum(l_run);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -541,6 +442,6 @@ PD_EXPORT int pd_tri_attention(const pd_tri_attn_args* a, void* stream) {
             return PD_ERR_LAUNCH;
         raised = true;
     }
-    hipLaunchKernelGGL(tri_attn_kernel, dim3((unsigned)(a->T / RPB), CZ / 32), dim3(NTHR), LDS_BYTES, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(tri_attn_kernel, dim3((unsigned)a->T, CZ / 32), dim3(NTHR), LDS_BYTES, (hipStream_t)stream, *a);
     return pd_check_launch();
 }

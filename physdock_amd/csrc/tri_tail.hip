@@ -45,30 +45,9 @@ __device__ __forceinline__ void block_barrier() {
     asm volatile("" ::: "memory");
 }
 
-// lab ablations (timing only, wrong results): 1 no re-read of z in the epilogue, 2 no store of z, 4 no MFMAs, 8 rows of o not loaded,
-// 16 rows of z not loaded
-#ifdef PD_TRI_TAIL_ABL
-constexpr int TABL = PD_TRI_TAIL_ABL;
-#else
-constexpr int TABL = 0;
-#endif
-#ifndef PD_TRI_TAIL_GRID0
-#define PD_TRI_TAIL_GRID0 3     // blocks per CU of the launch, MODE 0 (47 KB of LDS)
-#endif
-#ifndef PD_TRI_TAIL_GRID1
-#define PD_TRI_TAIL_GRID1 2     // MODE 1 (71 KB)
-#endif
-__device__ __forceinline__ f32x16 tmma(f16x8 a, f16x8 b, f32x16 c, int, int, int) {
-    if constexpr (TABL & 4) { c[0] += (float)a[0] + (float)b[0]; return c; }
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-#ifndef PD_TRI_TAIL_EPI
-#define PD_TRI_TAIL_EPI 1       // lab: 0 = z re-read and stored in accumulator order
-#endif
-#ifndef PD_TRI_TAIL_PF
-#define PD_TRI_TAIL_PF 0        // lab: 0 = a tile's rows requested at the top of its own iteration (the round-5 form)
-#endif
+constexpr int GRID0 = 3;        // blocks per CU of the launch, MODE 0 (47 KB of LDS)
+constexpr int GRID1 = 2;        // MODE 1 (71 KB)
+__device__ __forceinline__ f32x16 tmma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
 template <int MODE>
 __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args p) {
@@ -95,10 +74,10 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
     const int n = 32 * wave + l31;               // this lane's output column
     const float cg = p.wg_inv[n] * inv_z_s, cz = p.wz_inv[n] * inv_o_s, bg = p.bg ? p.bg[n] : 0.f, bz = p.bz ? p.bz[n] : 0.f;
 
-    // The rows of a tile are requested ONE TILE AHEAD (round 6): a block's life was a chain of round trips - rows of z and o from HBM,
-    // barrier, weight fragments from L2, the read-modify-write of z - with two waves per SIMD to hide them (39.7 / 30.7 us per launch for
-    // 100 / 75 MB: 2.5 TB/s).  Now the requests of tile t + 1 are issued right behind the barrier that ends tile t's staging and travel
-    // under its contractions and its epilogue; same arithmetic, bit-identical results.
+    // A block's life is a chain of round trips - rows of z and o from HBM, barrier, weight fragments from L2, the read-modify-write of z -
+    // with two waves per SIMD to hide them.  The rows of a tile are requested at the top of its own iteration: requesting tile t + 1 right
+    // behind the barrier that ends tile t's staging (bit-identical) measured 10 % slower, 43.2 against 38.4 us - the epilogue's reads of z
+    // queue behind the prefetched rows (NOTES.md "Retired lab knobs").
     const int pr = tid >> 2, pq = tid & 3;                  // staging: four threads per row, 16-byte chunks interleaved
     f32x4 zv[8];                                            // the thread's chunks of its z row
     f32x4 orv[MODE == 0 ? 1 : 8];                           // MODE 1: its chunks of the attention-output row
@@ -108,23 +87,23 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
         const bool live = row0 + pr < p.M;
         const float* zr = p.z + (row0 + (live ? pr : 0)) * C_;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) zv[i] = (TABL & 16) ? f32x4{1.f, 2.f, 3.f, (float)i} : *reinterpret_cast<const f32x4*>(zr + 4 * (pq + 4 * i));
+        for (int i = 0; i < 8; ++i) zv[i] = *reinterpret_cast<const f32x4*>(zr + 4 * (pq + 4 * i));
         if constexpr (MODE == 0) {
             const bool livel = row0 + lane < p.M;
             const float* orow = p.o + row0 + (livel ? lane : 0);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) ov[e] = (TABL & 8) ? (float)e : orow[(long long)(8 * wave + e) * p.M];
+            for (int e = 0; e < 8; ++e) ov[e] = orow[(long long)(8 * wave + e) * p.M];
         } else {
             const float* orow = p.o + (row0 + (live ? pr : 0)) * C_;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) orv[i] = (TABL & 8) ? f32x4{1.f, 2.f, 3.f, (float)i} : *reinterpret_cast<const f32x4*>(orow + 4 * (pq + 4 * i));
+            for (int i = 0; i < 8; ++i) orv[i] = *reinterpret_cast<const f32x4*>(orow + 4 * (pq + 4 * i));
         }
     };
     if ((int)blockIdx.x < ntiles) fetch(blockIdx.x);
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long row0 = (long long)tile * BM;
-        if (!PD_TRI_TAIL_PF && tile != (int)blockIdx.x) fetch(tile);
+        if (tile != (int)blockIdx.x) fetch(tile);
         // ---- phase 0: RMSNorm of the tile's z rows (four threads per row) -> scale -> split -> sA
         {
             const int r = pr, q = pq;
@@ -191,7 +170,6 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
             }
         }
         block_barrier();
-        if (PD_TRI_TAIL_PF && tile + (int)gridDim.x < ntiles) fetch(tile + gridDim.x);      // the next tile's rows travel from here on
         __builtin_amdgcn_sched_barrier(0);
 
         // ---- phase 1: gate logits = sA . W_g^T (K = 128), phase 2: update = sO . W_z^T (K = 32); this wave: all 64 rows x columns
@@ -219,9 +197,9 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
                     const f16x8 a0 = *reinterpret_cast<const f16x8*>(abase + 32 * i * LP + 16 * ks);
                     const f16x8 a1 = *reinterpret_cast<const f16x8*>(abase + PART_A + 32 * i * LP + 16 * ks);
                     f32x16 t = accg[i];
-                    t = tmma(a0, wf[ks % (PF + 1)][1], t, 0, 0, 0);
-                    t = tmma(a1, wf[ks % (PF + 1)][0], t, 0, 0, 0);
-                    t = tmma(a0, wf[ks % (PF + 1)][0], t, 0, 0, 0);
+                    t = tmma(a0, wf[ks % (PF + 1)][1], t);
+                    t = tmma(a1, wf[ks % (PF + 1)][0], t);
+                    t = tmma(a0, wf[ks % (PF + 1)][0], t);
                     accg[i] = t;
                 }
             }
@@ -242,31 +220,13 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
                     const f16x8 a0 = *reinterpret_cast<const f16x8*>(obase + 32 * i * OP + 16 * ks);
                     const f16x8 a1 = *reinterpret_cast<const f16x8*>(obase + PART_O + 32 * i * OP + 16 * ks);
                     f32x16 t = accz[i];
-                    t = tmma(a0, wf[ks % (PF + 1)][1], t, 0, 0, 0);
-                    t = tmma(a1, wf[ks % (PF + 1)][0], t, 0, 0, 0);
-                    t = tmma(a0, wf[ks % (PF + 1)][0], t, 0, 0, 0);
+                    t = tmma(a0, wf[ks % (PF + 1)][1], t);
+                    t = tmma(a1, wf[ks % (PF + 1)][0], t);
+                    t = tmma(a0, wf[ks % (PF + 1)][0], t);
                     accz[i] = t;
                 }
             }
         }
-        if constexpr (PD_TRI_TAIL_EPI == 0) {
-        // ---- epilogue, round-5 form (lab): z re-read and stored in accumulator order (lane = column: 4-byte accesses, 128-byte row segments)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const long long rb = row0 + 32 * i + 4 * hh;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const long long row = rb + (r & 3) + 8 * (r >> 2);
-                if (row < p.M) {
-                    float* zp = p.z + row * C_ + n;
-                    const float gl = accg[i][r] * cg + bg;
-                    const float zo = (TABL & 1) ? cg : *zp;
-                    const float zn = zo + (MODE == 0 ? pd_sigmoid(gl) : gl) * (accz[i][r] * cz + bz);
-                    if (!(TABL & 2) || zn == 12345.f) *zp = zn;
-                }
-            }
-        }
-        } else {
         // ---- epilogue: z += sigmoid(gate logits) * update with z read ONCE.  The staging threads still hold their chunks of the z rows
         // (zv: four threads per row); the accumulators hold lane = column.  Re-reading z in accumulator order cost 7.3 of 38 us and
         // storing it 2.8 (ablations, profiles/r06_tri_tail_ablations.txt).  Here the rows pass through LDS - an fp32 tile in the space
@@ -289,12 +249,11 @@ __global__ __launch_bounds__(4 * BM) void tri_tail_kernel(const pd_tri_tail_args
             }
         }
         block_barrier();                                          // Z: the updated rows are in D
-        if (row0 + pr < p.M && (!(TABL & 2) || cg == 12345.f)) {
+        if (row0 + pr < p.M) {
             float* zr = p.z + (row0 + pr) * C_;
 #pragma unroll
             for (int i = 0; i < 8; ++i)
                 *reinterpret_cast<f32x4*>(zr + 4 * (pq + 4 * i)) = *reinterpret_cast<const f32x4*>(D + pr * LP + 4 * (pq + 4 * i));
-        }
         }
         block_barrier();                          // the LDS tiles are free for the next tile
     }
@@ -315,10 +274,10 @@ PD_EXPORT int pd_tri_tail(const pd_tri_tail_args* a, void* stream) {
     if (((uintptr_t)a->z | (uintptr_t)a->w_in | (uintptr_t)a->Wg | (uintptr_t)a->Wz | (a->mode ? (uintptr_t)a->o : 0)) & 15) return PD_ERR_UNSUPPORTED;
     const int ntiles = (a->M + BM - 1) / BM;
     if (a->mode == 0) {
-        const int grid = 256 * PD_TRI_TAIL_GRID0;
+        const int grid = 256 * GRID0;
         hipLaunchKernelGGL(tri_tail_kernel<0>, dim3(ntiles < grid ? ntiles : grid), dim3(4 * BM), TM<0>::LDS_BYTES, (hipStream_t)stream, *a);
     } else {
-        const int grid = 256 * PD_TRI_TAIL_GRID1;
+        const int grid = 256 * GRID1;
         hipLaunchKernelGGL(tri_tail_kernel<1>, dim3(ntiles < grid ? ntiles : grid), dim3(4 * BM), TM<1>::LDS_BYTES, (hipStream_t)stream, *a);
     }
     return pd_check_launch();

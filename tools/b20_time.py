@@ -19,5 +19,5 @@ for B in [int(a) for a in sys.argv[1:]] or [20]:
     for i in range(n):
         x = model.sample_diffusion(dbatch, seed=10 + i, **kw)
     torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / n
-    print(f"B={B}: {dt * 1e3:.1f} ms per call, {B / dt:.1f} poses/s  (PD_ATTN_TAIL={os.environ.get('PD_ATTN_TAIL', 'default')})", flush=True)
+    print(f"B={B}: {dt * 1e3:.1f} ms per call, {B / dt:.1f} poses/s", flush=True)
     model.release_workspace()

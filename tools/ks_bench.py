@@ -1,6 +1,6 @@
-"""lab: the token-level projections of a DiT block that the K-split-tail wide-rows kernel takes (csrc/gemm_f16.hip, gemm_f16_wrows_ks_kernel):
+"""lab: the token-level projections of a DiT block on the wide-rows kernels (csrc/gemm_f16.hip, gemm_f16_wrows_kernel):
 q | k | v (LayerNorm + AdaLN prologue, head norm, k | v pre-split: N = 1536) and linear_o (pre-split A, gate + residual: N = 512), K = 512.
-Run once per build (PD_F16_WROWS_KS=0 / 1, tools/ab_ks.sh)."""
+"""
 import ctypes as C
 import math
 import os
@@ -56,5 +56,5 @@ for B in (64, 128):
                           mul_rows_per_group=rows, mul_gstride=0)
     t_o = timeit(lo)
     fl_q, fl_o = 2.0 * rows * 3 * Cd * Cd, 2.0 * rows * Cd * Cd
-    print(f"KS={os.environ.get('PD_F16_WROWS_KS', 'default')} B={B}: q|k|v {t_qkv:6.1f} us ({fl_q / t_qkv / 1e6:5.0f} TF, variant {seen[0]}) | linear_o {t_o:6.1f} us "
+    print(f"B={B}: q|k|v {t_qkv:6.1f} us ({fl_q / t_qkv / 1e6:5.0f} TF, variant {seen[0]}) | linear_o {t_o:6.1f} us "
           f"({fl_o / t_o / 1e6:5.0f} TF)", flush=True)
