@@ -441,6 +441,38 @@ int pd_pairwise_rmsd(const float* x, const int* idx, const float* ref, float* D,
  * L <= 1024, M <= 65535, n <= 65535 (else PD_ERR_UNSUPPORTED).                                                              */
 int pd_sym_rmsd(const float* x, const int* idx, const float* ref, const unsigned short* perms_t, float* D, float* rmsd_ref,
                 int* best_perm_ref, int n, int A, int L, int M, void* stream);
+/* PoseBusters-style geometry checks of P poses of one ligand in its receptor, without leaving the device (validity.hip; ABI 11,
+ * additive; the reference runs the `posebusters` package on the host through files, PhysDock/data/relaxation.py:24-50).  Tables,
+ * built once per ligand (physdock_amd/validity.py): lig_idx [L] the ligand's atoms in a pose (any order, any place); radius [A] van
+ * der Waals radii; rec_mask [A] 1 = the atom counts as receptor (never a ligand atom); lig_active [L] 0 = left out of the receptor
+ * and the non-bonded check (a hydrogen), never of the bond / angle checks; pair12 [n12][2], pair13 [n13][2] local ligand indices
+ * of the bonded and of the 1-3 pairs with their reference distances d12_ref, d13_ref; far [L][L] 1 = the pair is four or more bonds
+ * apart or in different fragments (read for a < b); planar [G][8] local indices of the groups that must be flat, padded with -1.
+ * Per pose p, with d the fp32 distance sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))):
+ *   val[p][0], [1]  min, max over bonded pairs of d / d12_ref        val[p][2], [3]  the same over 1-3 pairs and d13_ref
+ *   val[p][4]       min over active far pairs of d / (r_a + r_b)
+ *   val[p][5]       min over (active ligand atom a, receptor atom j) of d / (r_a + r_j);  worst[p] = the (a, j) that attains it,
+ *                   the lexicographically smallest pair on an exact tie
+ *   val[p][6]       min over the same pairs of d (Angstrom)
+ *   val[p][7]       max over groups and their atoms of the distance (Angstrom, computed in double) to the group's least-squares
+ *                   plane; 0 for a group whose atoms are collinear or coincident (second eigenvalue <= 1e-10 of the largest)
+ *   flags[p]        bit 0: [0] < bond_lo or [1] > bond_hi; bit 1: the same for [2], [3] and angle_lo, angle_hi; bit 2: [4] <
+ *                   internal_clash; bit 3: [5] < receptor_clash; bit 4: [7] > planarity; bit 5: detached < [6] < +inf - applied
+ *                   to the values as stored
+ * Empty sets (n12, n13, G may be 0; there may be no receptor atom) report 1 (columns 0 - 3), +inf (4 - 6), 0 (7), worst -1, and
+ * set no bit.  ws: pd_pose_validity_workspace_numel(P, A) 64-bit words of scratch (2 P ceil(A / PD_VALIDITY_REC_TILE)), written
+ * before they are read.  Results are bit-identical from launch to launch: minima of identically computed values, no atomics.
+ * L <= 1024, G <= 256, A <= 2^22, P <= 65535 (else PD_ERR_UNSUPPORTED).                                                          */
+#define PD_VALIDITY_REC_TILE 256
+typedef struct pd_validity_thresholds {
+    float bond_lo, bond_hi, angle_lo, angle_hi, internal_clash, receptor_clash, planarity, detached;
+} pd_validity_thresholds;
+int pd_pose_validity_workspace_numel(int P, int A);
+int pd_pose_validity(const float* x, const int* lig_idx, const float* radius, const unsigned char* rec_mask,
+                     const unsigned char* lig_active, const int* pair12, const float* d12_ref, const int* pair13,
+                     const float* d13_ref, const unsigned char* far, const int* planar, pd_validity_thresholds thr,
+                     unsigned long long* ws, float* val, int* worst, int* flags, int P, int A, int L, int n12, int n13, int G,
+                     void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

@@ -19,3 +19,4 @@ from .loss import ConfidenceLoss, cal_lddt, pae_loss, pde_loss, plddt_loss  # no
 from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_clash, get_metrics,  # noqa: F401
                       predicted_tm_score)  # (reference data/tools/get_metrics.py; csrc/metrics.hip)
 from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-corrected ligand RMSD for the ranking step; csrc/sym_rmsd.hip)
+from .validity import PoseValidity  # noqa: F401  (PoseBusters-style geometry checks of every pose; csrc/validity.hip)

@@ -108,6 +108,12 @@ class TriMulArgs(C.Structure):
                 ("transpose", C.c_int), ("q_amax", _fp), ("k_amax", _fp)]
 
 
+class ValidityThresholds(C.Structure):
+    """mirror of pd_validity_thresholds (passed by value)"""
+    _fields_ = [(k, C.c_float) for k in ("bond_lo", "bond_hi", "angle_lo", "angle_hi", "internal_clash", "receptor_clash",
+                                         "planarity", "detached")]
+
+
 class HipLibraryMissing(RuntimeError):
     pass
 
@@ -235,6 +241,8 @@ def _declare(L):
     sig("pd_metrics_pae_tm", p, p, p, p, p, p, p, p, p, p, i, i, i, p)
     sig("pd_metrics_clash", p, p, p, p, p, p, p, i, p, p, i, i, i, i, p)
     sig("pd_sym_rmsd", p, p, p, p, p, p, p, i, i, i, i, p)                               # ABI 11, additive (sym_rmsd.hip)
+    sig("pd_pose_validity_workspace_numel", i, i)                                    # ABI 11, additive (validity.hip)
+    sig("pd_pose_validity", p, p, p, p, p, p, p, p, p, p, p, ValidityThresholds, p, p, p, p, i, i, i, i, i, i, p)
 
 
 def ptr(t):

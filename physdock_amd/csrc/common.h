@@ -144,3 +144,16 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
+
+// Exact minimum of (value, index) pairs: a key holds the bits of a NON-NEGATIVE float in its high word and an index in its low
+// word, so keys are ordered as the pairs are and the smallest index wins a tie (sym_rmsd.hip, validity.hip)
+typedef unsigned long long pd_u64;
+__device__ __forceinline__ pd_u64 pd_key_min(pd_u64 a, pd_u64 b) { return a < b ? a : b; }
+__device__ __forceinline__ pd_u64 pd_wave_key_min(pd_u64 k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)k, o), hi = __shfl_xor((unsigned)(k >> 32), o);
+        k = pd_key_min(k, ((pd_u64)hi << 32) | lo);
+    }
+    return k;
+}

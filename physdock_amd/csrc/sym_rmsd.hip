@@ -19,17 +19,7 @@ constexpr int SYM_MAX_L = 1024;        // ligand atoms: (TJ + 1) * 16 * L bytes 
 constexpr int SYM_MAX_M = 65535;       // table rows: an unsigned short entry addresses an atom, the key's low word holds m
 constexpr int SYM_TJ_WIDE_MAX_L = 768;
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 key_min(u64 a, u64 b) { return a < b ? a : b; }
-__device__ __forceinline__ u64 wave_key_min(u64 k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned lo = __shfl_xor((unsigned)k, o), hi = __shfl_xor((unsigned)(k >> 32), o);
-        k = key_min(k, ((u64)hi << 32) | lo);
-    }
-    return k;
-}
+typedef pd_u64 u64;
 
 template <int TJ>
 __global__ __launch_bounds__(256) void sym_rmsd_kernel(const float* __restrict__ x, const int* __restrict__ idx,
@@ -78,17 +68,17 @@ __global__ __launch_bounds__(256) void sym_rmsd_kernel(const float* __restrict__
             }
         }
 #pragma unroll
-        for (int t = 0; t < TJ; ++t) best[t] = key_min(best[t], ((u64)__float_as_uint(acc[t]) << 32) | (unsigned)m);
+        for (int t = 0; t < TJ; ++t) best[t] = pd_key_min(best[t], ((u64)__float_as_uint(acc[t]) << 32) | (unsigned)m);
     }
 #pragma unroll
     for (int t = 0; t < TJ; ++t) {
-        const u64 k = wave_key_min(best[t]);
+        const u64 k = pd_wave_key_min(best[t]);
         if ((tid & 63) == 0) red[tid >> 6][t] = k;
     }
     __syncthreads();
     if (tid < TJ) {
         const int j = j0 + tid;
-        const u64 k = key_min(key_min(red[0][tid], red[1][tid]), key_min(red[2][tid], red[3][tid]));
+        const u64 k = pd_key_min(pd_key_min(red[0][tid], red[1][tid]), pd_key_min(red[2][tid], red[3][tid]));
         const float r = sqrtf(__uint_as_float((unsigned)(k >> 32)) / (float)L);
         if (j == i) {
             D[(long long)i * n + i] = 0.f;

@@ -86,13 +86,34 @@ def _mol_num_atoms(ref_mol) -> Optional[int]:
     return None
 
 
+def _device_accept(x_pred, chirality, validity):
+    """the device half of accept / reject: (per-pose list of bool, or None without a test; number of poses the validity test fails,
+    or None without it) - the chirality mask and the validity mask reach the host in ONE [*, B] read"""
+    masks = ([chirality.accept(x_pred)] if chirality is not None else []) + \
+            ([validity.check(x_pred)["valid"]] if validity is not None else [])
+    if not masks:
+        return None, None
+    rows = torch.stack(masks).tolist()
+    return [all(c) for c in zip(*rows)], (len(rows[-1]) - sum(rows[-1]) if validity is not None else None)
+
+
+def score_validity(validity, aligned, out) -> dict:
+    """redock(validity=): {"validity": PoseValidity.check of the kept poses} and, when they were scored by the confidence head too,
+    "order_confidence_valid": their ids best first with the valid poses in front"""
+    from .ranking import rank_by_confidence
+    res = {"validity": validity.check(aligned)}
+    if "confidence" in out:
+        res["order_confidence_valid"] = rank_by_confidence(out["confidence"], valid=res["validity"]["valid"])
+    return res
+
+
 def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses: Optional[torch.Tensor] = None,
            accept_fn: Optional[Callable[[torch.Tensor], bool]] = None, chirality=None, physics_correction: bool = False,
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
-           ligand_symmetry=None) -> dict:
+           ligand_symmetry=None, validity=None, validity_filter: bool = False) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -107,7 +128,12 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     the trunk's (s, z) of the last sampler call, and `order_confidence` = `ranking.rank_by_confidence` of it, a device LongTensor
     over the kept poses.  `ranking`, its `order` and `rmsd` are what they are without it.
     `ligand_symmetry` (a `symmetry.LigandSymmetry` of the ligand's atoms in pose order): `ranking` is built from the
-    symmetry-corrected ligand RMSD (`rank_poses(..., symmetry=)`); sampling, accept / reject and the confidence scores do not see it."""
+    symmetry-corrected ligand RMSD (`rank_poses(..., symmetry=)`); sampling, accept / reject and the confidence scores do not see it.
+    `validity` (a `validity.PoseValidity` of the ligand): the result gains `validity` = its `check` of the returned `poses` (the
+    aligned ones, in their order) and, together with `confidence=`, `order_confidence_valid` (`rank_by_confidence(..., valid=)`:
+    valid poses first).  With `validity_filter=True` as well a pose that fails a check is rejected where and when the chirality test
+    rejects (`physics_correction`, before `accept_fn`; the two masks share one read per round) and each round's log entry gains
+    `invalid`, the number of poses that failed.  Nothing else changes."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -170,7 +196,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
             cond = None                      # z [T,T,128] - hundreds of MB at large crops, per StreamPool replica) is released here
         # accept / reject (redocking.py:303-317): on the device when a ChiralityReference is given (one kernel, one [B]
         # mask to the host), else through the injected per-pose callable (which needs the poses on the host)
-        dev_ok = chirality.accept(x_pred).tolist() if (physics_correction and chirality is not None) else None
+        dev_ok, n_invalid = _device_accept(x_pred, chirality, validity if validity_filter else None) if physics_correction else (None, None)
         x_cpu = x_pred.cpu() if (physics_correction and accept_fn is not None) else x_pred
         flags = []
         for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
@@ -187,6 +213,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
                 reject.append(x)
         log.append({"round": rnd, "gamma_factor": factor, "accepted": int(sum(flags)), "sampled": len(flags),
                     "templates": 0 if templates is None else int(templates.shape[0])})
+        if n_invalid is not None:
+            log[-1]["invalid"] = n_invalid
         if physics_correction:
             factor = next_gamma_factor(factor, any(flags))
             if len(accept) >= max_samples:
@@ -207,6 +235,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out["ranking"] = rank_poses(poses, x_gt, w, is_lig, symmetry=ligand_symmetry)
     if confidence is not None:
         out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
+    if validity is not None:
+        out.update(score_validity(validity, aligned, out))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -244,7 +274,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -334,7 +364,8 @@ class _RedockState:
     def __init__(self, batch, pbatch, *, ref_mol=None, ref_mol_poses=None, accept_fn=None, chirality=None, physics_correction=False,
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
-                 steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None):
+                 steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
+                 validity_filter=False):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -358,6 +389,7 @@ class _RedockState:
         self.cond, self.done, self.templates = None, False, None
         self.confidence, self.conf_sz = confidence, None
         self.ligand_symmetry = ligand_symmetry
+        self.validity, self.validity_filter = validity, bool(validity_filter)
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -386,7 +418,7 @@ class _RedockState:
             self.cond = cond
         if rnd + 1 >= self.max_rounds:
             self.cond = None
-        dev_ok = self.chirality.accept(x_pred).tolist() if (self.pc and self.chirality is not None) else None
+        dev_ok, n_invalid = _device_accept(x_pred, self.chirality, self.validity if self.validity_filter else None) if self.pc else (None, None)
         x_cpu = x_pred.cpu() if (self.pc and self.accept_fn is not None) else x_pred
         flags = []
         for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
@@ -403,6 +435,8 @@ class _RedockState:
                 self.reject.append(x)
         self.log.append({"round": rnd, "gamma_factor": self.factor, "accepted": int(sum(flags)), "sampled": len(flags),
                          "templates": 0 if self.templates is None else int(self.templates.shape[0])})
+        if n_invalid is not None:
+            self.log[-1]["invalid"] = n_invalid
         if self.pc:
             self.factor = next_gamma_factor(self.factor, any(flags))
             if len(self.accept) >= self.max_samples:
@@ -430,6 +464,8 @@ class _RedockState:
             out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig, symmetry=self.ligand_symmetry)
         if self.confidence is not None:
             out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
+        if self.validity is not None:
+            out.update(score_validity(self.validity, aligned, out))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)

@@ -99,12 +99,20 @@ def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Te
     return out
 
 
-def rank_by_confidence(scores) -> torch.Tensor:
+def rank_by_confidence(scores, valid=None) -> torch.Tensor:
     """Pose ids, best first, by the ground-truth-free scores of `ConfidenceModule.score_poses` (or of `get_metrics` on stacked
     logits): descending ranking_confidence, ties by descending mean_plddt, then by ascending pose id.  LongTensor [P] on the
-    scores' device: two stable sorts there, nothing is read back."""
+    scores' device: two stable sorts there, nothing is read back.
+    `valid` (bool [P], e.g. `PoseValidity.check(...)["valid"]`): the valid poses come first, and the valid and the invalid ones
+    each keep that order among themselves (one more stable sort on the device)."""
     rc, pl = scores["ranking_confidence"].reshape(-1), scores["mean_plddt"].reshape(-1)
     if rc.shape != pl.shape:
         raise ValueError(f"ranking_confidence {tuple(rc.shape)} and mean_plddt {tuple(pl.shape)} differ in the number of poses")
     by_plddt = torch.sort(pl, descending=True, stable=True).indices          # stable: equal pLDDT keeps ascending pose id
-    return by_plddt[torch.sort(rc[by_plddt], descending=True, stable=True).indices]
+    order = by_plddt[torch.sort(rc[by_plddt], descending=True, stable=True).indices]
+    if valid is None:
+        return order
+    v = valid.reshape(-1)
+    if v.dtype != torch.bool or v.shape != rc.shape:
+        raise ValueError(f"valid must be a bool mask over the {rc.shape[0]} poses, got {v.dtype} {tuple(valid.shape)}")
+    return order[torch.sort((~v.to(order.device))[order].to(torch.uint8), stable=True).indices]
