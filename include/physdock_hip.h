@@ -473,6 +473,31 @@ int pd_pose_validity(const float* x, const int* lig_idx, const float* radius, co
                      const float* d13_ref, const unsigned char* far, const int* planar, pd_validity_thresholds thr,
                      unsigned long long* ws, float* val, int* worst, int* flags, int P, int A, int L, int n12, int n13, int G,
                      void* stream);
+/* lDDT-PLI of P poses of one ligand in its receptor against one ground truth, maximised over the ligand's automorphisms
+ * (lddt_pli.hip; ABI 11, additive).  Tables, built once per system on the host (physdock_amd/lddt_pli.py): lig_idx [L] the
+ * ligand's atoms in a pose; the contacts of the ground truth in CSR form - contact_start [L+1], contact_atom [n_contacts] (pose
+ * atom) and contact_dist [n_contacts] (its distance to ligand atom i in the ground truth); the candidate images of every ligand
+ * atom in CSR form - cand_start [L+1], cand_atom [n_cand] (local ligand index; the distinct perms[:, i], ascending); slot_t
+ * [L][M], atom-major as the table of pd_sym_rmsd: cand_atom[cand_start[i] + slot_t[i*M + m]] = perms[m][i].
+ * pd_lddt_pli_counts:  counts[p][cand_start[i] + s][t] = #{ contacts c of i : | |x_p[lig_idx[k]] - x_p[contact_atom[c]]| -
+ *   contact_dist[c] | < thr_t },  k = cand_atom[cand_start[i] + s], the distance as sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))).
+ *   An atom takes its contacts PD_LDDT_PLI_TILE at a time.  contact_atom / contact_dist may be NULL when n_contacts == 0.
+ * pd_lddt_pli_select:  best_perm[p] = the smallest m that maximises sum_i sum_t counts[p][cand_start[i] + slot_t[i*M + m]][t];
+ *   conserved[p][t] = that permutation's sum over i of the counts of threshold t; per_atom[p][i] = its sum over t for atom i /
+ *   (4 |N(i)|), 0 for an atom without contacts; lddt[p] = sum_t conserved[p][t] / (4 n_contacts), 0 without contacts (one fp32
+ *   division of the two integers each).  The totals of up to PD_LDDT_PLI_LDS_CAND candidates are kept in LDS, beyond that they
+ *   are read from counts.
+ * counts [P][n_cand][4] must be 16-byte aligned.  Integer sums throughout and an exact maximum: results do not depend on the
+ * launch shape.  No allocation, no synchronisation.  L <= 1024, M <= 65535, P <= 65535, L <= n_cand <= L * L, n_contacts <=
+ * PD_LDDT_PLI_MAX_CONTACTS (else PD_ERR_UNSUPPORTED).                                                                          */
+#define PD_LDDT_PLI_TILE 512
+#define PD_LDDT_PLI_LDS_CAND 4096
+#define PD_LDDT_PLI_MAX_CONTACTS ((1 << 29) - 1)
+int pd_lddt_pli_counts(const float* x, const int* lig_idx, const int* contact_start, const int* contact_atom,
+                       const float* contact_dist, const int* cand_start, const int* cand_atom, float thr0, float thr1, float thr2,
+                       float thr3, int* counts, int P, int A, int L, int n_contacts, int n_cand, void* stream);
+int pd_lddt_pli_select(const int* counts, const int* contact_start, const int* cand_start, const unsigned short* slot_t,
+                       float* lddt, int* conserved, float* per_atom, int* best_perm, int P, int L, int M, int n_cand, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

@@ -20,3 +20,4 @@ from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_cl
                       predicted_tm_score)  # (reference data/tools/get_metrics.py; csrc/metrics.hip)
 from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-corrected ligand RMSD for the ranking step; csrc/sym_rmsd.hip)
 from .validity import PoseValidity  # noqa: F401  (PoseBusters-style geometry checks of every pose; csrc/validity.hip)
+from .lddt_pli import LddtPli  # noqa: F401  (symmetry-aware lDDT-PLI of every pose against the ground truth; csrc/lddt_pli.hip)

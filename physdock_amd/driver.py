@@ -113,7 +113,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
-           ligand_symmetry=None, validity=None, validity_filter: bool = False) -> dict:
+           ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -133,7 +133,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     aligned ones, in their order) and, together with `confidence=`, `order_confidence_valid` (`rank_by_confidence(..., valid=)`:
     valid poses first).  With `validity_filter=True` as well a pose that fails a check is rejected where and when the chirality test
     rejects (`physics_correction`, before `accept_fn`; the two masks share one read per round) and each round's log entry gains
-    `invalid`, the number of poses that failed.  Nothing else changes."""
+    `invalid`, the number of poses that failed.  Nothing else changes.
+    `lddt_pli` (an `lddt_pli.LddtPli` of the system): `ranking` gains the lDDT-PLI of the kept poses (`rank_poses(..., lddt_pli=)`)."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -232,7 +233,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     out = {"poses": aligned, "accepted": n_accepted, "rounds": log, "gamma_factor": factor, "ranking": None}
     if ranking:
         from .ranking import rank_poses
-        out["ranking"] = rank_poses(poses, x_gt, w, is_lig, symmetry=ligand_symmetry)
+        out["ranking"] = rank_poses(poses, x_gt, w, is_lig, symmetry=ligand_symmetry, lddt_pli=lddt_pli)
     if confidence is not None:
         out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
     if validity is not None:
@@ -274,7 +275,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -365,7 +366,7 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False):
+                 validity_filter=False, lddt_pli=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -390,6 +391,7 @@ class _RedockState:
         self.confidence, self.conf_sz = confidence, None
         self.ligand_symmetry = ligand_symmetry
         self.validity, self.validity_filter = validity, bool(validity_filter)
+        self.lddt_pli = lddt_pli
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -461,7 +463,7 @@ class _RedockState:
         out = {"poses": aligned, "accepted": n_accepted, "rounds": self.log, "gamma_factor": self.factor, "ranking": None}
         if self.ranking:
             from .ranking import rank_poses
-            out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig, symmetry=self.ligand_symmetry)
+            out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig, symmetry=self.ligand_symmetry, lddt_pli=self.lddt_pli)
         if self.confidence is not None:
             out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
         if self.validity is not None:

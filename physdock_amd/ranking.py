@@ -71,12 +71,14 @@ def get_representatives(distance_matrix: np.ndarray, num_clusters: int = 5):
 
 
 def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Tensor, is_ligand_atom: torch.Tensor,
-               num_clusters: int = 5, symmetry=None):
+               num_clusters: int = 5, symmetry=None, lddt_pli=None):
     """Accepted poses [n,A,3] -> dict(order=ranked pose ids (global medoid first, redocking.py:410-418),
     rmsd=ligand RMSD to x_gt of the ranked poses, x_aligned, dist).
     With `symmetry` (symmetry.LigandSymmetry) dist, rmsd_all, rmsd and order are built from the symmetry-corrected RMSD, and
     the dict also holds rmsd_plain_all (the index-wise values the reference reports) and symmetry_complete (False: the
-    automorphism table was cut, the corrected values are upper bounds)."""
+    automorphism table was cut, the corrected values are upper bounds).
+    With `lddt_pli` (lddt_pli.LddtPli of the system) it also holds lddt_pli_all [n] (device), lddt_pli (floats of the ranked poses)
+    and lddt_pli_detail (the `LddtPli.score` dict) of x_pred as given - the measure needs no alignment; nothing else changes."""
     x_al = weighted_rigid_align(x_gt[None].expand(x_pred.shape[0], -1, -1).contiguous(), x_pred, align_weights)
     lig = torch.nonzero(is_ligand_atom.to(x_pred.device) > 0).flatten().to(torch.int32)
     D, r = pairwise_ligand_rmsd(x_al, lig, x_gt, symmetry=symmetry)
@@ -96,6 +98,10 @@ def rank_poses(x_pred: torch.Tensor, x_gt: torch.Tensor, align_weights: torch.Te
     if symmetry is not None:
         out["rmsd_plain_all"] = pairwise_ligand_rmsd(x_al, lig, x_gt)[1]
         out["symmetry_complete"] = bool(symmetry.complete)
+    if lddt_pli is not None:
+        detail = lddt_pli.score(x_pred)
+        lh = detail["lddt_pli"].cpu().numpy()
+        out.update(lddt_pli_all=detail["lddt_pli"], lddt_pli=[float(lh[i]) for i in ids], lddt_pli_detail=detail)
     return out
 
 
