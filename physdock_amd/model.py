@@ -16,22 +16,18 @@ relaxation branch runs (physics.py), ``conditioning=`` / ``return_conditioning=`
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 import os
-import threading
 from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 
-from . import ops
-from .engine import Engine, off
+from . import ops, sampling
+from .engine import Engine
 from .packing import PackedWeights
 from .params import param_shapes
 
 
-_CAPTURE_LOCK = threading.Lock()
 #: PD_CHECK_FINITE=1: EVERY sample_diffusion call checks its poses for inf / NaN (one tiny reduction + a host sync) and raises;
 #: without it the check still runs on the first call of every (shape, schedule, weights version) and on every eager call
 _CHECK_FINITE = os.environ.get("PD_CHECK_FINITE") == "1"
@@ -216,9 +212,10 @@ class PhysDock(nn.Module):
         return karras_noise_schedule(num_steps, sigma_data, s_max, s_min, p)
 
     def _step_plan(self, steps, gamma_0, gamma_min, step_scale_eta, ode_step_scale_eta, mmff_gamma_0_factor,
-                   align_ref_pos, p):
+                   align_ref_pos, p, relaxes=True):
         """Host-side resolution of every per-step scalar and branch of reference model.py:211-281
-        (all t-dependent branches depend only on the schedule, so none needs a device sync)."""
+        (all t-dependent branches depend only on the schedule, so none needs a device sync).
+        relaxes: is there a molecule to relax (the elif of model.py:252 is only reachable with one)"""
         sig = karras_noise_schedule(steps, p=p)
         sd = float(self.sigma_data)
         plan = []
@@ -229,13 +226,44 @@ class PhysDock(nn.Module):
             sdev = torch.sqrt(t_hat ** 2 - t_cur ** 2) if noisy else torch.zeros(())
             c_in = 1 / torch.sqrt(t_hat ** 2 + sd ** 2)
             c_noise = torch.log(t_hat / sd) / 4.0
+            align = bool(align_ref_pos and t_cur > gamma_min * mmff_gamma_0_factor)
             plan.append(dict(
                 t_hat=float(t_hat), sdev=float(sdev), noisy=noisy, c_in=float(c_in), tau=float(t_hat * c_noise),
                 c_skip=float(sd ** 2 / (sd ** 2 + t_hat ** 2)), c_out=float(sd * t_hat / torch.sqrt(sd ** 2 + t_hat ** 2)),
-                dt=float(t_next - t_hat), eta=float(step_scale_eta if noisy else ode_step_scale_eta),
-                align=bool(align_ref_pos and t_cur > gamma_min * mmff_gamma_0_factor),
-                mmff=bool(t_cur <= gamma_min * mmff_gamma_0_factor)))
+                dt=float(t_next - t_hat), eta=float(step_scale_eta if noisy else ode_step_scale_eta), align=align,
+                mmff=bool(relaxes and not align and t_cur <= gamma_min * mmff_gamma_0_factor)))
         return sig, plan
+
+    def _check_bounds_once(self, eng, sched, check):
+        """First call of this engine (= these weights) on this schedule: check the fp16-format operand bounds against what the
+        denoiser's launches really see (`check()` runs engine.check_dit_bounds) - a violated bound raises, on this and on EVERY later
+        call of this engine + schedule; a uselessly loose one moves the family to bf16 x 6: returns True, and the caller prepares
+        the denoiser again.  Once per (weights, schedule); replays and later systems pay nothing."""
+        ck = sched[:5]
+        if not (_BOUND_CHECK and ops.F16_GEMM and ops.SPLIT_GEMM) or ck in eng._bounds_checked:
+            return False
+        if ck in eng._bounds_failed:
+            raise eng._bounds_failed[ck]
+        try:
+            switched = check()
+        except FloatingPointError as e:
+            eng._bounds_failed[ck] = e
+            raise
+        eng._bounds_checked.add(ck)          # only a check that RETURNED counts (ADVICE r5)
+        if switched:
+            self._drop_graphs()
+        return bool(switched)
+
+    def _check_finite(self, outs, fresh, use_graph, who):
+        """Finite check: ALWAYS on the first call of a (shape, schedule, weights version) - the eager pass that precedes a graph
+        capture, and every eager call - and on every call with PD_CHECK_FINITE=1 (one tiny reduction + a host sync; replays stay
+        sync-free).  A violated magnitude bound (weights changed behind the engine's back through `.data`, a caller-supplied bound
+        that does not hold) overflows the fp16 operand format to inf / NaN: that must be an exception, not a pose."""
+        if (_CHECK_FINITE or fresh) and not all(bool(torch.isfinite(o).all()) for o in outs):
+            if use_graph:
+                self._drop_graphs()          # the loop captured from this pass would replay the same overflow
+            raise FloatingPointError(f"{who} produced non-finite coordinates: an fp16-format operand bound was violated "
+                                     "(rebuild the engine after changing weights; ops.F16_GEMM / F16_ATTN = False to confirm)")
 
     @torch.no_grad()
     def sample_diffusion(
@@ -269,7 +297,7 @@ class PhysDock(nn.Module):
 
         `ref_mol` switches on the relaxation branch (model.py:252-261) exactly as in the reference; how the relaxed
         ligand is produced is described in physics.py (device MMFF94 kernel, host RDKit, or an injected `relax_fn` with
-        the signature of the reference's `get_next_step_pos`)."""
+        the signature of the reference's `get_next_step_pos`).  The step loop itself is sampling.py."""
         from . import physics
         device = batch["x_gt"].device
         eng = self.engine(device)
@@ -281,7 +309,6 @@ class PhysDock(nn.Module):
         B = num_sample
         A = batch["ref_pos"].shape[0]            # padded atom count
         A_real = batch["_A_real"]
-        sp = ops.stream()
         if B <= 0:
             return torch.empty(0, A_real, 3, device=device)
 
@@ -294,35 +321,19 @@ class PhysDock(nn.Module):
             ref_mol_poses = physics.rdkit_ref_mol_poses(ref_mol, 512)[:, :n_lig_real]
 
         sig, plan = self._step_plan(steps, gamma_0, gamma_min, step_scale_eta, ode_step_scale_eta, mmff_gamma_0_factor,
-                                    align_ref_pos, karras_noise_schedule_power)
-        for p in plan:                                        # the elif of model.py:252 is only reachable with a molecule
-            p["mmff"] = bool(p["mmff"] and not p["align"] and relaxer.kind != "none")
+                                    align_ref_pos, karras_noise_schedule_power, relaxes=relaxer.kind != "none")
+        sched = sampling.sched_id(steps, sig, gamma_0, gamma_min, karras_noise_schedule_power)
 
         # ---- per-call setup: conditioning trunk, hoisted biases, AdaLN tables
         a, ap, s, z = conditioning if conditioning is not None else eng.conditioning(batch)
         tau = ws.get("tau", steps)
         tau.copy_(torch.tensor([p["tau"] for p in plan], dtype=torch.float32))
         prep = eng.prepare_dit(a, ap, s, z, batch, tau, B=B)
-        # First call of this engine (= these weights) on this schedule: check the fp16-format operand bounds against what the
-        # denoiser's launches really see (engine.check_dit_bounds) - a violated bound raises, a uselessly loose one moves the
-        # family to bf16 x 6 and the call is re-prepared.  Once per (weights, schedule); replays and later systems pay nothing.
-        ck = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min))
-        if _BOUND_CHECK and ops.F16_GEMM and ops.SPLIT_GEMM and ck not in eng._bounds_checked:
-            if ck in eng._bounds_failed:         # a violated bound stays an exception on EVERY later call of this engine + schedule
-                raise eng._bounds_failed[ck]
-            try:
-                switched = eng.check_dit_bounds(batch, a, s, prep, plan, B, float(self.sigma_data))
-            except FloatingPointError as e:
-                eng._bounds_failed[ck] = e
-                raise
-            eng._bounds_checked.add(ck)          # only a check that RETURNED counts
-            if switched:
-                self._drop_graphs()
-                prep = eng.prepare_dit(a, ap, s, z, batch, tau, B=B)
+        if self._check_bounds_once(eng, sched, lambda: eng.check_dit_bounds(batch, a, s, prep, plan, B, float(self.sigma_data))):
+            prep = eng.prepare_dit(a, ap, s, z, batch, tau, B=B)
 
-        # Everything the step loop reads is staged in workspace buffers: a captured hipGraph replays raw addresses, so
-        # no caller-owned or per-call temporary tensor may be referenced from inside the loop (a / s included: a graph
-        # captured with the trunk's own outputs must stay valid when a later call passes conditioning=, and vice versa).
+        # the denoiser's inputs are staged like the loop's own (sampling.py; a / s included: a graph captured with the trunk's own
+        # outputs must stay valid when a later call passes conditioning=, and vice versa)
         def staged(name, t):
             buf = ws.get("loop:" + name, *t.shape, dtype=t.dtype)
             buf.copy_(t)
@@ -332,258 +343,55 @@ class PhysDock(nn.Module):
         batch = dict(batch)
         for k in ("a_mask", "atom_id_to_token_id", "_tok_start", "ref_pos"):
             batch[k] = staged(k, batch[k])
-        lig_flag = batch["is_ligand"][batch["atom_id_to_token_id"]]          # index gather on metadata, once per call
-        if A_real < A:
-            lig_flag = lig_flag.clone()
-            lig_flag[A_real:] = 0                                            # padded atoms carry a placeholder token index
-        lig_w = ws.get("lig_w", A)
-        lig_w.copy_(batch["a_mask"] * lig_flag)
-        any_align = any(p["align"] for p in plan)
-        any_mmff = any(p["mmff"] for p in plan)
-        ref_dist = poses = lig_idx = atom_slot = tm_eps = None
-        n_conf = n_lig = 0
-        if (any_align and ref_mol_poses is not None) or any_mmff:
-            lig_idx = torch.nonzero(lig_flag > 0).flatten().to(torch.int32)
-            n_lig = int(lig_idx.numel())
-            lig_idx = staged("lig_idx", lig_idx)
-        if any_align:
-            bref = ws.get("batch_ref_pos", B, A, 3)
-            if ref_mol_poses is not None and ref_mol_poses.shape[1] == n_lig:   # mismatch: reference silently keeps ref_pos (model.py:229-243)
-                poses = staged("poses", ref_mol_poses.to(device).float())
-                n_conf = poses.shape[0]
-                ref_dist = ws.get("ref_dist", n_conf, n_lig, n_lig)
-                tm_eps = ws.get("tm_eps", B, n_conf)          # eps[b, c] scratch: lets the matching run conformer-parallel
-                ops.check(L.pd_pose_dist(ops.ptr(poses), ops.ptr(ref_dist), n_conf, n_lig, sp), "pose_dist")
-        if any_mmff:
-            if n_lig == 0:
-                raise ValueError("ref_mol given but the crop has no ligand atoms")
-            x_ref = ws.get("x_ref", B, A, 3)
-            if relaxer.kind == "host":
-                slot = torch.full((A,), -1, dtype=torch.int32, device=device)
-                slot[lig_idx.long()] = torch.arange(n_lig, dtype=torch.int32, device=device)
-                atom_slot = staged("atom_slot", slot)
-                lig_in = ws.get("lig_in", B, n_lig, 3)
-                lig_out = ws.get("lig_out", B, n_lig, 3)
-            else:
-                mm = relaxer.terms.device_tables(device, n_lig)
-                mm_ws = ws.get("mmff_ws", relaxer.terms.workspace_numel(B), dtype=torch.float64)
+        loop = sampling.StepLoop(eng, "loop:", [plan], B, A, sig[0], noise_scale_lambda, mmff_iters, noise is not None)
+        slot = loop.add_slot("loop:", "the crop", batch, batch["a_mask"], batch["ref_pos"], plan, relaxer, ref_mol_poses,
+                             noise, seed, sample_offset)
 
-        # ---- random numbers: parity mode copies the caller's draws into fixed buffers
-        x_a = ws.get("x_a", B, A, 3)
-        x_hat = ws.get("x_hat", B, A, 3)
-        x_den = ws.get("x_den", B, A, 3)
-        x_proj = ws.get("x_proj", B, A, 3)
-        n_noisy = sum(p["noisy"] for p in plan)
-        if noise is not None:
-            n_init = ws.get("n_init", B, A, 3, zero=True); n_init[:, :A_real].copy_(noise["init"])
-            n_rot = ws.get("n_rot", steps, 4, B); n_rot.copy_(noise["rot_u"])
-            n_tr = ws.get("n_trans", steps, B, 3); n_tr.copy_(noise["trans"])
-            n_dif = ws.get("n_diffuse", max(n_noisy, 1), B, A, 3, zero=True)
-            if n_noisy:
-                n_dif[:n_noisy, :, :A_real].copy_(noise["diffuse"])
-            seed_buf = None
-        else:
-            seed_buf = ws.get("seed", 1, dtype=torch.int64)
-            seed_buf.fill_(int(seed))
-        k_noisy = [sum(q["noisy"] for q in plan[:i]) for i in range(steps)]
-
-        def step_head(i):
-            """model.py:212-221: augmentation, noise injection, denoiser (the ligand read-out of a host relaxation: gather_fn below)"""
-            p = plan[i]
-            sp_ = ops.stream()
-            if i == 0 and any_align:     # `batch_ref_pos = ref_pos[None].repeat(...)` (model.py:183): part of the replayed loop
-                bref.copy_(batch["ref_pos"][None].expand(B, A, 3))
-            if noise is not None:
-                ru, tr = off(n_rot, i * 4 * B), off(n_tr, i * B * 3)
-                nz = off(n_dif, k_noisy[i] * B * A * 3) if p["noisy"] else None
-                sd_ptr = None
-                src, x_scale = (n_init, float(sig[0])) if i == 0 else (x_a, 1.0)
-            else:
-                ru = tr = nz = None
-                sd_ptr = ops.ptr(seed_buf)
-                src, x_scale = x_a, 1.0
-                if i == 0:
-                    ops.check(L.pd_init_noise(ops.ptr(x_a), sd_ptr, sample_offset, float(sig[0]), B, A, sp_), "init_noise")
-            ops.check(L.pd_augment(ops.ptr(src), x_scale, ops.ptr(batch["a_mask"]), ru, tr, nz, float(noise_scale_lambda),
-                                   p["sdev"], sd_ptr, i, sample_offset, ops.ptr(x_hat), B, A, sp_), "augment")
-            eng.af3_dit(batch, x_hat, x_den, a, s, prep, B, p, row=i)
-
-        def step_tail(i):
-            """model.py:223-281: physics correction and Euler update"""
-            p = plan[i]
-            sp_ = ops.stream()
-            if p["align"]:
-                if poses is not None:
-                    ops.check(L.pd_template_match(ops.ptr(x_den), ops.ptr(lig_idx), ops.ptr(ref_dist), ops.ptr(poses),
-                                                  ops.ptr(bref), ops.ptr(tm_eps), None, B, A, n_lig, n_conf, sp_), "template_match")
-                target, tstride = bref, A * 3
-            elif p["mmff"]:
-                if relaxer.kind == "host":
-                    ops.check(L.pd_ligand_scatter(ops.ptr(x_ref), ops.ptr(x_den), ops.ptr(lig_out), ops.ptr(atom_slot),
-                                                  B, A, n_lig, sp_), "ligand_scatter")
-                else:
-                    relaxer.terms.launch_relax(mm, x_den, lig_idx, x_ref, mm_ws, B, A, int(mmff_iters), sp_)
-                target, tstride = x_ref, A * 3
-            else:
-                ops.check(L.pd_euler(ops.ptr(x_hat), ops.ptr(x_den), None, None, p["t_hat"], p["eta"], p["dt"],
-                                     ops.ptr(x_a), B, A, sp_), "euler")
-                return
-            ops.check(L.pd_kabsch_align(ops.ptr(x_den), ops.ptr(batch["a_mask"]), ops.ptr(target), tstride, ops.ptr(lig_w),
-                                        ops.ptr(x_proj), B, A, sp_), "kabsch")
-            ops.check(L.pd_euler(ops.ptr(x_hat), ops.ptr(x_den), ops.ptr(x_proj), ops.ptr(lig_w), p["t_hat"], p["eta"],
-                                 p["dt"], ops.ptr(x_a), B, A, sp_), "euler")
-
-        # ---- the loop as UNITS (round 6): one unit = the launches of one step's head (augmentation + denoiser: ~115 kernels, the
-        #      expensive part) or of one step's tail (physics correction + Euler update: 1 - 4 kernels).  A head depends on the shape,
-        #      the schedule and the step index only; what the drivers change between calls - the physics threshold
-        #      (`mmff_gamma_0_factor` x 1.15 / x 0.7 per round, redocking.py:318-322), the template pool size, the relaxation - lives in
-        #      the tails.  Every unit is captured as its own hipGraph, keyed by exactly what its launches depend on, so a call with a new
-        #      threshold or pool replays all 40 heads and the unchanged tails and runs (then captures) only the few tails that changed.
-        #      A whole schedule seen twice is additionally captured as ONE graph (segments around a host relaxation), as before.
-        sched_id = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min), float(karras_noise_schedule_power))
-        common = (B, A, batch["target_feat"].shape[0], batch["_A_real"], batch["_T_real"], sched_id, noise is not None,
+        def denoise(i):
+            eng.af3_dit(batch, loop.x_hat, loop.x_den, a, s, prep, B, plan[i], row=i)
+        common = (B, A, batch["target_feat"].shape[0], A_real, batch["_T_real"], sched, noise is not None,
                   float(noise_scale_lambda), sample_offset)
-        host_relax_steps = relaxer.kind == "host"
-        pool_sig = poses is not None and (n_conf, n_lig)
-        relax_sig = (relaxer.kind, relaxer.kind == "device" and relaxer.terms.signature(), int(mmff_iters), n_lig)
+        units = loop.units(common, denoise)
 
-        def gather_fn(i):
-            ops.check(L.pd_ligand_gather(ops.ptr(x_den), ops.ptr(lig_idx), ops.ptr(lig_in), B, A, n_lig, ops.stream()), "ligand_gather")
-
-        units = []                   # (key, [(fn, i), ...], host break after this unit?)
-        for i, p in enumerate(plan):
-            units.append(((common, "H", i, p["noisy"], p["sdev"], p["t_hat"], i == 0 and any_align), [(step_head, i)], False))
-            if p["mmff"] and host_relax_steps:
-                units.append(((common, "G", i, n_lig), [(gather_fn, i)], True))
-            kind = ("align", pool_sig) if p["align"] else (("mmff", relax_sig) if p["mmff"] else ("plain",))
-            units.append(((common, "T", i, p["t_hat"], p["eta"], p["dt"], kind), [(step_tail, i)], False))
-        segments, cur = [], []
-        for ukey, fns, brk in units:
-            cur.extend(fns)
-            if brk:
-                segments.append(cur)
-                cur = []
-        segments.append(cur)
-
-        def run_fns(fns):
-            for fn, i in fns:
-                fn(i)
-
-        def host_relax():
-            lig_out.copy_(relaxer(lig_in.clone(), int(mmff_iters)).to(device=device, dtype=torch.float32))
-
-        def capture(fn_lists, sync=True):
-            """record (not run) each launch list as one hipGraph; one capture at a time per process: objects driven from several host
-            threads (parallel.StreamPool) replay concurrently, but two overlapping captures make unrelated launches of the other
-            thread fail.  sync=False (units recorded in the middle of a call, below): no device synchronisation around the recording -
-            nothing is enqueued on the recording stream, and the launch stream keeps executing the units issued before"""
-            import time as _time
-            with _CAPTURE_LOCK:
-                if sync:
-                    torch.cuda.synchronize()
-                t_cap = _time.perf_counter()
-                execs = []
-                cap = self._capture_stream if getattr(self, "_capture_stream", None) is not None else torch.cuda.Stream()
-                self._capture_stream = cap
-                with torch.cuda.stream(cap):
-                    for fns in fn_lists:
-                        ops.check(L.pd_graph_begin(ops.stream()), "graph_begin")
-                        run_fns(fns)
-                        ex = C.c_void_p()
-                        ops.check(L.pd_graph_end(ops.stream(), C.byref(ex)), "graph_end")
-                        execs.append(ex)
-                if sync:
-                    torch.cuda.synchronize()
-                    self.last_capture_ms = 1e3 * (_time.perf_counter() - t_cap)
-                else:
-                    self.last_capture_ms = (self.last_capture_ms or 0.0) + 1e3 * (_time.perf_counter() - t_cap)
-            return execs
-
-        fresh = not use_graph                 # did any launch of this call run eagerly (= was not replayed from a checked capture)?
+        # A whole schedule seen twice is additionally captured as ONE graph (one per segment around a host relaxation)
         entry = None
         if use_graph:
-            # (the REAL atom / token counts are launch arguments - reduction bounds - of the captured kernels: two systems that pad
-            #  to the same shape must not share a graph)
             key = (common, tuple(u[0] for u in units))
             entry = self._graphs.get(key)
             if entry is not None:
                 self._graphs[key] = self._graphs.pop(key)          # LRU order
         if entry is not None and entry["exec"] is not None:
+            fresh = False
+            breaks = [after for _, _, after, _ in units if after is not None]
             for k, g in enumerate(entry["exec"]):
-                ops.check(L.pd_graph_launch(g, sp), "graph_launch")
-                if k + 1 < len(segments):
-                    host_relax()
-        elif not use_graph:
-            for k, seg in enumerate(segments):
-                run_fns(seg)
-                if k + 1 < len(segments):
-                    host_relax()
+                ops.check(L.pd_graph_launch(g, ops.stream()), "graph_launch")
+                if k < len(breaks):
+                    breaks[k]()
         else:
-            # replay the units that exist; run the others eagerly - they produce this call's result AND allocate their workspace
-            # buffers, so the capture below (which only records) needs no launch of its own
-            # A missing unit whose KIND (head / gather / tail of one physics branch) has already run once on this shape - earlier in this
-            # call or in an earlier one - finds every workspace buffer it touches allocated: it is RECORDED first (no execution: ~12 us
-            # per launch on the host against ~35 us for an eager launch) and then launched like a cached one, while the GPU still works on
-            # the units issued before.  Only the first unit of a kind runs eagerly (it allocates).  First call of a new shape at 20 samples:
-            # 225 -> 179 ms against 164 ms cached; at 64 samples 392 -> 334 ms against 333 ms (profiles/r06_new_shape_call.txt).
-            missing, recorded = [], 0
-            terms = relaxer.terms if relaxer.kind == "device" else None
-            if PIPELINED_CAPTURE:
-                self.last_capture_ms = 0.0
-            for ukey, fns, brk in units:
-                u = self._units.get(ukey)
-                kind = (common, ukey[1], ukey[-1][0] if ukey[1] == "T" else None)
-                if u is None and PIPELINED_CAPTURE and kind in self._warm_kinds:
-                    ex = capture([fns], sync=False)[0]
-                    u = self._units[ukey] = {"exec": ex, "terms": terms if ukey[1] == "T" and ukey[-1][0] == "mmff" else None}
-                    self.unit_captures += 1
-                    recorded += 1
-                    fresh = True                                   # (its first execution: the finite check below applies)
-                if u is not None:
-                    self._units[ukey] = self._units.pop(ukey)      # LRU order
-                    ops.check(L.pd_graph_launch(u["exec"], sp), "graph_launch")
-                else:
-                    fresh = True
-                    run_fns(fns)
-                    missing.append((ukey, fns))
-                    self._warm_kinds.add(kind)
-                if brk:
-                    host_relax()
-            self.last_unit_misses = len(missing) + recorded
-            self.last_head_misses = sum(1 for k, _ in missing if k[1] == "H")
-            if missing:
-                # the captured launches hold raw device addresses: a unit keeps the MMFF table object whose tables it captured alive
-                # (a later call with an EQUAL table - same signature, e.g. rebuilt from the same RDKit molecule - replays against
-                # these tables, not against its own freshly built and soon freed ones)
-                for (ukey, _), ex in zip(missing, capture([fns for _, fns in missing], sync=not PIPELINED_CAPTURE)):
-                    self._units[ukey] = {"exec": ex, "terms": terms if ukey[1] == "T" and ukey[-1][0] == "mmff" else None}
-                self.unit_captures += len(missing)
-                while len(self._units) > self.max_cached_units:
-                    L.pd_graph_destroy(self._units.pop(next(iter(self._units)))["exec"])
+            fresh = sampling.run_units(self, units, use_graph, PIPELINED_CAPTURE)
+        if use_graph and not (entry and entry["exec"]):
+            terms = relaxer.terms if relaxer.kind == "device" else None    # (a graph keeps the tables it captured alive, as a unit)
             if entry is None:
-                entry = self._graphs[key] = {"exec": None, "terms": relaxer.terms if relaxer.kind == "device" else None}
+                self._graphs[key] = {"exec": None, "terms": terms}
             else:
                 # the second call of the same schedule on the same shape: the whole N-step loop as ONE graph from here on
                 # (recorded without a device synchronisation while the GPU executes the units launched above: a synchronising capture
                 #  stalled every stream of the device - the other replica of a StreamPool too: two systems at a time fell from 3.1 to 2.7
                 #  ligands/s when the promotion landed in the measured region)
-                entry["exec"] = capture(segments, sync=not PIPELINED_CAPTURE)
-                entry["terms"] = relaxer.terms if relaxer.kind == "device" else None      # the tables THIS capture recorded
+                segments = [[]]
+                for _, fn, after, _ in units:
+                    segments[-1].append(fn)
+                    if after is not None:
+                        segments.append([])
+                entry["exec"] = sampling.record(self, segments, sync=not PIPELINED_CAPTURE)
+                entry["terms"] = terms                                     # the tables THIS capture recorded
                 self.whole_captures += 1
             while len(self._graphs) > self.max_cached_graphs:
                 old = self._graphs.pop(next(iter(self._graphs)))
                 for ex in old["exec"] or ():
                     L.pd_graph_destroy(ex)
-        out = x_a[:, :A_real].clone()
-        # Finite check: ALWAYS on the first call of a (shape, schedule, weights version) - the eager pass that precedes a graph capture,
-        # and every eager call - and on every call with PD_CHECK_FINITE=1 (one tiny reduction + a host sync; replays stay sync-free).
-        # A violated magnitude bound (weights changed behind the engine's back through `.data`, a caller-supplied bound that does not
-        # hold) overflows the fp16 operand format to inf / NaN: that must be an exception, not a pose.
-        if (_CHECK_FINITE or fresh) and not bool(torch.isfinite(out).all()):
-            if use_graph:
-                self._drop_graphs()          # the loop captured from this pass would replay the same overflow
-            raise FloatingPointError("sample_diffusion produced non-finite coordinates: an fp16-format operand bound was violated "
-                                     "(rebuild the engine after changing weights; ops.F16_GEMM / F16_ATTN = False to confirm)")
+        out = slot.x_a[:, :A_real].clone()
+        self._check_finite([out], fresh, use_graph, "sample_diffusion")
         if return_conditioning:
             return out, tuple(t.clone() for t in cond_out)
         return out
@@ -607,28 +415,6 @@ class PhysDock(nn.Module):
             b["_tok_start"] = torch.cat([b["_tok_start"], b["_tok_start"][-1:].expand(pt)]).contiguous()
             out.append(b)
         return out
-
-    def _capture_lists(self, fn_lists):
-        """record (not run) each launch list as one hipGraph (as sample_diffusion's capture, with device synchronisation)"""
-        import time as _time
-        L = ops._lib.init()
-        with _CAPTURE_LOCK:
-            torch.cuda.synchronize()
-            t_cap = _time.perf_counter()
-            execs = []
-            cap = self._capture_stream if getattr(self, "_capture_stream", None) is not None else torch.cuda.Stream()
-            self._capture_stream = cap
-            with torch.cuda.stream(cap):
-                for fns in fn_lists:
-                    ops.check(L.pd_graph_begin(ops.stream()), "graph_begin")
-                    for fn, arg in fns:
-                        fn(*arg)
-                    ex = C.c_void_p()
-                    ops.check(L.pd_graph_end(ops.stream(), C.byref(ex)), "graph_end")
-                    execs.append(ex)
-            torch.cuda.synchronize()
-            self.last_capture_ms = 1e3 * (_time.perf_counter() - t_cap)
-        return execs
 
     @torch.no_grad()
     def sample_diffusion_many(self, batches, num_sample=5, steps=200, gamma_0=0.8, gamma_min=1.0, noise_scale_lambda=1.003,
@@ -687,13 +473,11 @@ class PhysDock(nn.Module):
         if eng.ws.nbytes() > self.workspace_limit_bytes:
             self.release_workspace()
         bats = self._pad_to_group([self._prepare_batch(b) for b in batches])
-        L = ops._lib.init()
         ws = eng.ws
         B = num_sample
         A, T = bats[0]["ref_pos"].shape[0], bats[0]["target_feat"].shape[0]
         Ars = [int(b["_A_real"]) for b in bats]
         Trs = [int(b["_T_real"]) for b in bats]
-        sp = ops.stream()
         if B <= 0:
             outs = [torch.empty(0, ar, 3, device=device) for ar in Ars]
             return (outs, [None] * G) if return_conditioning else outs
@@ -701,15 +485,13 @@ class PhysDock(nn.Module):
         plans = []
         for g in range(G):
             sig, plan = self._step_plan(steps, gamma_0, gamma_min, step_scale_eta, etas[g], facs[g], align_ref_pos,
-                                        karras_noise_schedule_power)
-            for p in plan:
-                p["mmff"] = bool(p["mmff"] and not p["align"] and relaxers[g].kind != "none")
+                                        karras_noise_schedule_power, relaxes=relaxers[g].kind != "none")
             plans.append(plan)
-        plan0 = plans[0]
+        sched = sampling.sched_id(steps, sig, gamma_0, gamma_min, karras_noise_schedule_power)
 
         # ---- conditioning per system (the trunk's outputs are shape-keyed workspace buffers: each is consumed before the next runs)
         tau = ws.get("tau", steps)
-        tau.copy_(torch.tensor([p["tau"] for p in plan0], dtype=torch.float32))
+        tau.copy_(torch.tensor([p["tau"] for p in plans[0]], dtype=torch.float32))
         memo = {}
         cond_out = [None] * G
 
@@ -727,27 +509,17 @@ class PhysDock(nn.Module):
                 if return_conditioning:
                     cond_out[g] = tuple(t.clone() for t in c)
             return memo[g]
-        ck = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min))
-        if _BOUND_CHECK and ops.F16_GEMM and ops.SPLIT_GEMM and ck not in eng._bounds_checked:
-            # the once-per-(weights, schedule) check of sample_diffusion, on the first system
-            if ck in eng._bounds_failed:
-                raise eng._bounds_failed[ck]
+
+        def check_first():                        # the once-per-(weights, schedule) check of sample_diffusion, on the first system
             a0, ap0, s0, z0 = cond_of(0)
             prep0 = eng.prepare_dit(a0, ap0, s0, z0, bats[0], tau, B=B)
-            try:
-                switched = eng.check_dit_bounds(bats[0], a0, s0, prep0, plan0, B, float(self.sigma_data))
-            except FloatingPointError as e:
-                eng._bounds_failed[ck] = e
-                raise
-            eng._bounds_checked.add(ck)
-            if switched:
-                self._drop_graphs()
+            return eng.check_dit_bounds(bats[0], a0, s0, prep0, plans[0], B, float(self.sigma_data))
+        self._check_bounds_once(eng, sched, check_first)
         prep = eng.prepare_dit_many(cond_of, bats, tau, B)
         memo.clear()
         a_g, s_g = prep["a"], prep["s"]
 
-        # ---- the group descriptor and every per-system input of the loop, staged in shape-keyed workspace buffers (graphs replay
-        #      raw addresses)
+        # ---- the group descriptor and the denoiser's per-system inputs, staged like the loop's own (sampling.py)
         def stacked(name, ts, dtype=None):
             buf = ws.get("grp:" + name, G, *ts[0].shape, dtype=dtype or ts[0].dtype)
             for g, t in enumerate(ts):
@@ -763,148 +535,19 @@ class PhysDock(nn.Module):
         gbatch = {"_A_real": max(Ars), "_T_real": max(Trs), "_pool_tpb": 0 if min(tpbs) <= 0 else min(tpbs),
                   "_tok_start": tok_start, "atom_id_to_token_id": a2t}
         grp = {"G": G, "B": B, "nk_atom": nk_a, "nk_token": nk_t}
-        lig_ws = []
-        for g, b in enumerate(bats):
-            lf = b["is_ligand"][b["atom_id_to_token_id"]].clone()
-            lf[Ars[g]:] = 0
-            lig_ws.append(b["a_mask"] * lf)
-        lig_w = stacked("lig_w", lig_ws)
-        x_a = ws.get("grp:x_a", G * B, A, 3)
-        x_hat = ws.get("grp:x_hat", G * B, A, 3)
-        x_den = ws.get("grp:x_den", G * B, A, 3)
-        x_proj = ws.get("grp:x_proj", G * B, A, 3)
-        any_align = [any(p["align"] for p in pl) for pl in plans]
-        any_mmff = [any(p["mmff"] for p in pl) for pl in plans]
-        bref = ws.get("grp:bref", G * B, A, 3) if any(any_align) else None
-        x_ref = ws.get("grp:x_ref", G * B, A, 3) if any(any_mmff) else None
-        phys = []                                 # per system: lig_idx, poses, ref_dist, tm_eps, n_lig, n_conf, mmff tables / scratch
+        loop = sampling.StepLoop(eng, "grp:", plans, B, A, sig[0], noise_scale_lambda, mmff_iters, noise_mode)
         for g in range(G):
-            d = {"poses": None, "n_lig": 0, "n_conf": 0}
-            if (any_align[g] and poses_in[g] is not None) or any_mmff[g]:
-                li = torch.nonzero(lig_ws[g] > 0).flatten().to(torch.int32)
-                d["n_lig"] = int(li.numel())
-                d["lig_idx"] = ws.get(f"grp{g}:lig_idx", *li.shape, dtype=li.dtype)
-                d["lig_idx"].copy_(li)
-            if any_align[g] and poses_in[g] is not None and poses_in[g].shape[1] == d["n_lig"]:
-                pz = poses_in[g].to(device).float()
-                d["poses"] = ws.get(f"grp{g}:poses", *pz.shape)
-                d["poses"].copy_(pz)
-                d["n_conf"] = n_conf = pz.shape[0]
-                d["ref_dist"] = ws.get(f"grp{g}:ref_dist", n_conf, d["n_lig"], d["n_lig"])
-                d["tm_eps"] = ws.get(f"grp{g}:tm_eps", B, n_conf)
-                ops.check(L.pd_pose_dist(ops.ptr(d["poses"]), ops.ptr(d["ref_dist"]), n_conf, d["n_lig"], sp), "pose_dist")
-            if any_mmff[g]:
-                if d["n_lig"] == 0:
-                    raise ValueError(f"ref_mol given but system {g}'s crop has no ligand atoms")
-                d["mm"] = relaxers[g].terms.device_tables(device, d["n_lig"])
-                d["mm_ws"] = ws.get(f"grp{g}:mmff_ws", relaxers[g].terms.workspace_numel(B), dtype=torch.float64)
-            phys.append(d)
+            loop.add_slot(f"grp{g}:", f"system {g}'s crop", bats[g], a_mask[g], ref_pos[g], plans[g], relaxers[g], poses_in[g],
+                          noises_[g], seeds_[g], offs[g])
 
-        # ---- random numbers: per system, exactly the draws of its own sample_diffusion call
-        n_noisy = sum(p["noisy"] for p in plan0)
-        k_noisy = [sum(q["noisy"] for q in plan0[:i]) for i in range(steps)]
-        if noise_mode:
-            n_init = ws.get("grp:n_init", G * B, A, 3, zero=True)
-            n_rot = ws.get("grp:n_rot", G, steps, 4, B)
-            n_tr = ws.get("grp:n_trans", G, steps, B, 3)
-            n_dif = ws.get("grp:n_diffuse", G, max(n_noisy, 1), B, A, 3, zero=True)
-            for g, nz in enumerate(noises_):
-                n_init[g * B:(g + 1) * B, :Ars[g]].copy_(nz["init"])
-                n_rot[g].copy_(nz["rot_u"])
-                n_tr[g].copy_(nz["trans"])
-                if n_noisy:
-                    n_dif[g, :n_noisy, :, :Ars[g]].copy_(nz["diffuse"])
-        else:
-            seed_buf = ws.get("grp:seed", G, dtype=torch.int64)
-            seed_buf.copy_(torch.tensor(seeds_, dtype=torch.int64))
-        xo = [g * B * A * 3 for g in range(G)]
-
-        def step_head(i):
-            p = plan0[i]
-            sp_ = ops.stream()
-            for g in range(G):
-                if i == 0 and any_align[g]:
-                    bref[g * B:(g + 1) * B].copy_(ref_pos[g][None].expand(B, A, 3))
-                if noise_mode:
-                    ru, tr = off(n_rot, (g * steps + i) * 4 * B), off(n_tr, (g * steps + i) * B * 3)
-                    nz = off(n_dif, ((g * max(n_noisy, 1) + k_noisy[i]) * B) * A * 3) if p["noisy"] else None
-                    sd_ptr = None
-                    src, x_scale = (off(n_init, xo[g]), float(sig[0])) if i == 0 else (off(x_a, xo[g]), 1.0)
-                else:
-                    ru = tr = nz = None
-                    sd_ptr = seed_buf.data_ptr() + 8 * g
-                    src, x_scale = off(x_a, xo[g]), 1.0
-                    if i == 0:
-                        ops.check(L.pd_init_noise(off(x_a, xo[g]), sd_ptr, offs[g], float(sig[0]), B, A, sp_), "init_noise")
-                ops.check(L.pd_augment(src, x_scale, off(a_mask, g * A), ru, tr, nz, float(noise_scale_lambda),
-                                       p["sdev"], sd_ptr, i, offs[g], off(x_hat, xo[g]), B, A, sp_), "augment")
-            eng.af3_dit(gbatch, x_hat, x_den, a_g, s_g, prep, G * B, p, row=i, grp=grp)
-
-        def step_tail(i, g):
-            p = plans[g][i]
-            d = phys[g]
-            sp_ = ops.stream()
-            xd, xh, xp, xa = off(x_den, xo[g]), off(x_hat, xo[g]), off(x_proj, xo[g]), off(x_a, xo[g])
-            lw = off(lig_w, g * A)
-            if p["align"]:
-                if d["poses"] is not None:
-                    ops.check(L.pd_template_match(xd, ops.ptr(d["lig_idx"]), ops.ptr(d["ref_dist"]), ops.ptr(d["poses"]),
-                                                  off(bref, xo[g]), ops.ptr(d["tm_eps"]), None, B, A, d["n_lig"], d["n_conf"], sp_),
-                              "template_match")
-                target = off(bref, xo[g])
-            elif p["mmff"]:
-                relaxers[g].terms.launch_relax(d["mm"], x_den[g * B:(g + 1) * B], d["lig_idx"], x_ref[g * B:(g + 1) * B], d["mm_ws"],
-                                               B, A, int(mmff_iters), sp_)
-                target = off(x_ref, xo[g])
-            else:
-                ops.check(L.pd_euler(xh, xd, None, None, p["t_hat"], p["eta"], p["dt"], xa, B, A, sp_), "euler")
-                return
-            ops.check(L.pd_kabsch_align(xd, off(a_mask, g * A), target, A * 3, lw, xp, B, A, sp_), "kabsch")
-            ops.check(L.pd_euler(xh, xd, xp, lw, p["t_hat"], p["eta"], p["dt"], xa, B, A, sp_), "euler")
-
-        # ---- the loop as units (sample_diffusion): one head per step for the whole group, one tail per step and system slot
-        sched_id = (steps, float(sig[0]), float(sig[-2]), float(gamma_0), float(gamma_min), float(karras_noise_schedule_power))
-        common = ("many", G, B, A, T, tuple(Ars), tuple(Trs), gbatch["_pool_tpb"], sched_id, noise_mode, float(noise_scale_lambda),
+        def denoise(i):
+            eng.af3_dit(gbatch, loop.x_hat, loop.x_den, a_g, s_g, prep, G * B, plans[0][i], row=i, grp=grp)
+        # one head per step for the whole group, one tail per step and slot; recorded behind the loop (not pipelined)
+        common = ("many", G, B, A, T, tuple(Ars), tuple(Trs), gbatch["_pool_tpb"], sched, noise_mode, float(noise_scale_lambda),
                   tuple(offs))
-        units = []
-        for i, p in enumerate(plan0):
-            units.append(((common, "H", i, p["noisy"], p["sdev"], p["t_hat"], tuple(i == 0 and al for al in any_align)),
-                          [(step_head, (i,))], None))
-            for g in range(G):
-                q, r = plans[g][i], relaxers[g]
-                pool_sig = phys[g]["poses"] is not None and (phys[g]["n_conf"], phys[g]["n_lig"])
-                relax_sig = (r.kind, r.kind == "device" and r.terms.signature(), int(mmff_iters), phys[g]["n_lig"])
-                kind = ("align", pool_sig) if q["align"] else (("mmff", relax_sig) if q["mmff"] else ("plain",))
-                units.append(((common, "T", g, i, q["t_hat"], q["eta"], q["dt"], kind), [(step_tail, (i, g))],
-                              r.terms if q["mmff"] else None))
-        fresh = not use_graph
-        missing = []
-        for ukey, fns, terms in units:
-            u = self._units.get(ukey) if use_graph else None
-            if u is not None:
-                self._units[ukey] = self._units.pop(ukey)          # LRU order
-                ops.check(L.pd_graph_launch(u["exec"], sp), "graph_launch")
-            else:
-                fresh = True
-                for fn, arg in fns:
-                    fn(*arg)
-                if use_graph:
-                    missing.append((ukey, fns, terms))
-        self.last_unit_misses = len(missing)
-        self.last_head_misses = sum(1 for k, _, _ in missing if k[1] == "H")
-        if missing:
-            # (a unit keeps the MMFF table object whose device tables it captured alive, as in sample_diffusion)
-            for (ukey, _, terms), ex in zip(missing, self._capture_lists([fns for _, fns, _ in missing])):
-                self._units[ukey] = {"exec": ex, "terms": terms}
-            self.unit_captures += len(missing)
-            while len(self._units) > self.max_cached_units:
-                L.pd_graph_destroy(self._units.pop(next(iter(self._units)))["exec"])
-        outs = [x_a[g * B:(g + 1) * B, :Ars[g]].clone() for g in range(G)]
-        if (_CHECK_FINITE or fresh) and not all(bool(torch.isfinite(o).all()) for o in outs):
-            if use_graph:
-                self._drop_graphs()
-            raise FloatingPointError("sample_diffusion_many produced non-finite coordinates: an fp16-format operand bound was violated "
-                                     "(rebuild the engine after changing weights; ops.F16_GEMM / F16_ATTN = False to confirm)")
+        fresh = sampling.run_units(self, loop.units(common, denoise), use_graph, False)
+        outs = [s.x_a[:, :Ars[s.g]].clone() for s in loop.slots]
+        self._check_finite(outs, fresh, use_graph, "sample_diffusion_many")
         if return_conditioning:
             return outs, cond_out
         return outs

@@ -93,7 +93,7 @@ class Relaxer:
 
 
 #: per-molecule memo of the device tables built from an RDKit molecule (the build reads ~10^3 RDKit getters and runs a
-#: self-check on the GPU; the step-loop graph cache keys on the table's content hash, see model.py)
+#: self-check on the GPU; the step-loop graph cache keys on the table's content hash, see sampling.py)
 _TERMS_MEMO: "dict[int, tuple]" = {}
 _TERMS_MEMO_MAX = 32
 

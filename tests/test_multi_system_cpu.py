@@ -86,3 +86,37 @@ def test_grouped_attention_abi_fields():
     for s in ("pd_precond_g", "pd_segment_pool_g", "pd_unpool_add_g", "pd_downscale_pool_g"):
         assert s in decl and hasattr(L, s), s
     assert L.pd_abi_version() == _lib.ABI_VERSION
+
+
+def test_tail_keys_are_the_same_for_one_system_and_for_slot_0_of_a_group():
+    """sampling.tail_key / tail_kind: the single-system loop and slot 0 of a group key a plan entry alike apart from `common`
+    (a group's starts with "many" and carries the group's fields); a device relaxer's table signature, mmff_iters, the ligand
+    atom count and the pool's size are part of the key"""
+    from types import SimpleNamespace as NS
+    from physdock_amd import sampling
+    from physdock_amd.configs import small_config
+    m = PhysDock(small_config())
+    sig, plan = m._step_plan(6, 0.8, 1.0, 1.5, 1.0, 6.0, True, 1000)
+    assert [p["align"] for p in plan] == [True] * 3 + [False] * 3 and [p["mmff"] for p in plan] == [False] * 3 + [True] * 3
+    _, bare = m._step_plan(6, 0.8, 1.0, 1.5, 1.0, 6.0, True, 1000, relaxes=False)
+    assert not any(p["mmff"] for p in bare)                  # no molecule: the relaxation branch is unreachable
+
+    def slot(sig_="abc", n_lig=6, n_conf=4, kind="device", poses=True, plan=plan):
+        terms = NS(signature=lambda: (n_lig, sig_))
+        return NS(g=0, plan=plan, relaxer=NS(kind=kind, terms=terms), n_lig=n_lig, n_conf=n_conf, poses=object() if poses else None)
+    sched = sampling.sched_id(6, sig, 0.8, 1.0, 1000)
+    one = (3, 96, 24, 96, 24, sched, False, 1.003, 2)
+    many = ("many", 1, 3, 96, 24, (96,), (24,), 8, sched, False, 1.003, (2,))
+    for i in range(6):
+        k1, kg = sampling.tail_key(one, slot(), i, 5), sampling.tail_key(many, slot(), i, 5)
+        assert k1[0] is one and kg[0] is many and kg[0][0] == "many" and k1[1] == kg[1] == "T"
+        assert k1[1:] == kg[1:]
+    assert sampling.tail_kind(plan[0], slot(), 5) == ("align", (4, 6))
+    assert sampling.tail_kind(plan[0], slot(poses=False), 5) == ("align", False)
+    assert sampling.tail_kind(plan[5], slot(), 5) == ("mmff", ("device", (6, "abc"), 5, 6))
+    assert sampling.tail_kind(bare[5], slot(kind="none"), 5) == ("plain",)
+    k = sampling.tail_key(one, slot(), 5, 5)
+    assert k != sampling.tail_key(one, slot(sig_="abd"), 5, 5)         # another table
+    assert k != sampling.tail_key(one, slot(), 5, 6)                   # another iteration count
+    assert k != sampling.tail_key(one, slot(kind="host"), 5, 5)
+    assert sampling.tail_key(one, slot(), 0, 5) != sampling.tail_key(one, slot(n_conf=5), 0, 5)

@@ -198,14 +198,27 @@ def _noise(B, steps, A, seed):
             "trans": torch.randn(steps, B, 3, generator=g), "diffuse": torch.randn(n_noisy, B, A, 3, generator=g)}
 
 
-@pytest.mark.parametrize("mode", ["seeded", "noise"])
+@pytest.mark.parametrize("mode", ["seeded", "noise", "templates", "mmff"])
 def test_one_system_equals_sample_diffusion(small, mode):
-    from physdock_amd.synthetic import small_batch
+    """templates / mmff: sigma = 2560, 310, 37.4, 4.50, 0.54, 0.064 against a threshold factor 6.0 gives 3 align steps and 3
+    plain (templates) or device-relaxation (mmff) steps: the shared tail runs all three branches from both entry points"""
+    from physdock_amd import mmff
+    from physdock_amd.synthetic import reference_conformers, small_batch
     model, cfg, P = small
-    b = to_dev(small_batch(0))
+    raw = small_batch(0)
+    b = to_dev(raw)
     A = b["ref_pos"].shape[0]
     kw = dict(num_sample=3, steps=6, karras_noise_schedule_power=1000)
-    if mode == "noise":
+    if mode in ("templates", "mmff"):
+        kw.update(align_ref_pos=True, mmff_gamma_0_factor=6.0)
+        pool = reference_conformers(raw, n_conf=4)
+        lig = raw["is_ligand"][raw["atom_id_to_token_id"]].bool()
+        mol = mmff.synthetic_terms(int(lig.sum()), 5, coords=raw["x_gt"][lig].double().numpy())[0] if mode == "mmff" else None
+        ref = model.sample_diffusion(b, seed=5, sample_offset=2, ref_mol_poses=pool, ref_mol=mol, **kw)
+        for _ in range(2):
+            (x,) = model.sample_diffusion_many([b], seeds=[5], sample_offsets=[2], ref_mol_poses=[pool], ref_mol=[mol], **kw)
+            assert torch.equal(x, ref)
+    elif mode == "noise":
         nz = _noise(3, 6, A, 11)
         ref = model.sample_diffusion(b, noise=nz, **kw)
         for _ in range(2):                               # first call (eager + capture), then the replay
