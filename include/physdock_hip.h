@@ -498,6 +498,30 @@ int pd_lddt_pli_counts(const float* x, const int* lig_idx, const int* contact_st
                        float thr3, int* counts, int P, int A, int L, int n_contacts, int n_cand, void* stream);
 int pd_lddt_pli_select(const int* counts, const int* contact_start, const int* cand_start, const unsigned short* slot_t,
                        float* lddt, int* conserved, float* per_atom, int* best_perm, int P, int L, int M, int n_cand, void* stream);
+/* Vina-style receptor - ligand interaction score of P poses of one ligand in its receptor and its analytic gradient on the ligand
+ * atoms (vina.hip; ABI 11, additive; the intermolecular part of the AutoDock Vina scoring function, Trott & Olson 2010, heavy atoms
+ * only - the reference has no counterpart on the device, it relaxes through OpenMM on the host, PhysDock/data/relaxation.py).
+ * Tables, built once per system (physdock_amd/scoring.py): lig_idx [L] the ligand's atoms in a pose; type [A] one byte per pose
+ * atom - bits 0 - 3 the radius class (0 C 1.9, 1 N 1.8, 2 O 1.7, 3 P 2.1, 4 S 2.0, 5 F 1.5, 6 Cl 1.8, 7 Br 2.0, 8 I 2.2, 9 and above
+ * 1.2 A), bit 4 hydrophobic, bit 5 hydrogen-bond donor, bit 6 acceptor; rec_mask [A] 1 = the atom counts as receptor (never a
+ * ligand atom); lig_active [L] 0 = the ligand atom takes no part (a hydrogen, a masked atom) and reports zeros.  Per pose p, over
+ * the pairs (active ligand atom i, receptor atom j) with r = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))) < 8 and d = r - (R_i + R_j):
+ *   atom_terms[p][i][t]  atom i's sums of gauss1 exp(-(d/0.5)^2), gauss2 exp(-((d-3)/2)^2), repulsion d^2 (d < 0), hydrophobic
+ *                        (both bit 4: 1 for d <= 0.5, 1.5 - d below 1.5) and hbond (a donor and an acceptor: 1 for d <= -0.7, -d/0.7
+ *                        below 0)
+ *   terms[p][t]          their sums over the ligand atoms in ascending order
+ *   inter[p]             -0.0356 gauss1 - 0.00516 gauss2 + 0.840 repulsion - 0.0351 hydrophobic - 0.587 hbond  (kcal/mol)
+ *   score[p]             inter[p] / (1 + 0.0585 n_rot)
+ *   per_atom[p][i]       the same weighted sum of atom_terms[p][i]
+ *   forces[p][i][3]      -d inter[p] / d x_i (not scaled by the n_rot factor; a pair with r == 0 contributes nothing); may be NULL
+ * Two launches, no atomics, no workspace beyond the outputs, no allocation, no synchronisation.  Every sum runs in a fixed order
+ * inside one pose: results are bit-identical from launch to launch and independent of P and of a pose's place among the P.
+ * float and int pointers must be 4-byte aligned and n_rot >= 0 (else PD_ERR_ARG); L <= 1024, A <= 2^22, P <= 65535 (else
+ * PD_ERR_UNSUPPORTED).                                                                                                        */
+#define PD_VINA_TERMS 5
+int pd_vina_score(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
+                  const unsigned char* lig_active, float n_rot, float* atom_terms, float* terms, float* inter, float* score,
+                  float* per_atom, float* forces, int P, int A, int L, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

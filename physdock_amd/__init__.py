@@ -21,3 +21,4 @@ from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_cl
 from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-corrected ligand RMSD for the ranking step; csrc/sym_rmsd.hip)
 from .validity import PoseValidity  # noqa: F401  (PoseBusters-style geometry checks of every pose; csrc/validity.hip)
 from .lddt_pli import LddtPli  # noqa: F401  (symmetry-aware lDDT-PLI of every pose against the ground truth; csrc/lddt_pli.hip)
+from .scoring import VinaScore  # noqa: F401  (Vina-style interaction score and forces of every pose; csrc/vina.hip)

@@ -245,6 +245,7 @@ def _declare(L):
     sig("pd_pose_validity", p, p, p, p, p, p, p, p, p, p, p, ValidityThresholds, p, p, p, p, i, i, i, i, i, i, p)
     sig("pd_lddt_pli_counts", p, p, p, p, p, p, p, f, f, f, f, p, i, i, i, i, i, p)         # ABI 11, additive (lddt_pli.hip)
     sig("pd_lddt_pli_select", p, p, p, p, p, p, p, p, i, i, i, i, p)
+    sig("pd_vina_score", p, p, p, p, p, f, p, p, p, p, p, p, i, i, i, p)                     # ABI 11, additive (vina.hip)
 
 
 def ptr(t):

@@ -107,13 +107,24 @@ def score_validity(validity, aligned, out) -> dict:
     return res
 
 
+def score_vina(vina, aligned, out) -> dict:
+    """redock(vina=): {"vina": VinaScore.score of the kept poses, "order_vina": their ids best first (lowest score)} and, when their
+    validity was checked too, "order_vina_valid": the same order with the valid poses in front"""
+    from .ranking import rank_by_score
+    res = {"vina": vina.score(aligned)}
+    res["order_vina"] = rank_by_score(res["vina"])
+    if "validity" in out:
+        res["order_vina_valid"] = rank_by_score(res["vina"], valid=out["validity"]["valid"])
+    return res
+
+
 def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses: Optional[torch.Tensor] = None,
            accept_fn: Optional[Callable[[torch.Tensor], bool]] = None, chirality=None, physics_correction: bool = False,
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
-           ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None) -> dict:
+           ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -134,7 +145,10 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     valid poses first).  With `validity_filter=True` as well a pose that fails a check is rejected where and when the chirality test
     rejects (`physics_correction`, before `accept_fn`; the two masks share one read per round) and each round's log entry gains
     `invalid`, the number of poses that failed.  Nothing else changes.
-    `lddt_pli` (an `lddt_pli.LddtPli` of the system): `ranking` gains the lDDT-PLI of the kept poses (`rank_poses(..., lddt_pli=)`)."""
+    `lddt_pli` (an `lddt_pli.LddtPli` of the system): `ranking` gains the lDDT-PLI of the kept poses (`rank_poses(..., lddt_pli=)`).
+    `vina` (a `scoring.VinaScore` of the system): the result gains `vina` = its `score` of the returned `poses` and `order_vina` =
+    `ranking.rank_by_score` of it (lowest score first), and together with `validity=` also `order_vina_valid` (valid poses first).
+    Nothing else changes."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -238,6 +252,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
     if validity is not None:
         out.update(score_validity(validity, aligned, out))
+    if vina is not None:
+        out.update(score_vina(vina, aligned, out))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -275,7 +291,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -366,7 +382,7 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False, lddt_pli=None):
+                 validity_filter=False, lddt_pli=None, vina=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -392,6 +408,7 @@ class _RedockState:
         self.ligand_symmetry = ligand_symmetry
         self.validity, self.validity_filter = validity, bool(validity_filter)
         self.lddt_pli = lddt_pli
+        self.vina = vina
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -468,6 +485,8 @@ class _RedockState:
             out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
         if self.validity is not None:
             out.update(score_validity(self.validity, aligned, out))
+        if self.vina is not None:
+            out.update(score_vina(self.vina, aligned, out))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)

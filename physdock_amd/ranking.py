@@ -122,3 +122,19 @@ def rank_by_confidence(scores, valid=None) -> torch.Tensor:
     if v.dtype != torch.bool or v.shape != rc.shape:
         raise ValueError(f"valid must be a bool mask over the {rc.shape[0]} poses, got {v.dtype} {tuple(valid.shape)}")
     return order[torch.sort((~v.to(order.device))[order].to(torch.uint8), stable=True).indices]
+
+
+def rank_by_score(scores, valid=None) -> torch.Tensor:
+    """Pose ids, best first, by the interaction score of `scoring.VinaScore.score` (its dict, or the `score` tensor itself):
+    ascending score (kcal/mol, lower is better), ties by ascending pose id.  LongTensor [P] on the scores' device: one stable sort
+    there, nothing is read back.
+    `valid` (bool [P], e.g. `PoseValidity.check(...)["valid"]`): the valid poses come first, and the valid and the invalid ones
+    each keep that order among themselves (one more stable sort on the device), as in `rank_by_confidence`."""
+    sc = (scores["score"] if isinstance(scores, dict) else scores).reshape(-1)
+    order = torch.sort(sc, stable=True).indices                              # stable: equal scores keep ascending pose id
+    if valid is None:
+        return order
+    v = valid.reshape(-1)
+    if v.dtype != torch.bool or v.shape != sc.shape:
+        raise ValueError(f"valid must be a bool mask over the {sc.shape[0]} poses, got {v.dtype} {tuple(valid.shape)}")
+    return order[torch.sort((~v.to(order.device))[order].to(torch.uint8), stable=True).indices]
