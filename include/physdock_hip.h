@@ -522,6 +522,42 @@ int pd_lddt_pli_select(const int* counts, const int* contact_start, const int* c
 int pd_vina_score(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
                   const unsigned char* lig_active, float n_rot, float* atom_terms, float* terms, float* inter, float* score,
                   float* per_atom, float* forces, int P, int A, int L, void* stream);
+/* Protein - ligand interaction fingerprint of P poses of one ligand in its receptor: which residues does a pose touch, and how?
+ * (plif.hip; ABI 11, additive; per-residue fingerprints in the manner of PLIP and ProLIF, heavy atoms only - the reference has no
+ * counterpart.)  Tables, built once per system (physdock_amd/interactions.py): lig_idx [L] the ligand's atoms in a pose;
+ * lig_active [L] 0 = the ligand atom takes no part (a hydrogen) and reports 0; type [A] the type byte of pd_vina_score (bit 4
+ * hydrophobic, bit 5 donor, bit 6 acceptor; bits 0 - 3 are not looked at); charge [A] bit 0 cation, bit 1 anion; the receptor
+ * atoms sorted by residue: res_start [R + 1] ascending from 0, res_atom [N] with N = res_start[R] <= A (distinct pose atoms, never
+ * a ligand atom; the atoms of residue s are res_atom[res_start[s] .. res_start[s + 1]), a residue may own none).  thresholds: FOUR
+ * floats ON THE HOST, read by the call and passed on as values: contact, hydrophobic, hbond, ionic (A).  Per pose p, over the pairs
+ * (active ligand atom i, receptor atom j) with r = sqrtf(fmaf(dz, dz, fmaf(dy, dy, dx * dx))), bit k of a byte = kind k:
+ *   0 contact         r < thresholds[0]                                      3 hbond_acceptor  i acceptor, j donor,  r < thresholds[2]
+ *   1 hydrophobic     both hydrophobic,    r < thresholds[1]                 4 cationic        i cation,   j anion,  r < thresholds[3]
+ *   2 hbond_donor     i donor, j acceptor, r < thresholds[2]                 5 anionic         i anion,    j cation, r < thresholds[3]
+ *   bits[p][s]          OR over the pairs whose receptor atom lies in residue s (bits 6 and 7 are 0)
+ *   ligand_bits[p][i]   OR over the receptor atoms for ligand atom i
+ *   min_dist[p][s]      the exact minimum of r over the residue's pairs; +inf without receptor atom or without active ligand atom
+ *   counts[p][k]        the number of residues whose byte has bit k
+ * ws_bits [P * N] bytes and ws_min [P * N] floats are the workspace (may be NULL when N == 0).  Three launches, no atomics, no
+ * allocation, no synchronisation; OR, minimum and integer sums only: bit-identical from launch to launch, independent of P and
+ * of a pose's place among the P.  float and int pointers must be 4-byte aligned, sizes positive (N >= 0, N <= A), thresholds
+ * finite and not negative (else PD_ERR_ARG); L <= 1024, A <= 2^22, P <= 65535, R <= A (else PD_ERR_UNSUPPORTED).  A rejected
+ * call writes nothing.                                                                                                         */
+#define PD_PLIF_KINDS 6
+#define PD_PLIF_THRESHOLDS 4
+int pd_plif_fingerprint(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* charge,
+                        const unsigned char* lig_active, const int* res_start, const int* res_atom, const float* thresholds,
+                        unsigned char* ws_bits, float* ws_min, unsigned char* bits, unsigned char* ligand_bits, float* min_dist,
+                        int* counts, int P, int A, int L, int R, int N, void* stream);
+/* bits [P][R] against one reference row ref_bits [R] (it may be a row of bits), both masked with kind_mask (bit k = kind k counts;
+ * 0 .. 63): shared[p] = popcount(bits & ref & mask), n_pose[p] = popcount(bits & mask), n_ref[0] = popcount(ref & mask) (int32,
+ * summed over the residues), recovery[p] = shared / n_ref (1 where n_ref == 0), tanimoto[p] = shared / (n_pose + n_ref - shared)
+ * (1 where the union is empty) - each ONE fp32 division of two integers (exactly representable up to 2^24).  One block per pose. */
+int pd_plif_compare(const unsigned char* bits, const unsigned char* ref_bits, int kind_mask, int* shared, int* n_pose, int* n_ref,
+                    float* recovery, float* tanimoto, int P, int R, void* stream);
+/* tanimoto [P][P]: the same Tanimoto between every two rows of bits [P][R]; symmetric, the diagonal exactly 1; row p equals
+ * pd_plif_compare against row p bit for bit.  One thread per pair, 16 x 16 pairs per block.  Limits and codes as above.          */
+int pd_plif_pairwise(const unsigned char* bits, int kind_mask, float* tanimoto, int P, int R, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

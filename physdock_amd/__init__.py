@@ -22,3 +22,4 @@ from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-cor
 from .validity import PoseValidity  # noqa: F401  (PoseBusters-style geometry checks of every pose; csrc/validity.hip)
 from .lddt_pli import LddtPli  # noqa: F401  (symmetry-aware lDDT-PLI of every pose against the ground truth; csrc/lddt_pli.hip)
 from .scoring import VinaScore  # noqa: F401  (Vina-style interaction score and forces of every pose; csrc/vina.hip)
+from .interactions import InteractionFingerprint  # noqa: F401  (per-residue interaction fingerprint of every pose; csrc/plif.hip)

@@ -118,13 +118,23 @@ def score_vina(vina, aligned, out) -> dict:
     return res
 
 
+def score_interactions(interactions, aligned, batch) -> dict:
+    """redock(interactions=): {"interactions": InteractionFingerprint.fingerprint of the kept poses} and, when the batch carries the
+    ground truth, "interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
+    res = {"interactions": interactions.fingerprint(aligned)}
+    if "x_gt" in batch:
+        res["interaction_recovery"] = interactions.compare(res["interactions"]["bits"], batch["x_gt"].float())
+    return res
+
+
 def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses: Optional[torch.Tensor] = None,
            accept_fn: Optional[Callable[[torch.Tensor], bool]] = None, chirality=None, physics_correction: bool = False,
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
            mmff_gamma_0_factor_start: float = 6.0, karras_noise_schedule_power: float = 1000, use_pocket: bool = True,
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
-           ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None) -> dict:
+           ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
+           interactions=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -148,7 +158,11 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `lddt_pli` (an `lddt_pli.LddtPli` of the system): `ranking` gains the lDDT-PLI of the kept poses (`rank_poses(..., lddt_pli=)`).
     `vina` (a `scoring.VinaScore` of the system): the result gains `vina` = its `score` of the returned `poses` and `order_vina` =
     `ranking.rank_by_score` of it (lowest score first), and together with `validity=` also `order_vina_valid` (valid poses first).
-    Nothing else changes."""
+    Nothing else changes.
+    `interactions` (an `interactions.InteractionFingerprint` of the system): the result gains `interactions` = its `fingerprint` of
+    the returned `poses` (per-residue and per-ligand-atom interaction bytes, closest distances, counts) and, as the batch carries
+    `x_gt`, `interaction_recovery` = its `compare` of those bits with the ground truth's.  Nothing else changes, with or without
+    `validity=`."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -254,6 +268,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_validity(validity, aligned, out))
     if vina is not None:
         out.update(score_vina(vina, aligned, out))
+    if interactions is not None:
+        out.update(score_interactions(interactions, aligned, batch))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -291,7 +307,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -382,7 +398,7 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False, lddt_pli=None, vina=None):
+                 validity_filter=False, lddt_pli=None, vina=None, interactions=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -409,6 +425,7 @@ class _RedockState:
         self.validity, self.validity_filter = validity, bool(validity_filter)
         self.lddt_pli = lddt_pli
         self.vina = vina
+        self.interactions = interactions
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -487,6 +504,8 @@ class _RedockState:
             out.update(score_validity(self.validity, aligned, out))
         if self.vina is not None:
             out.update(score_vina(self.vina, aligned, out))
+        if self.interactions is not None:
+            out.update(score_interactions(self.interactions, aligned, self.batch))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
