@@ -558,6 +558,39 @@ int pd_plif_compare(const unsigned char* bits, const unsigned char* ref_bits, in
 /* tanimoto [P][P]: the same Tanimoto between every two rows of bits [P][R]; symmetric, the diagonal exactly 1; row p equals
  * pd_plif_compare against row p bit for bit.  One thread per pair, 16 x 16 pairs per block.  Limits and codes as above.          */
 int pd_plif_pairwise(const unsigned char* bits, int kind_mask, float* tanimoto, int P, int R, void* stream);
+/* Ligand burial and interface area of P poses of one ligand in its receptor: solvent-accessible surface area by point counting
+ * (sasa.hip; ABI 11, additive; Shrake & Rupley 1973, HEAVY ATOMS ONLY - absolute areas are not comparable with all-atom tools, and
+ * the default radii and probe have not been validated on real complexes; the reference has no counterpart).  Tables, built once
+ * per system (physdock_amd/surface.py): cls [A] one byte per pose atom - 0 ignored (padding, an atom that does not exist, an
+ * inactive ligand atom), 1 receptor, 2 ligand; radius [A] (A); unit [n_points][3] the golden spiral in fp32 (t = k + 0.5, z = 1 -
+ * 2 t / n, phi = t pi (3 - sqrt 5), u_k = (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), computed in float64); lig_idx [L] the
+ * ligand's atoms in a pose (cls 2 or 0); polar [L] 1 = the ligand atom counts as polar; the receptor atoms (cls 1) sorted by
+ * residue, res_start [R + 1] / res_atom [N] as pd_plif_fingerprint takes them; probe (A) by value.  For pose p and atom i of class
+ * c != 0, with R_i = radius_i + probe: the point p_ik = x_i + R_i u_k (per coordinate fmaf(R_i, u, x_i)) is covered by atom j iff
+ * j != i (by index), cls_j != 0 and fmaf(dz, dz, fmaf(dy, dy, dx * dx)) < R_j * R_j with d = p_ik - x_j; same_k: a covering j has
+ * class c, other_k: one has the other class; n_free[i] = #{k: !same_k}, n_bound[i] = #{k: !same_k && !other_k}, n_buried = n_free -
+ * n_bound; area(m, i) = (float)m * ((12.566370614359172f * (R_i * R_i)) / (float)n_points) in A^2.
+ *   free_points[p][s]      n_free of ligand atom lig_idx[s] (0 for an inactive one)
+ *   buried_points[p][a]    n_buried of every pose atom (0 for an ignored atom and for a receptor atom no ligand atom reaches)
+ *   per_atom[p][s]         area(n_buried) of ligand atom s
+ *   totals[t][p]           PD_SASA_TOTALS rows of P: 0 ligand_free, 1 ligand_bound, 2 ligand_buried (sums of area(n_free), area(n_bound),
+ *                          area(n_buried) over the ligand atoms in ascending order), 3 buried_fraction = buried / free (0 where free
+ *                          is 0), 4 buried_polar, 5 buried_apolar (ligand_buried split by polar), 6 receptor_buried (sum over the
+ *                          receptor atoms in ascending atom order), 7 interface_area = (ligand_buried + receptor_buried) / 2
+ *   residue_buried[p][r]   sum of area(n_buried) over the residue's receptor atoms in the order of its run
+ *   interface_residues[p]  the number of residues with residue_buried > 0
+ * ws_free [P * A] ints is the workspace.  The neighbour list of an atom is walked in pieces of PD_SASA_LIST or more entries: no
+ * input is truncated.  Two launches, no atomics, no allocation, no synchronisation; "any", integer sums and float sums in a fixed
+ * order: bit-identical from launch to launch, independent of P and of a pose's place among the P.  float and int pointers must be
+ * 4-byte aligned, sizes positive (N >= 0, N <= A), probe finite and not negative (else PD_ERR_ARG); n_points <= PD_SASA_MAX_POINTS,
+ * L <= 1024, A <= 2^22, P <= 65535, R <= A (else PD_ERR_UNSUPPORTED).  A rejected call writes nothing.                             */
+#define PD_SASA_MAX_POINTS 1024
+#define PD_SASA_LIST 256
+#define PD_SASA_TOTALS 8
+int pd_buried_surface(const float* x, const unsigned char* cls, const float* radius, const float* unit, const int* lig_idx,
+                      const unsigned char* polar, const int* res_start, const int* res_atom, float probe, int* ws_free,
+                      int* free_points, int* buried_points, float* per_atom, float* totals, float* residue_buried,
+                      int* interface_residues, int P, int A, int L, int R, int N, int n_points, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

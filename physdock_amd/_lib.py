@@ -249,6 +249,7 @@ def _declare(L):
     sig("pd_plif_fingerprint", p, p, p, p, p, p, p, C.POINTER(C.c_float), p, p, p, p, p, p, i, i, i, i, i, p)   # ABI 11, additive (plif.hip)
     sig("pd_plif_compare", p, p, i, p, p, p, p, p, i, i, p)
     sig("pd_plif_pairwise", p, i, p, i, i, p)
+    sig("pd_buried_surface", p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p, i, i, i, i, i, i, p)       # ABI 11, additive (sasa.hip)
 
 
 def ptr(t):
