@@ -522,6 +522,42 @@ int pd_lddt_pli_select(const int* counts, const int* contact_start, const int* c
 int pd_vina_score(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
                   const unsigned char* lig_active, float n_rot, float* atom_terms, float* terms, float* inter, float* score,
                   float* per_atom, float* forces, int P, int A, int L, void* stream);
+/* Local refinement of P poses of one ligand in its rigid receptor, as a rigid body and about its rotatable bonds - the move set of
+ * `vina --local_only` (vina_refine.hip; ABI 11, additive; the device counterpart of the reference's host relaxation through OpenMM,
+ * PhysDock/data/relaxation.py, with another energy).  Tables, built once per system (physdock_amd/refine.py): lig_idx, type,
+ * rec_mask, lig_active as pd_vina_score takes them; rot [T][2] the rotatable bonds (a_k, b_k) as LOCAL ligand indices, b_k on the
+ * moving side; rot_mask [T][ceil(L / 32)] bit i % 32 of word i / 32 of row k = ligand atom i moves with torsion k (b_k does, a_k does
+ * not; hydrogens move with their side); intra_start [L + 1] / intra_atom [2 n_intra]: for every ligand atom the ACTIVE atoms more
+ * than three bonds away from it or in another component (ascending; every pair appears from both of its atoms).  All of it float64:
+ *   E(y)      inter + intra: the pair function of pd_vina_score (five weighted terms of d = r - R_i - R_j, pairs with r < 8, no force
+ *             from a pair at r == 0) over (active ligand atom, receptor atom) and over the intramolecular pairs; no n_rot factor
+ *   move(y,s) s in R^(6+T): for k = 0 .. T-1 rotate the atoms of row k by s[6+k] about the axis through y[a_k] along y[b_k] - y[a_k]
+ *             (Rodrigues, on the coordinates as they stand), then rotate all atoms about their unweighted centroid c by the rotation
+ *             vector s[3:6], then translate by s[0:3]
+ *   ggrad     at s = 0: [0:3] sum_i dE/dy_i, [3:6] sum_i (y_i - c) x dE/dy_i, [6+k] sum_{i in row k} dE/dy_i . (u_k x (y_i - y[a_k]))
+ * pd_vina_refine_energy: energy, inter, intra [P], grad [P][L][3] = dE/dy (zeros for an inactive atom), ggrad [P][6+T] of the poses
+ * as they are; any output may be NULL.  pd_vina_refine: BFGS with the line search of pd_mmff_relax (Numerical Recipes dfpmin /
+ * lnsrch, same constants) in the 6 + T coordinates, the chart re-centred after every accepted step, the direction cut to |xi|_2 <=
+ * max_step (A and radians) before each line search; it stops on max|ggrad| < grad_tol (status 0), after max_iters accepted steps
+ * (1) or when the line search finds no lower point (2).  x_refined [P][A][3] = x with the ligand rows replaced; energy_start, energy
+ * [P] (float64); iterations (accepted steps), evaluations (of E), status [P] (int32); moved [P] (float64): RMSD of the L ligand atoms
+ * between start and end; energy_trace [P][max_iters + 1] (float64, may be NULL): E at the start and after each accepted step, padded
+ * with the last value.  ws: pd_vina_refine_workspace_numel(P, L, T) = P ((6+T)^2 + 3 L) doubles.  One launch, one block per pose, no
+ * atomics, no allocation, no synchronisation; every sum in a fixed order: bit-identical from launch to launch, independent of P and
+ * of a pose's place among the P.  NULL required pointers, misaligned pointers (4 bytes for float / int, 8 for double), sizes < 1,
+ * max_iters < 0, grad_tol < 0, max_step <= 0 or a short workspace: PD_ERR_ARG; L > 1024, T > PD_VINA_REFINE_MAX_TORSIONS, A > 2^22,
+ * P > 65535: PD_ERR_UNSUPPORTED.  A rejected call writes nothing.  tests/vina_refine_ref.py is the written definition.            */
+#define PD_VINA_REFINE_MAX_TORSIONS 58
+int pd_vina_refine_workspace_numel(int P, int L, int T);
+int pd_vina_refine_energy(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
+                          const unsigned char* lig_active, const int* rot, const unsigned* rot_mask, const int* intra_start,
+                          const int* intra_atom, int n_intra, double* energy, double* inter, double* intra, double* grad,
+                          double* ggrad, int P, int A, int L, int T, void* stream);
+int pd_vina_refine(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
+                   const unsigned char* lig_active, const int* rot, const unsigned* rot_mask, const int* intra_start,
+                   const int* intra_atom, int n_intra, int max_iters, double grad_tol, double max_step, double* ws,
+                   long long ws_numel, float* x_refined, double* energy_start, double* energy, int* iterations, int* evaluations,
+                   int* status, double* moved, double* energy_trace, int P, int A, int L, int T, void* stream);
 /* Protein - ligand interaction fingerprint of P poses of one ligand in its receptor: which residues does a pose touch, and how?
  * (plif.hip; ABI 11, additive; per-residue fingerprints in the manner of PLIP and ProLIF, heavy atoms only - the reference has no
  * counterpart.)  Tables, built once per system (physdock_amd/interactions.py): lig_idx [L] the ligand's atoms in a pose;

@@ -246,6 +246,10 @@ def _declare(L):
     sig("pd_lddt_pli_counts", p, p, p, p, p, p, p, f, f, f, f, p, i, i, i, i, i, p)         # ABI 11, additive (lddt_pli.hip)
     sig("pd_lddt_pli_select", p, p, p, p, p, p, p, p, i, i, i, i, p)
     sig("pd_vina_score", p, p, p, p, p, f, p, p, p, p, p, p, i, i, i, p)                     # ABI 11, additive (vina.hip)
+    d = C.c_double
+    sig("pd_vina_refine_workspace_numel", i, i, i)                                           # ABI 11, additive (vina_refine.hip)
+    sig("pd_vina_refine_energy", p, p, p, p, p, p, p, p, p, i, p, p, p, p, p, i, i, i, i, p)
+    sig("pd_vina_refine", p, p, p, p, p, p, p, p, p, i, i, d, d, p, ll, p, p, p, p, p, p, p, p, i, i, i, i, p)
     sig("pd_plif_fingerprint", p, p, p, p, p, p, p, C.POINTER(C.c_float), p, p, p, p, p, p, i, i, i, i, i, p)   # ABI 11, additive (plif.hip)
     sig("pd_plif_compare", p, p, i, p, p, p, p, p, i, i, p)
     sig("pd_plif_pairwise", p, i, p, i, i, p)

@@ -118,6 +118,18 @@ def score_vina(vina, aligned, out) -> dict:
     return res
 
 
+def score_refined(refine, aligned, validity, vina, refine_kwargs=None) -> dict:
+    """redock(refine=): {"refined": VinaRefine.refine of the kept poses} - with `validity=` also refined["validity"], its check of
+    `x_refined`, and with `vina=` "order_vina_refined": the poses' ids by their refined score, best first"""
+    from .ranking import rank_by_score
+    res = {"refined": refine.refine(aligned, **(refine_kwargs or {}))}
+    if validity is not None:
+        res["refined"]["validity"] = validity.check(res["refined"]["x_refined"])
+    if vina is not None:
+        res["order_vina_refined"] = rank_by_score({"score": res["refined"]["score"]})
+    return res
+
+
 def score_interactions(interactions, aligned, batch) -> dict:
     """redock(interactions=): {"interactions": InteractionFingerprint.fingerprint of the kept poses} and, when the batch carries the
     ground truth, "interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
@@ -143,7 +155,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
-           interactions=None, surface=None) -> dict:
+           interactions=None, surface=None, refine=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -175,7 +187,11 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `surface` (a `surface.BuriedSurface` of the system): the result gains `surface` = its `measure` of the returned `poses` (the
     ligand's solvent-accessible area free and in the complex, the buried fraction and its polar / apolar split, the area each residue
     loses to the ligand) and, as the batch carries `x_gt`, `surface_gt` = its `measure` of the ground truth (one pose).  Nothing else
-    changes."""
+    changes.
+    `refine` (a `refine.VinaRefine` of the system): the result gains `refined` = its `refine` of the returned `poses` (rigid-body and
+    torsion minimisation in the rigid receptor: `x_refined`, energies, scores before and after, iterations, status, `moved`), with
+    `validity=` also `refined["validity"]` (the check of `x_refined`) and with `vina=` also `order_vina_refined` (`rank_by_score` of
+    the refined scores).  The returned `poses` are not replaced; nothing else changes."""
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -285,6 +301,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_interactions(interactions, aligned, batch))
     if surface is not None:
         out.update(score_surface(surface, aligned, batch))
+    if refine is not None:
+        out.update(score_refined(refine, aligned, validity, vina))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -322,7 +340,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `surface`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `surface`, `refine`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -413,7 +431,7 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None):
+                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         if physics_correction and ref_mol_poses is None:
@@ -442,6 +460,7 @@ class _RedockState:
         self.vina = vina
         self.interactions = interactions
         self.surface = surface
+        self.refine = refine
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -524,6 +543,8 @@ class _RedockState:
             out.update(score_interactions(self.interactions, aligned, self.batch))
         if self.surface is not None:
             out.update(score_surface(self.surface, aligned, self.batch))
+        if self.refine is not None:
+            out.update(score_refined(self.refine, aligned, self.validity, self.vina))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)

@@ -16,8 +16,9 @@ d = r - R_i - R_j (X-Score radii `RADII`)
 It needs no ground truth and no trained weights, and it is the one pose measure of the package that can compare different ligands
 in one receptor.  **Two caveats.**  The weights are Vina's published ones; nothing here validates them on real complexes or fits
 them to this model's poses.  The atom typing is heuristic: the model predicts heavy atoms only, so hydrogens - and with them
-donors - are inferred from valences (ligand) or from residue and atom names (receptor).  Out of scope: Vina's intramolecular term,
-any minimiser on top of the forces.
+donors - are inferred from valences (ligand) or from residue and atom names (receptor).  Vina's intramolecular term and a minimiser
+on top of the forces live in `refine.VinaRefine` (rigid-body and torsion refinement of every pose, csrc/vina_refine.hip); this score
+stays the intermolecular part.
 
 `VinaScore` holds one system's type table, built once on the host; `score(x_pred)` returns device tensors and never synchronises.
 `ranking.rank_by_score` orders poses by it, `driver.redock(..., vina=)` reports it for the kept poses.
