@@ -441,6 +441,30 @@ int pd_pairwise_rmsd(const float* x, const int* idx, const float* ref, float* D,
  * L <= 1024, M <= 65535, n <= 65535 (else PD_ERR_UNSUPPORTED).                                                              */
 int pd_sym_rmsd(const float* x, const int* idx, const float* ref, const unsigned short* perms_t, float* D, float* rmsd_ref,
                 int* best_perm_ref, int n, int A, int L, int M, void* stream);
+/* Binding modes of n poses: greedy leader clustering on a distance matrix, best pose first, as Vina, AutoDock, GNINA and rDock report
+ * them (cluster.hip; ABI 11, additive; the consumer of pd_pairwise_rmsd / pd_sym_rmsd and of 1 - pd_plif_pairwise - the reference runs
+ * K-means(5) of scikit-learn on the host, redocking.py:389-416).  D [n][n] symmetric with a zero diagonal; order [n] the pose ids best
+ * first, a permutation of 0 .. n-1 (an entry outside 0 .. n-1 is skipped and never followed); valid [n] bytes (NULL: all valid); score
+ * [n] (NULL: none).  labels = -1, k = 0; for r = 0 .. n-1 and i = order[r], unless i is invalid or labelled: i leads cluster k, i and
+ * every valid unlabelled j with D[i][j] <= cutoff (fp32, inclusive, false for a NaN) get label k, k += 1.  Invalid poses keep -1.
+ *   labels[i], dist_to_leader[i]   the pose's cluster and D[its leader][i] (-1 and NaN for an invalid pose)
+ *   leader[k], size[k], radius[k]  the leading pose, the number of members, the exact maximum of D[leader][member]
+ *   medoid[k]                      the member i with the smallest s_i = sum over the OTHER members j, ascending, of (double)D[j][i] (fp64;
+ *                                  a NaN counts as +inf), the smallest i on a tie
+ *   spread[k]                      (float)((sum of s_i over the members, ascending) / (double)(size (size - 1))), 0 for a singleton
+ *   mean_score[k]                  (float)((sum of (double)score[i] over the members, ascending) / (double)size), NaN without score
+ *   n_clusters[0]                  k at the end
+ * The per-cluster arrays hold n entries; those at k >= n_clusters are -1 (leader, medoid), 0 (size) and NaN (the floats).  ws:
+ * pd_pose_clusters_workspace_numel(n) = n doubles (the s_i), written before they are read.  Only the rows of D that belong to leaders
+ * and the columns of the poses are read.  Three launches, no atomics, no allocation, no synchronisation; maxima and sums in the
+ * stated order: bit-identical from launch to launch.  n < 1, a NULL required pointer, a misaligned pointer (4 bytes for float / int,
+ * 8 for ws), a negative or non-finite cutoff or a short workspace: PD_ERR_ARG; n > PD_POSE_CLUSTERS_MAX_POSES: PD_ERR_UNSUPPORTED.  A
+ * rejected call writes nothing.  tests/pose_clusters_ref.py is the written definition.                                             */
+#define PD_POSE_CLUSTERS_MAX_POSES 8192
+int pd_pose_clusters_workspace_numel(int n);
+int pd_pose_clusters(const float* D, const int* order, float cutoff, const unsigned char* valid, const float* score, double* ws,
+                     long long ws_numel, int* labels, float* dist_to_leader, int* leader, int* size, float* radius, int* medoid,
+                     float* spread, float* mean_score, int* n_clusters, int n, void* stream);
 /* PoseBusters-style geometry checks of P poses of one ligand in its receptor, without leaving the device (validity.hip; ABI 11,
  * additive; the reference runs the `posebusters` package on the host through files, PhysDock/data/relaxation.py:24-50).  Tables,
  * built once per ligand (physdock_amd/validity.py): lig_idx [L] the ligand's atoms in a pose (any order, any place); radius [A] van

@@ -25,3 +25,4 @@ from .scoring import VinaScore  # noqa: F401  (Vina-style interaction score and 
 from .interactions import InteractionFingerprint  # noqa: F401  (per-residue interaction fingerprint of every pose; csrc/plif.hip)
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
+from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)

@@ -254,6 +254,8 @@ def _declare(L):
     sig("pd_plif_compare", p, p, i, p, p, p, p, p, i, i, p)
     sig("pd_plif_pairwise", p, i, p, i, i, p)
     sig("pd_buried_surface", p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p, i, i, i, i, i, i, p)       # ABI 11, additive (sasa.hip)
+    sig("pd_pose_clusters_workspace_numel", i)                                               # ABI 11, additive (cluster.hip)
+    sig("pd_pose_clusters", p, p, f, p, p, p, ll, p, p, p, p, p, p, p, p, p, i, p)
 
 
 def ptr(t):

@@ -155,7 +155,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
-           interactions=None, surface=None, refine=None) -> dict:
+           interactions=None, surface=None, refine=None, clusters=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -191,7 +191,16 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `refine` (a `refine.VinaRefine` of the system): the result gains `refined` = its `refine` of the returned `poses` (rigid-body and
     torsion minimisation in the rigid receptor: `x_refined`, energies, scores before and after, iterations, status, `moved`), with
     `validity=` also `refined["validity"]` (the check of `x_refined`) and with `vina=` also `order_vina_refined` (`rank_by_score` of
-    the refined scores).  The returned `poses` are not replaced; nothing else changes."""
+    the refined scores).  The returned `poses` are not replaced; nothing else changes.
+    `clusters` (a `clustering.PoseClusters` spec): the result gains `clusters` = the binding modes of the returned `poses`
+    (`PoseClusters.cluster`: labels, leaders, medoids, sizes, radii, spreads, `dist`).  `metric="rmsd"` clusters their pairwise ligand RMSD
+    (`ranking["dist"]` when `ranking` ran, else `pairwise_ligand_rmsd` with `ligand_symmetry=`), `metric="interactions"` clusters 1 -
+    `interactions.pairwise(bits)` and needs `interactions=`.  The poses are walked in the order `by` names: `"confidence"` needs
+    `confidence=`, `"vina"` needs `vina=`, `"vina_refined"` needs `refine=` and `vina=`; a missing prerequisite raises ValueError before
+    anything is sampled.  With `vina=` the modes carry `mean_score`, with `validity=` only valid poses lead and join, and when `ranking`
+    ran `clusters["leader_rmsd"]` is the RMSD to `x_gt` of each mode's leader (NaN behind `n_clusters`).  Nothing else changes."""
+    from .clustering import check_redock_prerequisites, cluster_kept_poses
+    check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -303,6 +312,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_surface(surface, aligned, batch))
     if refine is not None:
         out.update(score_refined(refine, aligned, validity, vina))
+    if clusters is not None:
+        out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -340,7 +351,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `surface`, `refine`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -431,9 +442,11 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None):
+                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
+        from .clustering import check_redock_prerequisites
+        check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
         if physics_correction and ref_mol_poses is None:
             raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                              "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
@@ -461,6 +474,7 @@ class _RedockState:
         self.interactions = interactions
         self.surface = surface
         self.refine = refine
+        self.clusters = clusters
 
     def round_args(self, rnd):
         """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
@@ -545,6 +559,10 @@ class _RedockState:
             out.update(score_surface(self.surface, aligned, self.batch))
         if self.refine is not None:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
+        if self.clusters is not None:
+            from .clustering import cluster_kept_poses
+            out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,
+                                          ligand_symmetry=self.ligand_symmetry))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
