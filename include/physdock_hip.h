@@ -13,6 +13,7 @@
  */
 #ifndef PHYSDOCK_HIP_H
 #define PHYSDOCK_HIP_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -618,6 +619,48 @@ int pd_plif_compare(const unsigned char* bits, const unsigned char* ref_bits, in
 /* tanimoto [P][P]: the same Tanimoto between every two rows of bits [P][R]; symmetric, the diagonal exactly 1; row p equals
  * pd_plif_compare against row p bit for bit.  One thread per pair, 16 x 16 pairs per block.  Limits and codes as above.          */
 int pd_plif_pairwise(const unsigned char* bits, int kind_mask, float* tanimoto, int P, int R, void* stream);
+/* Ring interactions of P poses of one ligand in its receptor: pi-stacking, pi-cation and halogen bonds per residue - the kinds
+ * pd_plif_fingerprint leaves out (plif_rings.hip, whose header comment holds the full definition; ABI 11, additive; the conditions
+ * and default thresholds are PLIP's published ones - the reference has no counterpart).  x, lig_idx, type, charge, lig_active,
+ * res_start and res_atom are exactly what pd_plif_fingerprint takes; the receptor's CATION (charge bit 0) and ACCEPTOR (type bit 6)
+ * atoms are found through res_atom.  Rings as a CSR over pose atoms: ring g is ring_atom[ring_start[g] .. ring_start[g + 1]) in
+ * cyclic order, 3 .. 8 atoms, the ligand's G_l rings first (ring_residue -1), then the receptor's G_r rings IN ASCENDING ORDER OF
+ * ring_residue [G_l + G_r], the residue a ring belongs to.  halogen [H][2]: ligand-local indices (X, C).  thresholds: EIGHT doubles
+ * ON THE HOST, passed on as values - the five distances stack_dist, stack_offset, pication_dist, pication_offset, halogen_dist (A),
+ * then the three cosines of parallel_angle, t_angle, halogen_angle.  In double from the fp32 coordinates: centroid c = mean of the
+ * ring's atoms, normal n = sum_i (a_i - c) x (a_{i+1} - c) normalised; a ring whose normal has zero or non-finite length, with a
+ * non-finite coordinate, a size outside 3 .. 8 or an atom outside 0 .. A - 1 is degenerate, takes part in nothing and reports n = 0
+ * (ring_start is a device array: the call cannot reject a ring size).  Bit k of a byte = kind k:
+ *   0 pi_parallel   ligand ring g, receptor ring h: |c_g - c_h| < t[0], min(off_gh, off_hg) < t[1], |n_g . n_h| > t[5]
+ *   1 pi_tshaped    the same distance and offset, |n_g . n_h| < t[6]
+ *   2 pi_cation     ligand ring g, receptor cation j: |x_j - c_g| < t[2], the offset of x_j on the plane of g < t[3]
+ *   3 cation_pi     active ligand cation i, receptor ring h: the same with the roles swapped
+ *   4 halogen_bond  active ligand halogen X with its carbon C, receptor acceptor j: |x_X - x_j| < t[4], cos(C - X ... j) < t[7]
+ * with off_gh = sqrt(max(0, d^2 - ((c_h - c_g) . n_g)^2)).  Bits 5 - 7 are 0; a NaN fails every comparison.
+ *   bits[p][s]               OR over the rings, cations and acceptors of residue s
+ *   ligand_bits[p][i]        OR per ligand atom (a ring's byte goes to its atoms, bit 4 to X, bit 3 to the cation; inactive: 0)
+ *   ring_bits[p][g]          OR per ligand ring
+ *   centroid, normal         [P][G_l + G_r][3] doubles
+ *   min_centroid_dist[p][s]  the smallest ligand-ring to residue-ring centroid distance, minimum in double, rounded once; +inf
+ *                            when either side has no ring that is not degenerate
+ *   counts[p][k]             residues per kind, [P][5]
+ * workspace: pd_plif_rings_workspace(P, L, N, G_l, G_r, H) bytes, 8-byte aligned (the function returns PD_ERR_UNSUPPORTED when the
+ * size does not fit an int).  Four launches, no atomics, no allocation, no synchronisation; OR, exact minima and integer sums only:
+ * bit-identical from launch to launch, independent of P and of a pose's place among the P.  PD_ERR_ARG: a required pointer is NULL
+ * (res_atom may be when N == 0; ring_start, ring_atom, ring_residue, centroid and normal when G_l + G_r == 0; ring_bits when G_l ==
+ * 0; halogen when H == 0), P, A, L or R not positive, a negative count, N > A, an int or float pointer off 4-byte or a double
+ * pointer (thresholds and workspace included) off 8-byte alignment, a negative or non-finite distance, a cosine outside [-1, 1], a
+ * short workspace.  PD_ERR_UNSUPPORTED: L > 1024, G_l > 64, G_r > 4096, H > 64, A > 2^22, P > 65535, R > A.  A rejected call writes
+ * nothing.                                                                                                                       */
+#define PD_PLIF_RING_KINDS 5
+#define PD_PLIF_RING_THRESHOLDS 8
+int pd_plif_rings(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* charge,
+                  const unsigned char* lig_active, const int* res_start, const int* res_atom, const int* ring_start,
+                  const int* ring_atom, const int* ring_residue, int G_l, int G_r, const int* halogen, int H,
+                  const double* thresholds, void* workspace, size_t workspace_bytes, unsigned char* bits,
+                  unsigned char* ligand_bits, unsigned char* ring_bits, double* centroid, double* normal, float* min_centroid_dist,
+                  int* counts, int P, int A, int L, int R, int N, void* stream);
+int pd_plif_rings_workspace(int P, int L, int N, int G_l, int G_r, int H);
 /* Ligand burial and interface area of P poses of one ligand in its receptor: solvent-accessible surface area by point counting
  * (sasa.hip; ABI 11, additive; Shrake & Rupley 1973, HEAVY ATOMS ONLY - absolute areas are not comparable with all-atom tools, and
  * the default radii and probe have not been validated on real complexes; the reference has no counterpart).  Tables, built once

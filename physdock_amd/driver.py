@@ -139,6 +139,15 @@ def score_interactions(interactions, aligned, batch) -> dict:
     return res
 
 
+def score_ring_interactions(ring_interactions, aligned, batch) -> dict:
+    """redock(ring_interactions=): {"ring_interactions": RingInteractions.fingerprint of the kept poses} and, when the batch carries the
+    ground truth, "ring_interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
+    res = {"ring_interactions": ring_interactions.fingerprint(aligned)}
+    if "x_gt" in batch:
+        res["ring_interaction_recovery"] = ring_interactions.compare(res["ring_interactions"]["bits"], batch["x_gt"].float())
+    return res
+
+
 def score_surface(surface, aligned, batch) -> dict:
     """redock(surface=): {"surface": BuriedSurface.measure of the kept poses} and, when the batch carries the ground truth,
     "surface_gt": its measure of `x_gt` (one pose)"""
@@ -155,7 +164,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
-           interactions=None, surface=None, refine=None, clusters=None) -> dict:
+           interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -184,6 +193,10 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     the returned `poses` (per-residue and per-ligand-atom interaction bytes, closest distances, counts) and, as the batch carries
     `x_gt`, `interaction_recovery` = its `compare` of those bits with the ground truth's.  Nothing else changes, with or without
     `validity=`.
+    `ring_interactions` (a `ring_interactions.RingInteractions` of the system): the result gains `ring_interactions` = its
+    `fingerprint` of the returned `poses` (pi-stacking, pi-cation and halogen-bond bytes per residue, ligand atom and ligand ring, the
+    ring frames, closest centroid distances, counts) and, as the batch carries `x_gt`, `ring_interaction_recovery` = its `compare` of
+    those bits with the ground truth's.  Nothing else changes, with or without `interactions=`.
     `surface` (a `surface.BuriedSurface` of the system): the result gains `surface` = its `measure` of the returned `poses` (the
     ligand's solvent-accessible area free and in the complex, the buried fraction and its polar / apolar split, the area each residue
     loses to the ligand) and, as the batch carries `x_gt`, `surface_gt` = its `measure` of the ground truth (one pose).  Nothing else
@@ -308,6 +321,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_vina(vina, aligned, out))
     if interactions is not None:
         out.update(score_interactions(interactions, aligned, batch))
+    if ring_interactions is not None:
+        out.update(score_ring_interactions(ring_interactions, aligned, batch))
     if surface is not None:
         out.update(score_surface(surface, aligned, batch))
     if refine is not None:
@@ -351,7 +366,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -442,7 +457,8 @@ class _RedockState:
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
-                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None):
+                 validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
+                 ring_interactions=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
@@ -472,6 +488,7 @@ class _RedockState:
         self.lddt_pli = lddt_pli
         self.vina = vina
         self.interactions = interactions
+        self.ring_interactions = ring_interactions
         self.surface = surface
         self.refine = refine
         self.clusters = clusters
@@ -555,6 +572,8 @@ class _RedockState:
             out.update(score_vina(self.vina, aligned, out))
         if self.interactions is not None:
             out.update(score_interactions(self.interactions, aligned, self.batch))
+        if self.ring_interactions is not None:
+            out.update(score_ring_interactions(self.ring_interactions, aligned, self.batch))
         if self.surface is not None:
             out.update(score_surface(self.surface, aligned, self.batch))
         if self.refine is not None:

@@ -25,8 +25,9 @@ kind.  HYDROPHOBIC / DONOR / ACCEPTOR are the bits of the type byte of `scoring.
 The thresholds are the `thresholds=` argument of the constructors and reach the kernel as values.  The defaults are the usual
 heavy-atom distances of fingerprint packages; they are THIS PACKAGE'S DEFAULTS AND HAVE NOT BEEN VALIDATED on real complexes.
 **Two caveats.**  The model predicts no hydrogens, so there is no donor - H - acceptor angle test, and donors are inferred exactly
-as in `scoring.py` (ligand: valences; receptor: residue and atom names).  Pi-stacking, pi-cation, halogen and metal interactions
-and water bridges are out of scope: they need ring centroids and normals.
+as in `scoring.py` (ligand: valences; receptor: residue and atom names).  Pi-stacking, pi-cation and halogen bonds need ring
+centroids and normals: they are the kinds of `ring_interactions.RingInteractions`.  Metal interactions and water bridges are out of
+scope.
 
 The residue-side fingerprint is an OR over ligand atoms of equal type, so it is invariant under the ligand's automorphisms: no
 `LigandSymmetry` is needed to compare it with a ground truth.
@@ -77,20 +78,25 @@ _CATIONS = {"LYS": ("NZ",), "ARG": ("NE", "NH1", "NH2")}
 _ANIONS = {"ASP": ("OD1", "OD2"), "GLU": ("OE1", "OE2")}
 
 
-def kind_mask(kinds: Optional[Iterable[str]] = None) -> int:
-    """the byte mask of a sequence of kind names (default: all six)"""
+def _mask_of(kinds: Optional[Iterable[str]], names: Sequence[str]) -> int:
+    """the byte mask of a sequence of kind names out of `names` (None: all of them)"""
     if kinds is None:
-        return (1 << len(KIND_NAMES)) - 1
+        return (1 << len(names)) - 1
     if isinstance(kinds, str):
         kinds = (kinds,)
     mask = 0
     for k in kinds:
-        if k not in KIND_NAMES:
-            raise ValueError(f"unknown interaction kind {k!r}; the kinds are {KIND_NAMES}")
-        mask |= 1 << KIND_NAMES.index(k)
+        if k not in names:
+            raise ValueError(f"unknown interaction kind {k!r}; the kinds are {tuple(names)}")
+        mask |= 1 << names.index(k)
     if mask == 0:
         raise ValueError("kinds must name at least one interaction kind")
     return mask
+
+
+def kind_mask(kinds: Optional[Iterable[str]] = None) -> int:
+    """the byte mask of a sequence of kind names (default: all six)"""
+    return _mask_of(kinds, KIND_NAMES)
 
 
 def receptor_charges_from_names(res_names: Sequence[str], atom_names: Sequence[str]) -> np.ndarray:
@@ -214,7 +220,92 @@ def _thresholds(thresholds) -> Tuple[float, float, float, float]:
     return out
 
 
-class InteractionFingerprint:
+class _ByteRows:
+    """what `InteractionFingerprint` and `ring_interactions.RingInteractions` do with their `bits` [P,R] - one byte per residue, bit
+    k = kind k of the class's `_kind_names`: `compare`, `pairwise`, `satisfies`, `required_row`, `describe`, all through
+    `pd_plif_compare` / `pd_plif_pairwise`.  A subclass provides `_name`, `_kind_names`, `n_residues`, `n_pose_atoms`,
+    `residue_labels` and `fingerprint`."""
+    _name = "InteractionFingerprint"
+    _kind_names = KIND_NAMES
+
+    def _mask(self, kinds) -> int:
+        return _mask_of(kinds, self._kind_names)
+
+    def _bits(self, bits, what):
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[1] != self.n_residues:
+            raise ValueError(f"{self._name}.{what}: bits must be a uint8 tensor [P,{self.n_residues}] as `fingerprint` returns it")
+        if not 1 <= bits.shape[0] <= MAX_POSES:
+            raise ValueError(f"{self._name}.{what}: {bits.shape[0]} poses; the kernel takes 1 .. {MAX_POSES}")
+        return bits.contiguous()
+
+    def compare(self, bits: torch.Tensor, reference, kinds: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
+        """bits [P,R] against a reference: a uint8 row [R], or coordinates [A,3] (e.g. `x_gt`), which are fingerprinted first.  Counted
+        over (residue, kind) pairs of the `kinds` (names of the class's kinds, `KIND_NAMES` here; default all - `kinds=("hbond_donor",
+        "hbond_acceptor", "cationic", "anionic")` leaves plain contacts out): shared int32 [P], n_pose int32 [P], n_reference int32 [], recovery [P] =
+        shared / n_reference (1 where the reference shows nothing) and tanimoto [P] = shared / (n_pose + n_reference - shared) (1 where
+        both show nothing).  Device tensors, no read-back."""
+        mask = self._mask(kinds)
+        bits = self._bits(bits, "compare")
+        ref = reference if isinstance(reference, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(reference))
+        ref = ref.to(bits.device)
+        if ref.dtype != torch.uint8:
+            if ref.dim() != 2 or tuple(ref.shape) != (self.n_pose_atoms, 3) or not ref.is_floating_point():
+                raise ValueError(f"{self._name}.compare: the reference is a uint8 row [{self.n_residues}] or coordinates "
+                                 f"[{self.n_pose_atoms},3], got {ref.dtype} {tuple(ref.shape)}")
+            ref = self.fingerprint(ref[None])["bits"][0]
+        if ref.dim() != 1 or ref.shape[0] != self.n_residues:
+            raise ValueError(f"{self._name}.compare: a reference row holds {self.n_residues} bytes, got {tuple(ref.shape)}")
+        ref = ref.contiguous()
+        L_ = ops._lib.init()
+        P, R = bits.shape
+        new = lambda n, dtype: torch.empty(n, dtype=dtype, device=bits.device)
+        shared, n_pose, n_ref = new(P, torch.int32), new(P, torch.int32), new(1, torch.int32)
+        recovery, tanimoto = new(P, torch.float32), new(P, torch.float32)
+        ops.check(L_.pd_plif_compare(ops.ptr(bits), ops.ptr(ref), mask, ops.ptr(shared), ops.ptr(n_pose), ops.ptr(n_ref), ops.ptr(recovery),
+                                     ops.ptr(tanimoto), P, R, ops.stream()), "pd_plif_compare")
+        return {"shared": shared, "n_pose": n_pose, "n_reference": n_ref.reshape(()), "recovery": recovery, "tanimoto": tanimoto}
+
+    def pairwise(self, bits: torch.Tensor, kinds: Optional[Iterable[str]] = None) -> torch.Tensor:
+        """tanimoto fp32 [P,P] between every two rows of bits [P,R] over the `kinds` (as in `compare`): symmetric, the diagonal exactly
+        1 - a similarity to cluster poses by binding mode"""
+        mask = self._mask(kinds)
+        bits = self._bits(bits, "pairwise")
+        L_ = ops._lib.init()
+        P, R = bits.shape
+        out = torch.empty((P, P), dtype=torch.float32, device=bits.device)
+        ops.check(L_.pd_plif_pairwise(ops.ptr(bits), mask, ops.ptr(out), P, R, ops.stream()), "pd_plif_pairwise")
+        return out
+
+    def required_row(self, required: Iterable[Tuple[object, str]]) -> np.ndarray:
+        """uint8 [R]: the byte row with the bits of `required`, pairs (residue id or residue label, kind name)"""
+        row = np.zeros(self.n_residues, dtype=np.uint8)
+        for residue, kind in required:
+            if isinstance(residue, str):
+                if self.residue_labels is None or residue not in self.residue_labels:
+                    raise ValueError(f"{self._name}: no residue is labelled {residue!r}")
+                residue = self.residue_labels.index(residue)
+            if not 0 <= int(residue) < self.n_residues:
+                raise ValueError(f"{self._name}: residue {residue} is not in 0 .. {self.n_residues - 1}")
+            row[int(residue)] |= self._mask((kind,))
+        return row
+
+    def satisfies(self, bits: torch.Tensor, required: Iterable[Tuple[object, str]]) -> torch.Tensor:
+        """bool [P] on the device: does the pose show every required (residue, kind)?  A `compare` against the required row with
+        shared == n_reference; nothing required is satisfied by every pose."""
+        out = self.compare(bits, torch.from_numpy(self.required_row(required)))
+        return out["shared"] == out["n_reference"]
+
+    def describe(self, bits_row) -> List[Tuple[object, List[str]]]:
+        """host helper: one byte row [R] (a tensor is read back) -> [(residue label or id, [kind names])] of the residues that show
+        anything, in residue order"""
+        row = np.asarray(bits_row.detach().cpu() if isinstance(bits_row, torch.Tensor) else bits_row).reshape(-1)
+        if row.shape[0] != self.n_residues:
+            raise ValueError(f"{self._name}.describe: a row holds {self.n_residues} bytes, got {row.shape[0]}")
+        label = (lambda s: self.residue_labels[s] or s) if self.residue_labels is not None else (lambda s: s)
+        return [(label(int(s)), [k for b, k in enumerate(self._kind_names) if int(row[s]) >> b & 1]) for s in np.nonzero(row)[0]]
+
+
+class InteractionFingerprint(_ByteRows):
     """One system's tables for `pd_plif_fingerprint`: host copies (numpy: `types` uint8 [A], `charges` uint8 [A], `ligand_idx` int32
     [L], `lig_active` uint8 [L], `rec_mask` uint8 [A], `residue_of` int32 [A], the CSR `res_start` int32 [R + 1] / `res_atom` int32
     [N]), `thresholds` (dict, A), `receptor_typing` (how the receptor's bytes were made: "given", "names" or "elements" - the last
@@ -377,79 +468,6 @@ class InteractionFingerprint:
                                          self._thr, ops.ptr(ws_bits), ops.ptr(ws_min), ops.ptr(bits), ops.ptr(ligand_bits),
                                          ops.ptr(min_dist), ops.ptr(counts), P, A, L, R, N, ops.stream()), "pd_plif_fingerprint")
         return {"bits": bits, "ligand_bits": ligand_bits, "min_dist": min_dist, "counts": counts}
-
-    def _bits(self, bits, what):
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 2 or bits.shape[1] != self.n_residues:
-            raise ValueError(f"InteractionFingerprint.{what}: bits must be a uint8 tensor [P,{self.n_residues}] as `fingerprint` returns it")
-        if not 1 <= bits.shape[0] <= MAX_POSES:
-            raise ValueError(f"InteractionFingerprint.{what}: {bits.shape[0]} poses; the kernel takes 1 .. {MAX_POSES}")
-        return bits.contiguous()
-
-    def compare(self, bits: torch.Tensor, reference, kinds: Optional[Iterable[str]] = None) -> Dict[str, torch.Tensor]:
-        """bits [P,R] against a reference: a uint8 row [R], or coordinates [A,3] (e.g. `x_gt`), which are fingerprinted first.  Counted
-        over (residue, kind) pairs of the `kinds` (names of `KIND_NAMES`; default all six - `kinds=("hbond_donor", "hbond_acceptor",
-        "cationic", "anionic")` leaves plain contacts out): shared int32 [P], n_pose int32 [P], n_reference int32 [], recovery [P] =
-        shared / n_reference (1 where the reference shows nothing) and tanimoto [P] = shared / (n_pose + n_reference - shared) (1 where
-        both show nothing).  Device tensors, no read-back."""
-        mask = kind_mask(kinds)
-        bits = self._bits(bits, "compare")
-        ref = reference if isinstance(reference, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(reference))
-        ref = ref.to(bits.device)
-        if ref.dtype != torch.uint8:
-            if ref.dim() != 2 or tuple(ref.shape) != (self.n_pose_atoms, 3) or not ref.is_floating_point():
-                raise ValueError(f"InteractionFingerprint.compare: the reference is a uint8 row [{self.n_residues}] or coordinates "
-                                 f"[{self.n_pose_atoms},3], got {ref.dtype} {tuple(ref.shape)}")
-            ref = self.fingerprint(ref[None])["bits"][0]
-        if ref.dim() != 1 or ref.shape[0] != self.n_residues:
-            raise ValueError(f"InteractionFingerprint.compare: a reference row holds {self.n_residues} bytes, got {tuple(ref.shape)}")
-        ref = ref.contiguous()
-        L_ = ops._lib.init()
-        P, R = bits.shape
-        new = lambda n, dtype: torch.empty(n, dtype=dtype, device=bits.device)
-        shared, n_pose, n_ref = new(P, torch.int32), new(P, torch.int32), new(1, torch.int32)
-        recovery, tanimoto = new(P, torch.float32), new(P, torch.float32)
-        ops.check(L_.pd_plif_compare(ops.ptr(bits), ops.ptr(ref), mask, ops.ptr(shared), ops.ptr(n_pose), ops.ptr(n_ref), ops.ptr(recovery),
-                                     ops.ptr(tanimoto), P, R, ops.stream()), "pd_plif_compare")
-        return {"shared": shared, "n_pose": n_pose, "n_reference": n_ref.reshape(()), "recovery": recovery, "tanimoto": tanimoto}
-
-    def pairwise(self, bits: torch.Tensor, kinds: Optional[Iterable[str]] = None) -> torch.Tensor:
-        """tanimoto fp32 [P,P] between every two rows of bits [P,R] over the `kinds` (as in `compare`): symmetric, the diagonal exactly
-        1 - a similarity to cluster poses by binding mode"""
-        mask = kind_mask(kinds)
-        bits = self._bits(bits, "pairwise")
-        L_ = ops._lib.init()
-        P, R = bits.shape
-        out = torch.empty((P, P), dtype=torch.float32, device=bits.device)
-        ops.check(L_.pd_plif_pairwise(ops.ptr(bits), mask, ops.ptr(out), P, R, ops.stream()), "pd_plif_pairwise")
-        return out
-
-    def required_row(self, required: Iterable[Tuple[object, str]]) -> np.ndarray:
-        """uint8 [R]: the byte row with the bits of `required`, pairs (residue id or residue label, kind name)"""
-        row = np.zeros(self.n_residues, dtype=np.uint8)
-        for residue, kind in required:
-            if isinstance(residue, str):
-                if self.residue_labels is None or residue not in self.residue_labels:
-                    raise ValueError(f"InteractionFingerprint: no residue is labelled {residue!r}")
-                residue = self.residue_labels.index(residue)
-            if not 0 <= int(residue) < self.n_residues:
-                raise ValueError(f"InteractionFingerprint: residue {residue} is not in 0 .. {self.n_residues - 1}")
-            row[int(residue)] |= kind_mask((kind,))
-        return row
-
-    def satisfies(self, bits: torch.Tensor, required: Iterable[Tuple[object, str]]) -> torch.Tensor:
-        """bool [P] on the device: does the pose show every required (residue, kind)?  A `compare` against the required row with
-        shared == n_reference; nothing required is satisfied by every pose."""
-        out = self.compare(bits, torch.from_numpy(self.required_row(required)))
-        return out["shared"] == out["n_reference"]
-
-    def describe(self, bits_row) -> List[Tuple[object, List[str]]]:
-        """host helper: one byte row [R] (a tensor is read back) -> [(residue label or id, [kind names])] of the residues that show
-        anything, in residue order"""
-        row = np.asarray(bits_row.detach().cpu() if isinstance(bits_row, torch.Tensor) else bits_row).reshape(-1)
-        if row.shape[0] != self.n_residues:
-            raise ValueError(f"InteractionFingerprint.describe: a row holds {self.n_residues} bytes, got {row.shape[0]}")
-        label = (lambda s: self.residue_labels[s] or s) if self.residue_labels is not None else (lambda s: s)
-        return [(label(int(s)), [k for b, k in enumerate(KIND_NAMES) if int(row[s]) >> b & 1]) for s in np.nonzero(row)[0]]
 
     def __repr__(self):
         return (f"InteractionFingerprint(n_atoms={self.n_atoms}, n_pose_atoms={self.n_pose_atoms}, residues={self.n_residues}, "
