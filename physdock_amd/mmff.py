@@ -240,7 +240,7 @@ def synthetic_terms(n_atoms: int, seed: int = 0, coords: Optional[np.ndarray] = 
     n = int(n_atoms)
     parent = [-1] + [int(rng.integers(max(0, i - 3), i)) for i in range(1, n)]
     while True:                                          # valence <= 4
-        deg = np.bincount(np.asarray(parent[1:] + list(range(1, n))), minlength=n)
+        deg = np.bincount(np.asarray(parent[1:] + list(range(1, n)), dtype=np.int64), minlength=n)
         over = [i for i in range(1, n) if deg[parent[i]] > 4]
         if not over:
             break
@@ -264,7 +264,7 @@ def synthetic_terms(n_atoms: int, seed: int = 0, coords: Optional[np.ndarray] = 
                     break
             coords[b] = cand
     coords = np.asarray(coords, dtype=np.float64)
-    deg = np.bincount(np.asarray(bonds).reshape(-1), minlength=n)
+    deg = np.bincount(np.asarray(bonds, dtype=np.int64).reshape(-1), minlength=n)
     for _ in range(max(1, n // 8)):                      # ring closures: spatially close atoms >= 3 bonds apart
         d, _ = _topological_distances(n, bonds)
         cand = [(i, j) for i in range(n) for j in range(i + 1, n)
