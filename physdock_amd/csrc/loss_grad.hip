@@ -116,8 +116,20 @@ __global__ __launch_bounds__(1024) void smooth_lddt_grad_kernel(const float* __r
                 const float d2 = fmaf(dz, dz, fmaf(dy, dy, dx * dx));
                 const float r = __builtin_amdgcn_rsqf(d2);
                 const float del = d2 * r - dg[jj];
-                const float f = d2 > 0.f ? mk[jj] * dsig4(sig4(fabsf(del))) * sgn(del) * r : 0.f;
-                ax[bb] = fmaf(f, dx, ax[bb]); ay[bb] = fmaf(f, dy, ay[bb]); az[bb] = fmaf(f, dz, az[bb]);
+                float f = mk[jj] * dsig4(sig4(fabsf(del))) * sgn(del) * r, ux = dx, uy = dy, uz = dz;
+                if (d2 < 1.17549435e-38f) {
+                    // zero distance: zero direction.  A d2 below the normal range (two atoms closer than 1e-19) is no zero
+                    // distance, but v_rsq_f32 takes it for one and answers inf (f = 0 * inf): form the unit direction from
+                    // differences scaled by 2^96.  No d2 >= FLT_MIN comes here, so every other pair keeps its bits.
+                    f = 0.f;
+                    if (dx != 0.f || dy != 0.f || dz != 0.f) {
+                        ux = dx * 0x1p+96f; uy = dy * 0x1p+96f; uz = dz * 0x1p+96f;
+                        const float s2 = fmaf(uz, uz, fmaf(uy, uy, ux * ux)), rs = __builtin_amdgcn_rsqf(s2);
+                        const float dls = s2 * rs * 0x1p-96f - dg[jj];
+                        f = mk[jj] * dsig4(sig4(fabsf(dls))) * sgn(dls) * rs;
+                    }
+                }
+                ax[bb] = fmaf(f, ux, ax[bb]); ay[bb] = fmaf(f, uy, ay[bb]); az[bb] = fmaf(f, uz, az[bb]);
             }
         }
     }
