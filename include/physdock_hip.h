@@ -661,6 +661,60 @@ int pd_plif_rings(const float* x, const int* lig_idx, const unsigned char* type,
                   unsigned char* ligand_bits, unsigned char* ring_bits, double* centroid, double* normal, float* min_centroid_dist,
                   int* counts, int P, int A, int L, int R, int N, void* stream);
 int pd_plif_rings_workspace(int P, int L, int N, int G_l, int G_r, int H);
+/* Riding hydrogens of P poses of one ligand in its receptor, and the hydrogen bonds they make with the D - H ... A angle
+ * (hydrogens.hip, whose header comment holds the full definition; ABI 11, additive; bond lengths and thresholds are this package's
+ * defaults, the bond conditions PLIP's published ones - the reference has no counterpart).  Hydrogen table, H rows, built once per
+ * system (physdock_amd/hydrogens.py): parent [H] the pose atom a hydrogen rides on; ref [H][3] pose atoms n1, n2, n3 (-1 unused);
+ * mode [H] one of PD_H_*; length [H] (A), angle_a [H], angle_b [H] (radians); side [H] 0 receptor, 1 ligand.  In double from the fp32
+ * coordinates, with p the parent, u_i = unit(n_i - p), rounded once to fp32:
+ *   PD_H_TRI     H = p + length unit(-(u1 + u2 + u3))
+ *   PD_H_BISECT  H = p + length (cos a unit(-(u1 + u2)) + sin a unit(u1 x u2))
+ *   PD_H_NERF    bc = unit(p - n1), n = unit((n1 - n2) x bc), m = n x bc; H = p + length (-cos a bc + sin a (cos b m + sin b n))
+ *   PD_H_LINEAR  H = p + length unit(p - n1)
+ * A hydrogen is not placed (x_h NaN, placed 0) when a vector to be normalised is shorter than 1e-6, a coordinate it reads is not
+ * finite, a ref its mode needs is -1 or outside 0 .. A - 1, or its mode is none of the four.  group_h [G][3]: the rows of a rotor
+ * group - one OH / SH (row, -1, -1; 12 candidates) or one NH3+ (three rows; 4 candidates), NERF rows sharing parent, n1, n2.
+ * Candidate k adds k * 30 degrees to every b; its score is the smallest |A - H| over the group's hydrogens and the finite entries A
+ * of the other molecule's part of acc with |A - p| <= d_da; the smallest score wins, a tie goes to the smaller k, without such an
+ * acceptor k = 0; with orient == 0, or a row that is not placed, the group keeps its default angles and reports 0.  acc [NA_r +
+ * NA_l]: the receptor's acceptor atoms sorted by residue, then the ligand's.
+ *   x_h [P][H][3]  placed [P][H]  rotor_choice [P][G]
+ * Two launches, no atomics, no allocation; exact minima only: bit-identical from launch to launch, independent of P and of a pose's
+ * place among the P.  PD_ERR_ARG: a required pointer is NULL (group_h and rotor_choice may be when G == 0, acc when NA_r + NA_l ==
+ * 0), P, A or H not positive, a negative count, G > H, NA_r + NA_l > A, an int or float pointer off 4-byte alignment, d_da negative
+ * or not finite.  PD_ERR_UNSUPPORTED: H > 65535, A > 2^22, P > 65535.  A rejected call writes nothing.                            */
+#define PD_H_TRI 0
+#define PD_H_BISECT 1
+#define PD_H_NERF 2
+#define PD_H_LINEAR 3
+int pd_place_hydrogens(const float* x, const int* parent, const int* ref, const unsigned char* mode, const float* length,
+                       const float* angle_a, const float* angle_b, const unsigned char* side, const int* group_h, int G,
+                       const int* acc, int NA_r, int NA_l, double d_da, int orient, float* x_h, unsigned char* placed,
+                       int* rotor_choice, int P, int A, int H, void* stream);
+/* The hydrogen bonds of the placed hydrogens.  polar [HP_l + HP_r]: the rows whose parent is N, O or S, the ligand's first, then the
+ * receptor's sorted by the residue of the parent (rh_start [R + 1]: the CSR of that part); polar_slot [H]: a row's place in polar or
+ * -1; acc, NA_r, NA_l as above (racc_start [R + 1]: the CSR of the receptor's part); lig_idx [L]; lig_acc_slot [L]: a ligand atom's
+ * place in the ligand's part of acc or -1.  thresholds: TWO doubles ON THE HOST - d_da (A) and cos(angle_min).  A placed polar
+ * hydrogen H on D and an acceptor A of the other molecule bond iff |D - A| <= t[0] and (D - H) . (A - H) <= t[1] |D - H| |A - H|,
+ * in double on x and on the fp32 x_h as stored; a NaN fails.  Bit 0 hbond_donor (the ligand donates), bit 1 hbond_acceptor.
+ *   bits[p][s]         bit 0: a ligand hydrogen bonds to an acceptor of residue s; bit 1: a hydrogen of residue s to a ligand acceptor
+ *   ligand_bits[p][i]  bit 0: a hydrogen on ligand atom i donates; bit 1: ligand atom i accepts
+ *   h_bits[p][h]       the bit of the row's side when it bonds to anything
+ *   counts[p][k]       (hydrogen, acceptor) pairs per kind, [P][2]
+ * workspace: pd_hydrogen_bonds_workspace(P, HP_l, HP_r, NA_r, NA_l) bytes (at least 8; PD_ERR_UNSUPPORTED when an int cannot hold
+ * them), 8-byte aligned: a pair count per polar row and a byte per (row, acceptor of the other side).  Two launches, no atomics, no
+ * allocation; OR and integer sums only: bit-identical as above.  PD_ERR_ARG: a required pointer is NULL (polar may be when HP_l +
+ * HP_r == 0, acc when NA_r + NA_l == 0), a size not positive, a negative count, NA_r + NA_l > A, misalignment (thresholds and
+ * workspace: 8 bytes), d_da negative or not finite, a cosine outside [-1, 1], a short workspace.  PD_ERR_UNSUPPORTED: H > 65535,
+ * HP_l + HP_r > H, L > 1024, NA_l > 1024, A > 2^22, P > 65535, R > A.  A rejected call writes nothing.                                */
+#define PD_HBOND_KINDS 2
+#define PD_HBOND_THRESHOLDS 2
+int pd_hydrogen_bonds(const float* x, const float* x_h, const unsigned char* placed, const int* parent, const int* polar, int HP_l,
+                      int HP_r, const int* polar_slot, const int* acc, int NA_r, int NA_l, const int* racc_start, const int* rh_start,
+                      const int* lig_idx, const int* lig_acc_slot, const double* thresholds, void* workspace, size_t workspace_bytes,
+                      unsigned char* bits, unsigned char* ligand_bits, unsigned char* h_bits, int* counts, int P, int A, int H, int L,
+                      int R, void* stream);
+int pd_hydrogen_bonds_workspace(int P, int HP_l, int HP_r, int NA_r, int NA_l);
 /* Ligand burial and interface area of P poses of one ligand in its receptor: solvent-accessible surface area by point counting
  * (sasa.hip; ABI 11, additive; Shrake & Rupley 1973, HEAVY ATOMS ONLY - absolute areas are not comparable with all-atom tools, and
  * the default radii and probe have not been validated on real complexes; the reference has no counterpart).  Tables, built once

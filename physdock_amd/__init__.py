@@ -24,6 +24,7 @@ from .lddt_pli import LddtPli  # noqa: F401  (symmetry-aware lDDT-PLI of every p
 from .scoring import VinaScore  # noqa: F401  (Vina-style interaction score and forces of every pose; csrc/vina.hip)
 from .interactions import InteractionFingerprint  # noqa: F401  (per-residue interaction fingerprint of every pose; csrc/plif.hip)
 from .ring_interactions import RingInteractions  # noqa: F401  (pi-stacking, pi-cation and halogen bonds of every pose; csrc/plif_rings.hip)
+from .hydrogens import Hydrogens  # noqa: F401  (riding hydrogens of every pose and angle-tested hydrogen bonds; csrc/hydrogens.hip)
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)

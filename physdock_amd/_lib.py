@@ -256,6 +256,10 @@ def _declare(L):
     sig("pd_plif_rings", p, p, p, p, p, p, p, p, p, p, i, i, p, i, C.POINTER(C.c_double), p, C.c_size_t, p, p, p, p, p, p, p,
         i, i, i, i, i, p)                                                                    # ABI 11, additive (plif_rings.hip)
     sig("pd_plif_rings_workspace", i, i, i, i, i, i)
+    sig("pd_place_hydrogens", p, p, p, p, p, p, p, p, p, i, p, i, i, d, i, p, p, p, i, i, i, p)   # ABI 11, additive (hydrogens.hip)
+    sig("pd_hydrogen_bonds", p, p, p, p, p, i, i, p, p, i, i, p, p, p, p, C.POINTER(C.c_double), p, C.c_size_t, p, p, p, p,
+        i, i, i, i, i, p)
+    sig("pd_hydrogen_bonds_workspace", i, i, i, i, i)
     sig("pd_buried_surface", p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p, i, i, i, i, i, i, p)       # ABI 11, additive (sasa.hip)
     sig("pd_pose_clusters_workspace_numel", i)                                               # ABI 11, additive (cluster.hip)
     sig("pd_pose_clusters", p, p, f, p, p, p, ll, p, p, p, p, p, p, p, p, p, i, p)

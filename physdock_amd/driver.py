@@ -148,6 +148,27 @@ def score_ring_interactions(ring_interactions, aligned, batch) -> dict:
     return res
 
 
+def check_hydrogens(hydrogens, batch) -> None:
+    """redock(hydrogens=): raise ValueError unless `hydrogens` is a `hydrogens.Hydrogens` over the batch's atoms"""
+    if hydrogens is None:
+        return
+    if not callable(getattr(hydrogens, "hbonds", None)) or not hasattr(hydrogens, "n_pose_atoms"):
+        raise ValueError("hydrogens= takes a hydrogens.Hydrogens of the system")
+    n = int(batch["x_gt"].shape[0])
+    if hydrogens.n_pose_atoms != n:
+        raise ValueError(f"hydrogens= was built over {hydrogens.n_pose_atoms} pose atoms, the batch holds {n}")
+
+
+def score_hydrogens(hydrogens, aligned, batch) -> dict:
+    """redock(hydrogens=): {"hydrogens": x_h, placed, bits and counts of Hydrogens.hbonds of the kept poses} and, when the batch carries
+    the ground truth, "hbond_recovery": its `compare` of their bits with the hydrogen bonds of `x_gt`"""
+    found = hydrogens.hbonds(aligned)
+    res = {"hydrogens": {k: found[k] for k in ("x_h", "placed", "bits", "counts")}}
+    if "x_gt" in batch:
+        res["hbond_recovery"] = hydrogens.compare(found["bits"], batch["x_gt"].float())
+    return res
+
+
 def score_surface(surface, aligned, batch) -> dict:
     """redock(surface=): {"surface": BuriedSurface.measure of the kept poses} and, when the batch carries the ground truth,
     "surface_gt": its measure of `x_gt` (one pose)"""
@@ -164,7 +185,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
-           interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None) -> dict:
+           interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -197,6 +218,10 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `fingerprint` of the returned `poses` (pi-stacking, pi-cation and halogen-bond bytes per residue, ligand atom and ligand ring, the
     ring frames, closest centroid distances, counts) and, as the batch carries `x_gt`, `ring_interaction_recovery` = its `compare` of
     those bits with the ground truth's.  Nothing else changes, with or without `interactions=`.
+    `hydrogens` (a `hydrogens.Hydrogens` of the system): the result gains `hydrogens` = `x_h`, `placed`, `bits` and `counts` of its
+    `hbonds` of the returned `poses` (the riding hydrogens, the rotatable polar ones turned to the partner, and the angle-tested
+    hydrogen bonds per residue) and, as the batch carries `x_gt`, `hbond_recovery` = its `compare` of those bits with the ground
+    truth's.  One built over another number of atoms raises ValueError before anything is sampled.  Nothing else changes.
     `surface` (a `surface.BuriedSurface` of the system): the result gains `surface` = its `measure` of the returned `poses` (the
     ligand's solvent-accessible area free and in the complex, the buried fraction and its polar / apolar split, the area each residue
     loses to the ligand) and, as the batch carries `x_gt`, `surface_gt` = its `measure` of the ground truth (one pose).  Nothing else
@@ -214,6 +239,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     ran `clusters["leader_rmsd"]` is the RMSD to `x_gt` of each mode's leader (NaN behind `n_clusters`).  Nothing else changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+    check_hydrogens(hydrogens, batch)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     if physics_correction and ref_mol_poses is None:
@@ -323,6 +349,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_interactions(interactions, aligned, batch))
     if ring_interactions is not None:
         out.update(score_ring_interactions(ring_interactions, aligned, batch))
+    if hydrogens is not None:
+        out.update(score_hydrogens(hydrogens, aligned, batch))
     if surface is not None:
         out.update(score_surface(surface, aligned, batch))
     if refine is not None:
@@ -366,7 +394,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -458,11 +486,12 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None):
+                 ring_interactions=None, hydrogens=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+        check_hydrogens(hydrogens, batch)
         if physics_correction and ref_mol_poses is None:
             raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                              "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
@@ -489,6 +518,7 @@ class _RedockState:
         self.vina = vina
         self.interactions = interactions
         self.ring_interactions = ring_interactions
+        self.hydrogens = hydrogens
         self.surface = surface
         self.refine = refine
         self.clusters = clusters
@@ -574,6 +604,8 @@ class _RedockState:
             out.update(score_interactions(self.interactions, aligned, self.batch))
         if self.ring_interactions is not None:
             out.update(score_ring_interactions(self.ring_interactions, aligned, self.batch))
+        if self.hydrogens is not None:
+            out.update(score_hydrogens(self.hydrogens, aligned, self.batch))
         if self.surface is not None:
             out.update(score_surface(self.surface, aligned, self.batch))
         if self.refine is not None:

@@ -74,6 +74,20 @@ class PdbTemplate:
         if device is not None:
             self.to(device)
 
+    @classmethod
+    def from_rows(cls, rows, atom, n_atoms: int, device=None):
+        """a template from finished records: rows uint8 [N,81] (80 columns with blank coordinates and the newline), atom int32 [N]
+        (the index into a pose of every record) and the number of atoms of the poses `format` takes - the way
+        `hydrogens.Hydrogens.pdb_template` appends hydrogen records to a template built from the naming tables"""
+        rows, atom = torch.as_tensor(rows, dtype=torch.uint8).reshape(-1, 81).clone(), torch.as_tensor(atom, dtype=torch.int32).reshape(-1).clone()
+        if rows.shape[0] != atom.shape[0] or (atom.numel() and (int(atom.min()) < 0 or int(atom.max()) >= int(n_atoms))):
+            raise ValueError(f"PdbTemplate.from_rows: {rows.shape[0]} records, {atom.shape[0]} atom indices below {int(n_atoms)}")
+        self = cls.__new__(cls)
+        self.n_atoms, self.n_records, self.rows, self.atom = int(n_atoms), int(rows.shape[0]), rows, atom
+        if device is not None:
+            self.to(device)
+        return self
+
     def to(self, device):
         self.rows, self.atom = self.rows.to(device), self.atom.to(device)
         return self

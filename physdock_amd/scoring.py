@@ -100,19 +100,12 @@ def _bond_list(n, bonds, bond_orders, what):
     return bonds, orders
 
 
-def ligand_types_from_bonds(elements, bonds: Iterable[Tuple[int, int]], bond_orders: Optional[Sequence[float]] = None,
-                            n_hydrogens=None, formal_charges=None) -> np.ndarray:
-    """uint8 [L]: the type byte of every ligand atom from the bond graph.  elements: atomic numbers (or symbols) [L]; bonds: pairs of
-    indices into them; bond_orders (default: all single; aromatic bonds count 1.5).  Hydrogens, when `n_hydrogens` [L] is not given:
+def _hydrogen_counts(z, bonds, orders, n_hydrogens, charge):
+    """(n_h, h_nb, heavy_nb, polar_nb) of every atom of a bond graph: the hydrogens it carries - `n_hydrogens` when given, else the
     default valence (C 4, N 3, O 2, S 2, P 3, halogen 1) - floor(sum of bond orders) + formal charge, clipped at 0, plus the explicit
-    hydrogen neighbours.  Donor: N or O with at least one hydrogen.  Acceptor: every O, and N without hydrogen, with at most two heavy
-    neighbours and charge <= 0.  Hydrophobic: carbon not bonded to N or O, and F, Cl, Br, I."""
-    z = _atomic_numbers(elements)
+    hydrogen neighbours -, its explicit hydrogen neighbours, its heavy neighbours, and whether it is bonded to N or O.  The one
+    valence rule of the package: `ligand_types_from_bonds` types with it, `hydrogens.ligand_hydrogens_from_bonds` places with it."""
     n = len(z)
-    bonds, orders = _bond_list(n, bonds, bond_orders, "ligand_types_from_bonds")
-    charge = np.zeros(n, dtype=np.int64) if formal_charges is None else _host(formal_charges, np.int64).reshape(-1)
-    if charge.shape[0] != n or (n_hydrogens is not None and len(n_hydrogens) != n):
-        raise ValueError(f"ligand_types_from_bonds: {n} elements, but formal_charges / n_hydrogens of another length")
     order_sum, heavy_nb, h_nb, polar_nb = np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=bool)
     for (i, j), o in zip(bonds, orders):
         for a, b in ((i, j), (j, i)):
@@ -128,6 +121,23 @@ def ligand_types_from_bonds(elements, bonds: Iterable[Tuple[int, int]], bond_ord
         n_h = implicit + h_nb
     else:
         n_h = _host(n_hydrogens, np.int64).reshape(-1)
+    return n_h, h_nb, heavy_nb, polar_nb
+
+
+def ligand_types_from_bonds(elements, bonds: Iterable[Tuple[int, int]], bond_orders: Optional[Sequence[float]] = None,
+                            n_hydrogens=None, formal_charges=None) -> np.ndarray:
+    """uint8 [L]: the type byte of every ligand atom from the bond graph.  elements: atomic numbers (or symbols) [L]; bonds: pairs of
+    indices into them; bond_orders (default: all single; aromatic bonds count 1.5).  Hydrogens, when `n_hydrogens` [L] is not given:
+    default valence (C 4, N 3, O 2, S 2, P 3, halogen 1) - floor(sum of bond orders) + formal charge, clipped at 0, plus the explicit
+    hydrogen neighbours.  Donor: N or O with at least one hydrogen.  Acceptor: every O, and N without hydrogen, with at most two heavy
+    neighbours and charge <= 0.  Hydrophobic: carbon not bonded to N or O, and F, Cl, Br, I."""
+    z = _atomic_numbers(elements)
+    n = len(z)
+    bonds, orders = _bond_list(n, bonds, bond_orders, "ligand_types_from_bonds")
+    charge = np.zeros(n, dtype=np.int64) if formal_charges is None else _host(formal_charges, np.int64).reshape(-1)
+    if charge.shape[0] != n or (n_hydrogens is not None and len(n_hydrogens) != n):
+        raise ValueError(f"ligand_types_from_bonds: {n} elements, but formal_charges / n_hydrogens of another length")
+    n_h, _, heavy_nb, polar_nb = _hydrogen_counts(z, bonds, orders, n_hydrogens, charge)
     t = radius_class(z)
     t[((z == 6) & ~polar_nb) | np.isin(z, _HALOGENS)] |= HYDROPHOBIC
     t[((z == 7) | (z == 8)) & (n_h > 0)] |= DONOR
