@@ -466,6 +466,42 @@ int pd_pose_clusters_workspace_numel(int n);
 int pd_pose_clusters(const float* D, const int* order, float cutoff, const unsigned char* valid, const float* score, double* ws,
                      long long ws_numel, int* labels, float* dist_to_leader, int* leader, int* size, float* radius, int* medoid,
                      float* spread, float* mean_score, int* n_clusters, int n, void* stream);
+/* Distance-geometry conformers of one ligand: C independent float64 minimisations of a bounds error function from random 4-D
+ * coordinates (conformers.hip; ABI 11, additive; the reference calls RDKit ETKDG on the host, redocking.py:231-243 - this is the
+ * package's own definition, no metric-matrix eigen-solve and no torsion-knowledge terms; tests/conformers_ref.py is the written
+ * definition).  Tables, built once per ligand (physdock_amd/conformers.py): lo, up [L][L] float64, the triangle-smoothed distance
+ * bounds, symmetric; centres [n_centres][4] int32 (c, n1, n2, n3) with vol_lo <= vol_hi [n_centres] of the same sign.
+ *   E(x), x [L][4] = sum_{i<j} [d2 > up2] (d2 / up2 - 1)^2 + [d2 < lo2] (2 lo2 / (lo2 + d2) - 1)^2     (d over four coordinates)
+ *                  + w_chi sum_centres viol(V)^2 + w_4d sum_a x[a][3]^2
+ *   V = (n1 - c) . ((n2 - c) x (n3 - c)) over the first three coordinates, viol = the distance of V to [vol_lo, vol_hi]
+ * pd_dg_error_grad    : err [C] (nullable) = E and grad [C][L][4] (nullable) = dE/dx of pos [C][L][4]; not both NULL
+ * pd_embed_conformers : one block per conformer, one launch.  Start: `start` [C][L][4], or if NULL uniform in [-box, box]^4, x =
+ *                       (2 u - 1) box with u = (r_k + 0.5) 2^-32 in double and r = Philox4x32-10(key = seed, counter = (conformer,
+ *                       atom, 0, 0)).  Stage 1 minimises E with (w_chi, w_4d) = (1, 0.1), stage 2 with (0.2, 1.0): the BFGS / lnsrch
+ *                       of pd_mmff_relax (same constants, no gradient scaling) in dim = 4 L; a stage stops on max|grad| < grad_tol
+ *                       (status 0), after max_iters accepted steps (1) or when the line search finds no lower point (2), as
+ *                       pd_vina_refine.  Then the fourth coordinate is dropped, the conformer centred and rounded once to fp32 into
+ *                       x [C][L][3].  ok [C] = 1 when, in 3-D and in double, the largest bound violation max(d - up, lo - d) is <=
+ *                       0.1, every centre's V has the sign of vol_lo and max|x[a][3]| <= 0.1; else the row of x is zeros.  err [C] = E
+ *                       at the end of stage 2, max_violation [C] that largest violation, iterations / status [C][2] per stage.
+ *                       ws: pd_embed_conformers_workspace_numel(C, L) = C ((4 L)^2 + 8 * 4 L) doubles (the inverse Hessian; the
+ *                       tail of conformer c, at ws + c ((4 L)^2 + 32 L) + (4 L)^2, receives the point stage 2 ended at, [L][4],
+ *                       then its gradient, [L][4], accepted or not; the other 6 x 4 L doubles are not touched).
+ * No atomics, every sum in a fixed order: bit-identical from call to call, and a conformer's result does not depend on C or on its
+ * place among the C.  No allocation, no synchronisation.  A NULL required pointer, a misaligned pointer (8 bytes for doubles, 4 for
+ * float / int), C, L < 1, n_centres < 0, max_iters < 0, grad_tol < 0, box <= 0 or a short workspace: PD_ERR_ARG; L >
+ * PD_DG_MAX_ATOMS, n_centres > PD_DG_MAX_CENTRES, C > PD_DG_MAX_CONFORMERS: PD_ERR_UNSUPPORTED.  A rejected call writes nothing.   */
+#define PD_DG_MAX_ATOMS 128
+#define PD_DG_MAX_CENTRES 64
+#define PD_DG_MAX_CONFORMERS 4096
+int pd_embed_conformers_workspace_numel(int C, int L);
+int pd_dg_error_grad(const double* lo, const double* up, const int* centres, const double* vol_lo, const double* vol_hi,
+                     const double* pos, double w_chi, double w_4d, double* err, double* grad, int C, int L, int n_centres,
+                     void* stream);
+int pd_embed_conformers(const double* lo, const double* up, const int* centres, const double* vol_lo, const double* vol_hi,
+                        unsigned long long seed, int max_iters, double grad_tol, double box, double* ws, long long ws_numel,
+                        float* x, unsigned char* ok, double* err, double* max_violation, int* iterations, int* status,
+                        const double* start, int C, int L, int n_centres, void* stream);
 /* PoseBusters-style geometry checks of P poses of one ligand in its receptor, without leaving the device (validity.hip; ABI 11,
  * additive; the reference runs the `posebusters` package on the host through files, PhysDock/data/relaxation.py:24-50).  Tables,
  * built once per ligand (physdock_amd/validity.py): lig_idx [L] the ligand's atoms in a pose (any order, any place); radius [A] van

@@ -28,3 +28,4 @@ from .hydrogens import Hydrogens  # noqa: F401  (riding hydrogens of every pose 
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)
+from .conformers import ConformerEnsemble  # noqa: F401  (distance-geometry conformers of a ligand, the template pool; csrc/conformers.hip)

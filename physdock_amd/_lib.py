@@ -263,6 +263,9 @@ def _declare(L):
     sig("pd_buried_surface", p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p, i, i, i, i, i, i, p)       # ABI 11, additive (sasa.hip)
     sig("pd_pose_clusters_workspace_numel", i)                                               # ABI 11, additive (cluster.hip)
     sig("pd_pose_clusters", p, p, f, p, p, p, ll, p, p, p, p, p, p, p, p, p, i, p)
+    sig("pd_embed_conformers_workspace_numel", i, i)                                         # ABI 11, additive (conformers.hip)
+    sig("pd_dg_error_grad", p, p, p, p, p, p, d, d, p, p, i, i, i, p)
+    sig("pd_embed_conformers", p, p, p, p, p, ull, i, d, d, p, ll, p, p, p, p, p, p, p, i, i, i, p)
 
 
 def ptr(t):

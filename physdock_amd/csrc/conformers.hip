@@ -1,0 +1,413 @@
+// Distance-geometry conformers of one ligand on the device: C independent float64 minimisations of a bounds error function from
+// random four-dimensional coordinates (physdock_amd/conformers.py builds the bounds once per ligand; tests/conformers_ref.py is the
+// written definition of everything below, in float64 NumPy).  This is the package's own definition, not RDKit's ETKDG: no
+// metric-matrix eigen-solve, no torsion-knowledge terms.
+//
+//   E(x), x [L][4]  =  sum_{i<j} [d2 > up2] (d2 / up2 - 1)^2 + [d2 < lo2] (2 lo2 / (lo2 + d2) - 1)^2      d over four coordinates
+//                    + w_chi sum_centres viol(V)^2      V = (n1 - c) . ((n2 - c) x (n3 - c)) over the first three coordinates,
+//                                                       viol = the distance of V to [vol_lo, vol_hi]
+//                    + w_4d sum_a x[a][3]^2
+//
+// pd_embed_conformers: start uniform in [-box, box]^4 from Philox4x32-10 (key = seed, counter = (conformer, atom, 0, 0), u = (k +
+// 0.5) 2^-32 in double) or the caller's; stage 1 minimises with (w_chi, w_4d) = (1, 0.1), stage 2 with (0.2, 1.0), both with the
+// BFGS / lnsrch of mmff.hip (Numerical Recipes dfpmin, same constants, no gradient scaling) in dim = 4 L, stopping on max|g| <
+// grad_tol (status 0), after max_iters accepted steps (1) or when the line search finds no lower point (2), as pd_vina_refine;
+// then the fourth coordinate is dropped, the conformer centred and rounded once to fp32.  It is accepted when in 3-D and in double
+// the largest bound violation is <= 0.1 A, every centre has the sign of its reference volume and max|w| <= 0.1; a rejected row is
+// zeros.
+//
+// Mapping: one block of 256 threads per conformer, one launch.  An atom's row of pairs is dealt round-robin to `tpa` adjacent
+// lanes (the largest power of two <= 256 / L, at most 16), a butterfly adds their partial gradients and energies, the energy is
+// half the sum of the rows: no atomics, every sum in a fixed order, so a conformer's result is bit-identical from call to call and
+// does not depend on C or on its place among the C.  Every trial point of a line search is evaluated with its gradient (one pass
+// over the L (L - 1) ordered pairs), so an accepted first trial, the common case, costs one pass, not two.  The eight BFGS vectors
+// live in LDS (8 x 4 L doubles: 32 KiB at L = 128); the inverse Hessian ((4 L)^2 doubles, read by columns, coalesced since it is
+// kept exactly symmetric) lives in the caller's workspace, whose 8 x 4 L tail receives the final 4-D point and its gradient (the first
+// 2 x 4 L doubles; ConformerEnsemble.embed returns them as x4 / grad4, the rest is not touched).
+#include "common.h"
+#include "physdock_hip.h"
+
+namespace {
+
+constexpr int NT = 256;
+constexpr int DG_MAX_L = PD_DG_MAX_ATOMS, DG_MAX_CENTRES = PD_DG_MAX_CENTRES, DG_MAX_C = PD_DG_MAX_CONFORMERS;
+constexpr double FUNCTOL = 1e-4, MOVETOL = 1e-7, EPS_ = 3e-8, MAXSTEP = 100.0;
+constexpr double ACCEPT_VIOLATION = 0.1, ACCEPT_W = 0.1;
+static_assert(2 * DG_MAX_L <= NT, "error_grad gives every atom at least two lanes of the block in one pass");
+
+struct Tab {
+    const double* lo; const double* up; const int* centres; const double* vol_lo; const double* vol_hi;
+    int L, n_centres;
+};
+
+struct Philox {                                         // Philox4x32-10, the generator of sampler.hip (a copy: its bits stay put)
+    uint32_t k0, k1;
+    __device__ __forceinline__ void gen(uint32_t (&c)[4]) const {
+        uint32_t a = k0, b = k1;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ a, n1 = (uint32_t)p1;
+            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ b, n3 = (uint32_t)p0;
+            c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+            a += 0x9E3779B9u; b += 0xBB67AE85u;
+        }
+    }
+};
+
+// deterministic block reductions (fixed tree) of doubles; the result is returned to every thread
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ double block_max_d(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+__device__ __forceinline__ int threads_per_atom(int L) {
+    int t = 16;
+    while (t > 1 && t * L > NT) t >>= 1;
+    return t;
+}
+
+struct V3 { double x, y, z; };
+__device__ __forceinline__ V3 sub3(const double* p, int a, int c) { return {p[4 * a] - p[4 * c], p[4 * a + 1] - p[4 * c + 1], p[4 * a + 2] - p[4 * c + 2]}; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// E of the point p (LDS, [L][4]) - returned to every thread - and, if g != nullptr, its gradient g [L][4] (LDS or global).  Must be
+// called by all NT threads; ends with a barrier after which g is complete.
+__device__ double error_grad(const Tab& T, const double* p, double* g, double w_chi, double w_4d, double* red) {
+    const int L = T.L;
+    const int tpa = threads_per_atom(L), sub = threadIdx.x & (tpa - 1);
+    const int a = threadIdx.x / tpa;                     // one pass covers every atom: L <= PD_DG_MAX_ATOMS = NT / 2, so tpa >= 2 and tpa * L <= NT
+    double gx = 0.0, gy = 0.0, gz = 0.0, gw = 0.0, e = 0.0;
+    if (a < L) {
+        const double px = p[4 * a], py = p[4 * a + 1], pz = p[4 * a + 2], pw = p[4 * a + 3];
+        const double* lo_r = T.lo + a * L;
+        const double* up_r = T.up + a * L;
+        double e2 = 0.0;
+        for (int j = sub; j < L; j += tpa) {
+            if (j == a) continue;
+            const double dx = px - p[4 * j], dy = py - p[4 * j + 1], dz = pz - p[4 * j + 2], dw = pw - p[4 * j + 3];
+            const double d2 = dx * dx + dy * dy + dz * dz + dw * dw;
+            const double up = up_r[j], lo = lo_r[j];
+            const double up2 = up * up, lo2 = lo * lo;
+            double c = 0.0;
+            if (d2 > up2) {
+                const double t = d2 / up2 - 1.0;
+                e2 += t * t;
+                c = 4.0 * t / up2;
+            } else if (d2 < lo2) {
+                const double q = lo2 + d2;
+                const double s = 2.0 * lo2 / q - 1.0;
+                e2 += s * s;
+                c = -8.0 * s * lo2 / (q * q);
+            }
+            gx += c * dx; gy += c * dy; gz += c * dz; gw += c * dw;
+        }
+        e = 0.5 * e2;                                    // every pair is visited from both of its atoms
+        for (int q = sub; q < T.n_centres; q += tpa) {   // the centres this atom belongs to
+            const int c0 = T.centres[4 * q], n1 = T.centres[4 * q + 1], n2 = T.centres[4 * q + 2], n3 = T.centres[4 * q + 3];
+            if (a != c0 && a != n1 && a != n2 && a != n3) continue;
+            const V3 u = sub3(p, n1, c0), v = sub3(p, n2, c0), w = sub3(p, n3, c0);
+            const V3 vw = cross(v, w);
+            const double V = dot(u, vw);
+            const double vl = T.vol_lo[q], vh = T.vol_hi[q];
+            const double viol = V < vl ? V - vl : (V > vh ? V - vh : 0.0);
+            if (viol == 0.0) continue;
+            const double k = 2.0 * w_chi * viol;
+            const V3 wu = cross(w, u), uv = cross(u, v);
+            if (a == c0) {
+                e += w_chi * viol * viol;
+                gx -= k * (vw.x + wu.x + uv.x); gy -= k * (vw.y + wu.y + uv.y); gz -= k * (vw.z + wu.z + uv.z);
+            }
+            if (a == n1) { gx += k * vw.x; gy += k * vw.y; gz += k * vw.z; }
+            if (a == n2) { gx += k * wu.x; gy += k * wu.y; gz += k * wu.z; }
+            if (a == n3) { gx += k * uv.x; gy += k * uv.y; gz += k * uv.z; }
+        }
+        if (sub == 0) { e += w_4d * pw * pw; gw += 2.0 * w_4d * pw; }
+    }
+    for (int o = 1; o < tpa; o <<= 1) {                  // fixed tree over the atom's lanes (tpa <= 16: inside one wave)
+        gx += __shfl_xor(gx, o); gy += __shfl_xor(gy, o); gz += __shfl_xor(gz, o); gw += __shfl_xor(gw, o);
+        e += __shfl_xor(e, o);
+    }
+    if (g && sub == 0 && a < L) { g[4 * a] = gx; g[4 * a + 1] = gy; g[4 * a + 2] = gz; g[4 * a + 3] = gw; }
+    return block_sum_d(sub == 0 && a < L ? e : 0.0, red);
+}
+
+__global__ __launch_bounds__(NT) void dg_error_grad_kernel(const Tab T, const double* __restrict__ pos, double w_chi, double w_4d,
+                                                          double* __restrict__ err, double* __restrict__ grad) {
+    extern __shared__ double sm[];
+    double* sp = sm;                                     // [4 L]
+    double* red = sm + 4 * T.L;                          // [4]
+    const int b = blockIdx.x, dim = 4 * T.L;
+    for (int i = threadIdx.x; i < dim; i += NT) sp[i] = pos[(long long)b * dim + i];
+    __syncthreads();
+    const double e = error_grad(T, sp, grad ? grad + (long long)b * dim : nullptr, w_chi, w_4d, red);
+    if (threadIdx.x == 0 && err) err[b] = e;
+}
+
+// out[i] = sign * sum_j H[j][i] v[j] for the symmetric dim x dim matrix H (mmff.hip's matvec_sym; v and out in LDS).  Must be
+// called by all NT threads; ends with a barrier.
+__device__ void matvec_sym(const double* __restrict__ H, const double* v, double* out, double sign, int dim, double* part) {
+    const int tid = threadIdx.x;
+    const int parts = dim <= NT ? NT / dim : 1;
+    if (parts == 1) {
+        for (int i = tid; i < dim; i += NT) {
+            double h = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < dim; ++j) h += H[(long long)j * dim + i] * v[j];
+            out[i] = sign * h;
+        }
+        __syncthreads();
+        return;
+    }
+    const int jc = (dim + parts - 1) / parts;
+    double acc = 0.0;
+    if (tid < parts * dim) {
+        const int i = tid % dim, pt = tid / dim;
+        const int j0 = pt * jc, j1 = (j0 + jc < dim) ? j0 + jc : dim;
+#pragma unroll 4
+        for (int j = j0; j < j1; ++j) acc += H[(long long)j * dim + i] * v[j];
+    }
+    part[tid] = acc;
+    __syncthreads();
+    if (tid < dim) {
+        double h = 0.0;
+        for (int pt = 0; pt < parts; ++pt) h += part[pt * dim + tid];
+        out[tid] = sign * h;
+    }
+    __syncthreads();
+}
+
+struct Vecs { double *pos, *tp, *g, *gt, *xi, *dg, *hdg, *u, *red, *part; };
+
+// one stage: BFGS from v.pos (LDS) on E with the given weights; H in global memory.  Leaves the accepted point in v.pos, its
+// gradient in v.g and returns E there; it / st: accepted steps and status.
+__device__ double minimise(const Tab& T, const Vecs& v, double* __restrict__ H, double w_chi, double w_4d, int max_iters,
+                           double grad_tol, int& it_out, int& st_out) {
+    const int tid = threadIdx.x, dim = 4 * T.L;
+    double fp = error_grad(T, v.pos, v.g, w_chi, w_4d, v.red);
+    double ssum = 0.0, gmax = 0.0;
+    for (int i = tid; i < dim; i += NT) { v.xi[i] = -v.g[i]; ssum += v.pos[i] * v.pos[i]; gmax = fmax(gmax, fabs(v.g[i])); }
+    for (int e = tid; e < dim * dim; e += NT) H[e] = (e / dim == e % dim) ? 1.0 : 0.0;
+    ssum = block_sum_d(ssum, v.red);
+    gmax = block_max_d(gmax, v.red);
+    const double max_step = MAXSTEP * fmax(sqrt(ssum), (double)dim);
+    int it = 0, st = 1;
+    if (gmax < grad_tol) st = 0;
+    __syncthreads();
+    while (st == 1 && it < max_iters) {
+        // ---------------- the line search (Numerical Recipes lnsrch)
+        double s = 0.0;
+        for (int i = tid; i < dim; i += NT) s += v.xi[i] * v.xi[i];
+        s = sqrt(block_sum_d(s, v.red));
+        if (s > max_step)
+            for (int i = tid; i < dim; i += NT) v.xi[i] *= max_step / s;     // (each thread rescales the entries it reads below)
+        double slope = 0.0, test = 0.0;
+        for (int i = tid; i < dim; i += NT) {
+            slope += v.xi[i] * v.g[i];
+            test = fmax(test, fabs(v.xi[i]) / fmax(fabs(v.pos[i]), 1.0));
+        }
+        slope = block_sum_d(slope, v.red);
+        test = block_max_d(test, v.red);
+        if (!(slope < 0.0)) { st = 2; break; }
+        const double lam_min = MOVETOL / test;
+        double lam = 1.0, lam2 = 0.0, val2 = 0.0, fnew = fp;
+        bool ok = false;
+        for (int ls = 0; ls < 1000; ++ls) {
+            if (lam < lam_min) break;
+            for (int i = tid; i < dim; i += NT) v.tp[i] = v.pos[i] + lam * v.xi[i];
+            __syncthreads();
+            fnew = error_grad(T, v.tp, v.gt, w_chi, w_4d, v.red);
+            if (fnew - fp <= FUNCTOL * lam * slope) { ok = true; break; }
+            double tmp;
+            if (ls == 0) tmp = -slope / (2.0 * (fnew - fp - slope));
+            else {
+                const double rhs1 = fnew - fp - lam * slope, rhs2 = val2 - fp - lam2 * slope;
+                const double a = (rhs1 / (lam * lam) - rhs2 / (lam2 * lam2)) / (lam - lam2);
+                const double b = (-lam2 * rhs1 / (lam * lam) + lam * rhs2 / (lam2 * lam2)) / (lam - lam2);
+                if (a == 0.0) tmp = -slope / (2.0 * b);
+                else {
+                    const double disc = b * b - 3.0 * a * slope;
+                    if (disc < 0.0) tmp = 0.5 * lam;
+                    else if (b <= 0.0) tmp = (-b + sqrt(disc)) / (3.0 * a);
+                    else tmp = -slope / (b + sqrt(disc));
+                }
+                if (tmp > 0.5 * lam) tmp = 0.5 * lam;
+            }
+            lam2 = lam; val2 = fnew;
+            lam = fmax(tmp, 0.1 * lam);
+        }
+        if (!ok) { st = 2; break; }                      // "nothing was done": the accepted point stays
+        // ---------------- the step is accepted
+        double gm = 0.0;
+        for (int i = tid; i < dim; i += NT) {
+            v.xi[i] = v.tp[i] - v.pos[i]; v.pos[i] = v.tp[i];
+            v.dg[i] = v.gt[i] - v.g[i]; v.g[i] = v.gt[i];
+            gm = fmax(gm, fabs(v.gt[i]));
+        }
+        fp = fnew;
+        ++it;
+        gm = block_max_d(gm, v.red);                     // (its barriers also publish xi, pos, dg, g)
+        if (gm < grad_tol) { st = 0; break; }
+        // ---------------- BFGS update of the inverse Hessian
+        matvec_sym(H, v.dg, v.hdg, 1.0, dim, v.part);
+        double fac = 0.0, fae = 0.0, sdg = 0.0, sxi = 0.0;
+        for (int i = tid; i < dim; i += NT) {
+            fac += v.dg[i] * v.xi[i]; fae += v.dg[i] * v.hdg[i]; sdg += v.dg[i] * v.dg[i]; sxi += v.xi[i] * v.xi[i];
+        }
+        fac = block_sum_d(fac, v.red); fae = block_sum_d(fae, v.red); sdg = block_sum_d(sdg, v.red); sxi = block_sum_d(sxi, v.red);
+        if (fac > sqrt(EPS_ * sdg * sxi)) {
+            fac = 1.0 / fac;
+            const double fad = 1.0 / fae;
+            for (int i = tid; i < dim; i += NT) v.u[i] = fac * v.xi[i] - fad * v.hdg[i];
+            __syncthreads();
+            const unsigned udim = (unsigned)dim, n2 = udim * udim;
+            for (unsigned e = tid; e < n2; e += NT) {
+                const unsigned r = e / udim, c = e - r * udim;
+                const unsigned i = r < c ? r : c, j = r < c ? c : r;          // the (i <= j) element, mirrored
+                H[e] += (fac * v.xi[i]) * v.xi[j] - (fad * v.hdg[i]) * v.hdg[j] + (fae * v.u[i]) * v.u[j];
+            }
+            __threadfence_block();
+        }
+        __syncthreads();
+        matvec_sym(H, v.g, v.xi, -1.0, dim, v.part);
+    }
+    __syncthreads();
+    it_out = it; st_out = st;
+    return fp;
+}
+
+__global__ __launch_bounds__(NT) void embed_kernel(const Tab T, unsigned long long seed, int max_iters, double grad_tol, double box,
+                                                  double* __restrict__ ws, float* __restrict__ x, unsigned char* __restrict__ ok,
+                                                  double* __restrict__ err, double* __restrict__ max_violation,
+                                                  int* __restrict__ iterations, int* __restrict__ status,
+                                                  const double* __restrict__ start) {
+    extern __shared__ double sm[];
+    const int L = T.L, dim = 4 * L, c = blockIdx.x, tid = threadIdx.x;
+    Vecs v;
+    v.pos = sm; v.tp = sm + dim; v.g = sm + 2 * dim; v.gt = sm + 3 * dim; v.xi = sm + 4 * dim; v.dg = sm + 5 * dim;
+    v.hdg = sm + 6 * dim; v.u = sm + 7 * dim; v.red = sm + 8 * dim; v.part = v.red + 4;
+    double* H = ws + (long long)c * ((long long)dim * dim + 8ll * dim);
+    double* tail = H + (long long)dim * dim;
+    // ---------------- start
+    if (start) {
+        for (int i = tid; i < dim; i += NT) v.pos[i] = start[(long long)c * dim + i];
+    } else {
+        const Philox ph{(uint32_t)seed, (uint32_t)(seed >> 32)};
+        for (int a = tid; a < L; a += NT) {
+            uint32_t r[4] = {(uint32_t)c, (uint32_t)a, 0u, 0u};
+            ph.gen(r);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v.pos[4 * a + k] = (2.0 * (((double)r[k] + 0.5) * 0x1p-32) - 1.0) * box;
+        }
+    }
+    __syncthreads();
+    // ---------------- the two stages
+    int it0, st0, it1, st1;
+    minimise(T, v, H, 1.0, 0.1, max_iters, grad_tol, it0, st0);
+    const double e_end = minimise(T, v, H, 0.2, 1.0, max_iters, grad_tol, it1, st1);
+    for (int i = tid; i < dim; i += NT) { tail[i] = v.pos[i]; tail[dim + i] = v.g[i]; }
+    // ---------------- project: drop w, centre; accept in 3-D, in double
+    double sx = 0.0, sy = 0.0, sz = 0.0, wmax = 0.0;
+    for (int a = tid; a < L; a += NT) {
+        sx += v.pos[4 * a]; sy += v.pos[4 * a + 1]; sz += v.pos[4 * a + 2];
+        wmax = fmax(wmax, fabs(v.pos[4 * a + 3]));
+    }
+    sx = block_sum_d(sx, v.red) / (double)L; sy = block_sum_d(sy, v.red) / (double)L; sz = block_sum_d(sz, v.red) / (double)L;
+    wmax = block_max_d(wmax, v.red);
+    for (int a = tid; a < L; a += NT) {
+        v.tp[4 * a] = v.pos[4 * a] - sx; v.tp[4 * a + 1] = v.pos[4 * a + 1] - sy; v.tp[4 * a + 2] = v.pos[4 * a + 2] - sz;
+        v.tp[4 * a + 3] = 0.0;
+    }
+    __syncthreads();
+    double viol = 0.0;
+    for (int e = tid; e < L * L; e += NT) {
+        const int i = e / L, j = e - i * L;
+        if (j <= i) continue;
+        const double dx = v.tp[4 * i] - v.tp[4 * j], dy = v.tp[4 * i + 1] - v.tp[4 * j + 1], dz = v.tp[4 * i + 2] - v.tp[4 * j + 2];
+        const double d = sqrt(dx * dx + dy * dy + dz * dz);
+        viol = fmax(viol, fmax(d - T.up[e], T.lo[e] - d));
+    }
+    viol = block_max_d(viol, v.red);
+    double bad = 0.0;
+    for (int q = tid; q < T.n_centres; q += NT) {
+        const int c0 = T.centres[4 * q], n1 = T.centres[4 * q + 1], n2 = T.centres[4 * q + 2], n3 = T.centres[4 * q + 3];
+        const double V = dot(sub3(v.tp, n1, c0), cross(sub3(v.tp, n2, c0), sub3(v.tp, n3, c0)));
+        if (!(V * T.vol_lo[q] > 0.0)) bad = 1.0;
+    }
+    bad = block_max_d(bad, v.red);
+    const bool good = viol <= ACCEPT_VIOLATION && bad == 0.0 && wmax <= ACCEPT_W;
+    float* xo = x + (long long)c * L * 3;
+    for (int i = tid; i < 3 * L; i += NT) xo[i] = good ? (float)v.tp[4 * (i / 3) + i % 3] : 0.0f;
+    if (tid == 0) {
+        ok[c] = good ? 1 : 0;
+        err[c] = e_end; max_violation[c] = viol;
+        iterations[2 * c] = it0; iterations[2 * c + 1] = it1;
+        status[2 * c] = st0; status[2 * c + 1] = st1;
+    }
+}
+
+bool aligned(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }
+
+// PD_OK, or the code the tables and sizes earn
+int check_tables(const double* lo, const double* up, const int* centres, const double* vol_lo, const double* vol_hi, int C, int L,
+                 int n_centres) {
+    if (!lo || !up || C < 1 || L < 1 || n_centres < 0) return PD_ERR_ARG;
+    if (n_centres > 0 && (!centres || !vol_lo || !vol_hi)) return PD_ERR_ARG;
+    if (!aligned(lo, 8) || !aligned(up, 8) || !aligned(centres, 4) || !aligned(vol_lo, 8) || !aligned(vol_hi, 8)) return PD_ERR_ARG;
+    if (L > DG_MAX_L || n_centres > DG_MAX_CENTRES || C > DG_MAX_C) return PD_ERR_UNSUPPORTED;
+    return PD_OK;
+}
+
+}  // namespace
+
+PD_EXPORT int pd_embed_conformers_workspace_numel(int C, int L) {
+    if (C < 1 || L < 1) return PD_ERR_ARG;
+    if (L > DG_MAX_L || C > DG_MAX_C) return PD_ERR_UNSUPPORTED;
+    return C * (16 * L * L + 32 * L);                    // at most 4096 * 266240: an int holds it
+}
+
+PD_EXPORT int pd_dg_error_grad(const double* lo, const double* up, const int* centres, const double* vol_lo, const double* vol_hi,
+                               const double* pos, double w_chi, double w_4d, double* err, double* grad, int C, int L, int n_centres,
+                               void* stream) {
+    const int rc = check_tables(lo, up, centres, vol_lo, vol_hi, C, L, n_centres);
+    if (rc == PD_ERR_ARG) return rc;
+    if (!pos || (!err && !grad) || !aligned(pos, 8) || !aligned(err, 8) || !aligned(grad, 8)) return PD_ERR_ARG;
+    if (rc != PD_OK) return rc;
+    const Tab t = {lo, up, centres, vol_lo, vol_hi, L, n_centres};
+    hipLaunchKernelGGL(dg_error_grad_kernel, dim3(C), dim3(NT), (4 * (size_t)L + 4) * sizeof(double), (hipStream_t)stream, t, pos,
+                       w_chi, w_4d, err, grad);
+    return pd_check_launch();
+}
+
+PD_EXPORT int pd_embed_conformers(const double* lo, const double* up, const int* centres, const double* vol_lo, const double* vol_hi,
+                                  unsigned long long seed, int max_iters, double grad_tol, double box, double* ws,
+                                  long long ws_numel, float* x, unsigned char* ok, double* err, double* max_violation,
+                                  int* iterations, int* status, const double* start, int C, int L, int n_centres, void* stream) {
+    const int rc = check_tables(lo, up, centres, vol_lo, vol_hi, C, L, n_centres);
+    if (rc == PD_ERR_ARG) return rc;
+    if (!ws || !x || !ok || !err || !max_violation || !iterations || !status) return PD_ERR_ARG;
+    if (max_iters < 0 || !(grad_tol >= 0.0) || !(box > 0.0)) return PD_ERR_ARG;
+    if (!aligned(ws, 8) || !aligned(x, 4) || !aligned(err, 8) || !aligned(max_violation, 8) || !aligned(iterations, 4) ||
+        !aligned(status, 4) || !aligned(start, 8))
+        return PD_ERR_ARG;
+    if (rc != PD_OK) return rc;
+    if (ws_numel < (long long)pd_embed_conformers_workspace_numel(C, L)) return PD_ERR_ARG;
+    const Tab t = {lo, up, centres, vol_lo, vol_hi, L, n_centres};
+    const size_t lds = (32 * (size_t)L + 4 + NT) * sizeof(double);
+    hipLaunchKernelGGL(embed_kernel, dim3(C), dim3(NT), lds, (hipStream_t)stream, t, seed, max_iters, grad_tol, box, ws, x, ok, err,
+                       max_violation, iterations, status, start);
+    return pd_check_launch();
+}

@@ -15,7 +15,8 @@ What the reference does per system, and what is kept here:
     closest to this round's poses under the sampler's own soft distance-difference metric (device, pd_template_match);
   * top-up with rejected poses when fewer than one round's worth was accepted (:336-337), alignment of every kept
     pose into the ground-truth frame with pocket weights (:341-342) and ranking (ranking.py, :357-423).
-Conformer generation (ETKDG, :231-243) is an input (`ref_mol_poses [C,L,3]`).  `ref_mol` (an RDKit molecule, a
+Conformer generation (ETKDG, :231-243) is an input (`ref_mol_poses [C,L,3]`), or comes from `conformers=` (a
+`conformers.ConformerEnsemble`: distance geometry on the device, this package's own definition).  `ref_mol` (an RDKit molecule, a
 `physdock_amd.mmff.MMFFTerms` table, or any object with `sampler_kwargs={"relax_fn": ...}`) is handed to the sampler in
 every round as the reference does (:292), which switches on the relaxation branch below the adaptive threshold; as in the
 reference a molecule whose atom count differs from the crop's ligand is dropped and the ODE step scale becomes 1.5
@@ -169,6 +170,23 @@ def score_hydrogens(hydrogens, aligned, batch) -> dict:
     return res
 
 
+def conformer_pool(conformers, batch, seed, num_confs=128):
+    """redock(conformers=): (ref_mol_poses [n,L,3], log) - the accepted conformers of `conformers.embed(num_confs, seed)` on the batch's
+    device and their counts.  ValueError unless `conformers` is a `conformers.ConformerEnsemble` over the batch's ligand atoms, and
+    when no conformer is accepted."""
+    if not callable(getattr(conformers, "embed", None)) or not hasattr(conformers, "n_atoms"):
+        raise ValueError("conformers= takes a conformers.ConformerEnsemble of the ligand")
+    n = int(ligand_atom_mask(batch).sum())
+    if conformers.n_atoms != n:
+        raise ValueError(f"conformers= was built over {conformers.n_atoms} atoms, the batch's ligand holds {n}")
+    got = conformers.embed(num_confs, 0 if seed is None else int(seed), device=batch["x_gt"].device)
+    n_ok = int(got["poses"].shape[0])
+    if n_ok == 0:
+        raise ValueError(f"conformers=: none of the {num_confs} embedded conformers was accepted (largest bound violations from "
+                         f"{float(got['max_violation'].min()):.3f} A)")
+    return got["poses"], {"embedded": int(num_confs), "accepted": n_ok, "max_violation": got["max_violation"], "ok": got["ok"]}
+
+
 def score_surface(surface, aligned, batch) -> dict:
     """redock(surface=): {"surface": BuriedSurface.measure of the kept poses} and, when the batch carries the ground truth,
     "surface_gt": its measure of `x_gt` (one pose)"""
@@ -185,7 +203,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            align_weights: Optional[torch.Tensor] = None, ranking: bool = True, seed: Optional[int] = None,
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
-           interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None) -> dict:
+           interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
+           conformers=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -222,6 +241,11 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `hbonds` of the returned `poses` (the riding hydrogens, the rotatable polar ones turned to the partner, and the angle-tested
     hydrogen bonds per residue) and, as the batch carries `x_gt`, `hbond_recovery` = its `compare` of those bits with the ground
     truth's.  One built over another number of atoms raises ValueError before anything is sampled.  Nothing else changes.
+    `conformers` (a `conformers.ConformerEnsemble` of the ligand): with `physics_correction=True` and no `ref_mol_poses` the template
+    pool is the accepted conformers of its `embed(128, seed)` (distance geometry on the device, this package's own definition, not
+    ETKDG) and the result gains `conformers` = `embedded`, `accepted`, `max_violation`, `ok`; when none is accepted, or it was built over
+    another number of atoms, ValueError is raised before anything is sampled.  With `ref_mol_poses` given, or without physics
+    correction, it is not used.  Nothing else changes.
     `surface` (a `surface.BuriedSurface` of the system): the result gains `surface` = its `measure` of the returned `poses` (the
     ligand's solvent-accessible area free and in the complex, the buried fraction and its polar / apolar split, the area each residue
     loses to the ligand) and, as the batch carries `x_gt`, `surface_gt` = its `measure` of the ground truth (one pose).  Nothing else
@@ -242,6 +266,9 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     check_hydrogens(hydrogens, batch)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
+    pool_log = None
+    if physics_correction and ref_mol_poses is None and conformers is not None:
+        ref_mol_poses, pool_log = conformer_pool(conformers, batch, seed)
     if physics_correction and ref_mol_poses is None:
         raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                          "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
@@ -351,6 +378,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_ring_interactions(ring_interactions, aligned, batch))
     if hydrogens is not None:
         out.update(score_hydrogens(hydrogens, aligned, batch))
+    if pool_log is not None:
+        out["conformers"] = pool_log
     if surface is not None:
         out.update(score_surface(surface, aligned, batch))
     if refine is not None:
@@ -394,7 +423,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -486,12 +515,15 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None, hydrogens=None):
+                 ring_interactions=None, hydrogens=None, conformers=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
         check_hydrogens(hydrogens, batch)
+        self.pool_log = None
+        if physics_correction and ref_mol_poses is None and conformers is not None:
+            ref_mol_poses, self.pool_log = conformer_pool(conformers, batch, seed)
         if physics_correction and ref_mol_poses is None:
             raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                              "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
@@ -606,6 +638,8 @@ class _RedockState:
             out.update(score_ring_interactions(self.ring_interactions, aligned, self.batch))
         if self.hydrogens is not None:
             out.update(score_hydrogens(self.hydrogens, aligned, self.batch))
+        if self.pool_log is not None:
+            out["conformers"] = self.pool_log
         if self.surface is not None:
             out.update(score_surface(self.surface, aligned, self.batch))
         if self.refine is not None:
