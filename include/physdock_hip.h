@@ -751,6 +751,35 @@ int pd_hydrogen_bonds(const float* x, const float* x_h, const unsigned char* pla
                       unsigned char* bits, unsigned char* ligand_bits, unsigned char* h_bits, int* counts, int P, int A, int H, int L,
                       int R, void* stream);
 int pd_hydrogen_bonds_workspace(int P, int HP_l, int HP_r, int NA_r, int NA_l);
+/* SD file records of n ligand poses, formatted on the device (sdf.hip; ABI 11, additive; the CTfile V2000 specification, THIS
+ * PACKAGE'S definition - tests/sdf_ref.py writes it down - and not RDKit's bytes: no time stamp, no wedge flags, charges only as M  CHG).
+ * Tables, built once per ligand (physdock_amd/sdfio.py): tmpl [M] the molblock (title, program line, comment, counts line, one
+ * 69-column atom line per atom with 30 blank coordinate columns, bond lines, M  CHG lines, M  END, each with its newline); map [M]:
+ * < 0 copies tmpl[i], 30 s + col fills column col (0 .. 29) of template atom s; atom [na] the index into a pose of every template
+ * atom; hdr the item headers ">  <name>\n" one behind the other with hdr_start [K + 1]; decimals [K]: d = 0 .. 8 - values[k][p] [K][P]
+ * holds the bits of a float32 printed as Python's f"{v:.{d}f}" (nothing padded; "-0.0000", "nan", "inf", "-inf") -, < 0 - an int32
+ * printed as str(v).  Record r shows pose p = order[r] (order NULL: p = r; values are indexed by pose) and is
+ *   the molblock, column col of atom s holding character col % 10 of f"{v:10.4f}", v = x[p][atom[s]][col / 10];
+ *   per item: its header, the value's text, "\n\n";   then "$$$$\n".
+ * |v| 10^d is exact in float64 for a float32 v and d <= 8 (24 significand bits, at most 19 for 5^8), so rint of it is the
+ * round-half-even of the correctly rounded decimal conversion and every digit comes from that integer; the sign survives rounding to
+ * zero.  Counted in *overflow (the caller zeroes and reads it): a coordinate that is not finite or does not fit its 10 columns (after
+ * rounding above 99999.9999 or below -9999.9999), written as '*' in every column; a value with |v| 10^d >= 1e15, written as a single
+ * '*'; every number of a record whose order[r] is outside 0 .. P-1 (written from pose 0).
+ *   out [capacity]     the records one behind the other: a valid SD file as it stands
+ *   offsets [n + 1]    int64, record r is out[offsets[r] .. offsets[r + 1]); offsets[n] is the size of the file
+ *   vlen [n][K]        workspace: the length of every value's text
+ * fixed: the bytes of a record that are not a value's text (M, the headers, two newlines per item, 5 for "$$$$\n"); longest: fixed +
+ * the longest text of every value (18 for a float32, 11 for an int32); capacity >= n * longest.  Nothing is written at or behind
+ * out[capacity].  Three launches on the stream - measure (skipped when K == 0), an int64 exclusive scan in one block, one thread per
+ * byte -, no atomics but the overflow counter, no allocation.  PD_ERR_ARG: a required pointer is NULL (order may be; hdr, hdr_start,
+ * decimals, values, vlen may be when K == 0), n outside 1 .. 65535, K outside 0 .. PD_SDF_MAX_ITEMS, a size not positive, fixed <
+ * M + 5 + 6 K, longest < fixed + K, capacity < n * longest.                                                                          */
+#define PD_SDF_MAX_ITEMS 32
+int pd_sdf_format(const float* x, const unsigned char* tmpl, const int* map, const int* atom, const int* order,
+                  const unsigned char* hdr, const int* hdr_start, const int* decimals, const int* values, unsigned char* vlen,
+                  long long* offsets, unsigned char* out, int* overflow, int n, int P, int A, int M, int K, int fixed, int longest,
+                  long long capacity, void* stream);
 /* Ligand burial and interface area of P poses of one ligand in its receptor: solvent-accessible surface area by point counting
  * (sasa.hip; ABI 11, additive; Shrake & Rupley 1973, HEAVY ATOMS ONLY - absolute areas are not comparable with all-atom tools, and
  * the default radii and probe have not been validated on real complexes; the reference has no counterpart).  Tables, built once

@@ -29,3 +29,4 @@ from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)
 from .conformers import ConformerEnsemble  # noqa: F401  (distance-geometry conformers of a ligand, the template pool; csrc/conformers.hip)
+from .sdfio import SdfTemplate, parse_sdf  # noqa: F401  (ligand poses as SD file records, formatted on the device, and their reader; csrc/sdf.hip)

@@ -266,6 +266,7 @@ def _declare(L):
     sig("pd_embed_conformers_workspace_numel", i, i)                                         # ABI 11, additive (conformers.hip)
     sig("pd_dg_error_grad", p, p, p, p, p, p, d, d, p, p, i, i, i, p)
     sig("pd_embed_conformers", p, p, p, p, p, ull, i, d, d, p, ll, p, p, p, p, p, p, p, i, i, i, p)
+    sig("pd_sdf_format", p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, ll, p)       # ABI 11, additive (sdf.hip)
 
 
 def ptr(t):

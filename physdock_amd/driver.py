@@ -204,7 +204,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None) -> dict:
+           conformers=None, sdf=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -246,6 +246,12 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     ETKDG) and the result gains `conformers` = `embedded`, `accepted`, `max_violation`, `ok`; when none is accepted, or it was built over
     another number of atoms, ValueError is raised before anything is sampled.  With `ref_mol_poses` given, or without physics
     correction, it is not used.  Nothing else changes.
+    `sdf` (an `sdfio.SdfTemplate` of the ligand): the result gains `sdf` = its `format` of the returned `poses` in their order (`bytes`,
+    `offsets`, `n_records` on the device: an SD file as it stands, `SdfTemplate.split` cuts it into records) with the data items of what
+    the same call computed (`sdfio.redock_items`): always `pose`; with `confidence=` `ranking_confidence`; with `vina=` `vina_score`; with
+    `validity=` `valid`; with the ground truth and `ranking` `ligand_rmsd`; with `lddt_pli=` `lddt_pli`; with `clusters=` `cluster`.  With
+    `hydrogens=` given as well and a template made by `with_hydrogens` of that same object the records are protonated.  A template over
+    another number of atoms raises ValueError before anything is sampled.  Nothing else changes.
     `surface` (a `surface.BuriedSurface` of the system): the result gains `surface` = its `measure` of the returned `poses` (the
     ligand's solvent-accessible area free and in the complex, the buried fraction and its polar / apolar split, the area each residue
     loses to the ligand) and, as the batch carries `x_gt`, `surface_gt` = its `measure` of the ground truth (one pose).  Nothing else
@@ -262,8 +268,10 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     anything is sampled.  With `vina=` the modes carry `mean_score`, with `validity=` only valid poses lead and join, and when `ranking`
     ran `clusters["leader_rmsd"]` is the RMSD to `x_gt` of each mode's leader (NaN behind `n_clusters`).  Nothing else changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
+    from .sdfio import check_redock_sdf, score_sdf
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
     check_hydrogens(hydrogens, batch)
+    check_redock_sdf(sdf, batch, hydrogens)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
     pool_log = None
@@ -386,6 +394,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_refined(refine, aligned, validity, vina))
     if clusters is not None:
         out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
+    if sdf is not None:
+        out.update(score_sdf(sdf, aligned, out))
     if infer_meta_data is not None:
         from .pdbio import PdbTemplate
         out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
@@ -423,7 +433,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `sdf`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -515,12 +525,15 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None, hydrogens=None, conformers=None):
+                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
         check_hydrogens(hydrogens, batch)
+        from .sdfio import check_redock_sdf
+        check_redock_sdf(sdf, batch, hydrogens)
+        self.sdf = sdf
         self.pool_log = None
         if physics_correction and ref_mol_poses is None and conformers is not None:
             ref_mol_poses, self.pool_log = conformer_pool(conformers, batch, seed)
@@ -648,6 +661,9 @@ class _RedockState:
             from .clustering import cluster_kept_poses
             out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,
                                           ligand_symmetry=self.ligand_symmetry))
+        if self.sdf is not None:
+            from .sdfio import score_sdf
+            out.update(score_sdf(self.sdf, aligned, out))
         if self.infer_meta_data is not None:
             from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
