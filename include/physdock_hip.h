@@ -619,6 +619,43 @@ int pd_vina_refine(const float* x, const int* lig_idx, const unsigned char* type
                    const int* intra_atom, int n_intra, int max_iters, double grad_tol, double max_step, double* ws,
                    long long ws_numel, float* x_refined, double* energy_start, double* energy, int* iterations, int* evaluations,
                    int* status, double* moved, double* energy_trace, int P, int A, int L, int T, void* stream);
+/* Monte-Carlo global search of P poses, K independent chains each: perturb, minimise locally with the BFGS of pd_vina_refine,
+ * Metropolis test, keep the best (vina_refine.hip; ABI 11, additive; the loop every docking program that carries Vina's scoring
+ * function runs - here the package's own definition, tests/vina_search_ref.py, not a port of Vina's monte_carlo).  Tables, E, move
+ * and the minimiser as pd_vina_refine takes them.  For pose id q = pose0 + p and chain c, n = 6 + T:
+ *   start     y = the ligand rows of x[p]; (cur, E_cur) = descend(y) from H = I; best = cur, best_step = 0 - exactly pd_vina_refine's
+ *             result for the pose, in every chain
+ *   step m    m = 1 .. steps_total.  Philox4x32-10, key (seed lo, seed hi): counter (q, c, m, 0) gives w0 .. w3, counter (q, c, m, 1)
+ *             gives w4 as its first word; u_j = (w_j + 0.5) 2^-32 in float64; entity e = (w0 (2 + T)) >> 32 in integers.  s = 0, then
+ *             e == 0: s[0:3] = translate_amp (2 u_{1..3} - 1);  e == 1: s[3:6] = rotate_amp (2 u_{1..3} - 1) (rotation vector, radians);
+ *             e == 2 + k: s[6+k] = pi (2 u_1 - 1).  (new, E_new) = descend(move(cur, s)) from a fresh H = I.  Accept iff E_new is finite
+ *             and (E_new < E_cur or u_4 < exp((E_cur - E_new) / temperature)); temperature (kcal/mol) may be +inf.  On accept cur = new.
+ *             Independently: if E_new is finite and E_new < E_best, best = new and best_step = m.
+ * One launch runs the steps step0 + 1 .. step0 + n_steps (step0 == 0 also initialises the state with the start descent; step0 +
+ * n_steps <= steps_total, which sizes the traces).  The chain state lives in ws between launches, so a search cut into launches of
+ * any lengths is bit-identical to one launch; x, the tables, the settings and ws must be the same in all of them.  Outputs, written
+ * by every launch: x_chains [P][K][L][3] (fp32: each chain's best, rounded once), energy_chains, energy_start [P][K] (float64: E_best,
+ * E after the start), best_step, accepted, evaluations (of E, the start included) [P][K] (int32).  Optional (may be NULL):
+ * trace_energy [P][K][steps_total + 1] (float64: E after the start, then E_new of every step), trace_entity, trace_accept,
+ * trace_iterations, trace_status [P][K][steps_total] (int32: of step m at index m - 1; iterations and status of its descent).
+ * ws: pd_vina_search_workspace_numel(P, K, L, T) = P K ((6+T)^2 + 9 L + 8) doubles - a long long: 7 GB at the limits, a byte count
+ * no int holds (negative: the error code).  One block of 256 threads per (pose, chain), 6 L doubles of LDS, no atomics, no allocation, no
+ * synchronisation, every sum in the order pd_vina_refine uses: bit-identical from launch to launch, independent of P, K and pose0 +
+ * p's place in the batch.  pd_vina_search_select: best_chain [P] (the chain with the lowest energy_chains, the lowest index on a
+ * tie), energy [P], x_search [P][A][3] = x with the ligand rows of that chain; one block per pose.  NULL required pointers,
+ * misaligned pointers, sizes < 1, pose0 < 0, step0 < 0, n_steps < 0, step0 + n_steps > steps_total, temperature not > 0 (NaN
+ * included), an amplitude < 0 or NaN, a short workspace and pd_vina_refine's own rules: PD_ERR_ARG; L > 1024, T >
+ * PD_VINA_REFINE_MAX_TORSIONS, A > 2^22, K > 64, P K > 65535: PD_ERR_UNSUPPORTED.  A rejected call writes nothing.             */
+long long pd_vina_search_workspace_numel(int P, int K, int L, int T);
+int pd_vina_search(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
+                   const unsigned char* lig_active, const int* rot, const unsigned* rot_mask, const int* intra_start,
+                   const int* intra_atom, int n_intra, int max_iters, double grad_tol, double max_step, unsigned long long seed,
+                   int pose0, int step0, int n_steps, int steps_total, double temperature, double translate_amp, double rotate_amp,
+                   double* ws, long long ws_numel, float* x_chains, double* energy_chains, double* energy_start, int* best_step,
+                   int* accepted, int* evaluations, double* trace_energy, int* trace_entity, int* trace_accept,
+                   int* trace_iterations, int* trace_status, int P, int K, int A, int L, int T, void* stream);
+int pd_vina_search_select(const float* x, const int* lig_idx, const float* x_chains, const double* energy_chains, int* best_chain,
+                          double* energy, float* x_search, int P, int K, int A, int L, void* stream);
 /* Protein - ligand interaction fingerprint of P poses of one ligand in its receptor: which residues does a pose touch, and how?
  * (plif.hip; ABI 11, additive; per-residue fingerprints in the manner of PLIP and ProLIF, heavy atoms only - the reference has no
  * counterpart.)  Tables, built once per system (physdock_amd/interactions.py): lig_idx [L] the ligand's atoms in a pose;

@@ -146,10 +146,10 @@ SYMBOLS = {}
 
 
 def _declare(L):
-    def sig(name, *argtypes):
+    def sig(name, *argtypes, restype=C.c_int):
         fn = getattr(L, name)
         fn.argtypes = list(argtypes)
-        fn.restype = C.c_int
+        fn.restype = restype
         SYMBOLS[name] = fn
 
     i, f, p, ll = C.c_int, C.c_float, C.c_void_p, C.c_longlong
@@ -250,6 +250,10 @@ def _declare(L):
     sig("pd_vina_refine_workspace_numel", i, i, i)                                           # ABI 11, additive (vina_refine.hip)
     sig("pd_vina_refine_energy", p, p, p, p, p, p, p, p, p, i, p, p, p, p, p, i, i, i, i, p)
     sig("pd_vina_refine", p, p, p, p, p, p, p, p, p, i, i, d, d, p, ll, p, p, p, p, p, p, p, p, i, i, i, i, p)
+    sig("pd_vina_search_workspace_numel", i, i, i, i, restype=ll)                            # ABI 11, additive (vina_refine.hip)
+    sig("pd_vina_search", p, p, p, p, p, p, p, p, p, i, i, d, d, C.c_ulonglong, i, i, i, i, d, d, d, p, ll, p, p, p, p, p, p,
+        p, p, p, p, p, i, i, i, i, i, p)
+    sig("pd_vina_search_select", p, p, p, p, p, p, p, i, i, i, i, p)
     sig("pd_plif_fingerprint", p, p, p, p, p, p, p, C.POINTER(C.c_float), p, p, p, p, p, p, i, i, i, i, i, p)   # ABI 11, additive (plif.hip)
     sig("pd_plif_compare", p, p, i, p, p, p, p, p, i, i, p)
     sig("pd_plif_pairwise", p, i, p, i, i, p)

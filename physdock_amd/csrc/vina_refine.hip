@@ -24,6 +24,14 @@
 // coordinates of the BFGS vectors live one per lane, in every wave alike: dot products are butterflies and need no barrier.  The
 // inverse Hessian and the accepted conformation live in the caller's workspace (per pose (6+T)^2 + 3 L doubles), the conformation
 // under evaluation and its Cartesian gradient in LDS (6 L doubles).
+//
+// pd_vina_search is the Monte-Carlo loop around that minimiser (tests/vina_search_ref.py is its written definition): K independent
+// chains per pose, each perturbing one entity per step (translation, rotation or one torsion; Philox draws keyed by seed, pose id,
+// chain and step), minimising, applying the Metropolis test and keeping its best.  One block per (pose, chain) with the same LDS
+// layout, so that chains whose descents take different numbers of iterations never wait for one another; `descend` below is the one
+// BFGS both kernels call.  Per chain the workspace holds H, the descent's conformation, cur and best ((6+T)^2 + 9 L doubles) and the
+// chain's scalars, which is what makes a search resumable launch by launch.  LDS: 6 L doubles is 48 KB at L = 1024, with the 2 KB of
+// static scratch inside the 64 KB a workgroup may have; the chains are latency-bound float64 VALU work, as the refinement is.
 #include "common.h"
 #include "physdock_hip.h"
 
@@ -251,26 +259,19 @@ __global__ __launch_bounds__(NT) void vina_refine_energy_kernel(const Tab t, con
     }
 }
 
-__global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const float* __restrict__ x, float* __restrict__ x_out,
-                                                         double* __restrict__ ws, int max_iters, double grad_tol, double max_step,
-                                                         double* __restrict__ e_start, double* __restrict__ e_end,
-                                                         int* __restrict__ iterations, int* __restrict__ evaluations,
-                                                         int* __restrict__ status, double* __restrict__ moved,
-                                                         double* __restrict__ trace) {
-    extern __shared__ double sm[];
-    __shared__ double red[8], cen[3], gg[64], sx[64], sh[64], sv[64];
-    const int tid = threadIdx.x, lane = tid & 63, p = blockIdx.x, L = t.L, A = t.A, n = 6 + t.T;
-    double* y = sm;
-    double* gy = sm + 3 * L;
-    double* H = ws + (long long)p * ((long long)n * n + 3ll * L);         // inverse Hessian [n][n], kept exactly symmetric
-    double* pos = H + n * n;                                             // the accepted conformation [L][3]
-    const float* xp = x + (long long)p * A * 3;
-    float* ob = x_out + (long long)p * A * 3;
-    for (int i = tid; i < 3 * A; i += NT) ob[i] = xp[i];
-    for (int i = tid; i < 3 * L; i += NT) {
-        const double v = (double)xp[3 * t.lig_idx[i / 3] + i % 3];
-        pos[i] = v; y[i] = v;
-    }
+// The LDS of a block that minimises: the conformation under evaluation and its Cartesian gradient (3 L doubles each, dynamic), the
+// scratch of the reductions and of the BFGS update (static).
+struct Lds { double *y, *gy, *red, *cen, *gg, *sx, *sh, *sv; };
+struct Descent { double f0, fp; int it, nev, st; };                     // E at the start and the end, accepted steps, evaluations, status
+
+// The minimiser, shared by pd_vina_refine and pd_vina_search: descend from the conformation that `pos` (workspace, [L][3]) and s.y
+// (LDS) both hold, with a fresh H = I (workspace, [n][n]).  All NT threads; on return `pos` holds the accepted conformation (published
+// to the block), `d` the same values in every thread.  trace: this descent's max_iters + 1 energies, or NULL.
+__device__ __forceinline__ void descend(const Tab& t, const float* __restrict__ xp, double* __restrict__ H, double* __restrict__ pos,
+                                        const Lds& s_, int max_iters, double grad_tol, double max_step, double* __restrict__ trace,
+                                        Descent& d) {
+    double *y = s_.y, *gy = s_.gy, *red = s_.red, *cen = s_.cen, *gg = s_.gg, *sx = s_.sx, *sh = s_.sh, *sv = s_.sv;
+    const int tid = threadIdx.x, lane = tid & 63, L = t.L, n = 6 + t.T;
     for (int e = tid; e < n * n; e += NT) H[e] = (e / n == e % n) ? 1.0 : 0.0;
     __syncthreads();
     double ei, ea;
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
     double xi = -g;
     const double f0 = fp;
     int it = 0, nev = 1, st = 1;
-    if (trace && tid == 0) trace[(long long)p * (max_iters + 1)] = fp;
+    if (trace && tid == 0) trace[0] = fp;
     if (wave_max_d(fabs(g)) < grad_tol) st = 0;
     while (st == 1 && it < max_iters) {
         // ---------------- the line search (Numerical Recipes lnsrch)
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
         for (int i = tid; i < 3 * L; i += NT) pos[i] = y[i];
         fp = fnew;
         ++it;
-        if (trace && tid == 0) trace[(long long)p * (max_iters + 1) + it] = fp;
+        if (trace && tid == 0) trace[it] = fp;
         const double step = lam * xi, g_old = g;
         generalised(t, y, gy, cen, gg);                                  // (its barriers also publish pos)
         g = lane < n ? gg[lane] : 0.0;
@@ -360,7 +361,31 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
     }
     __syncthreads();
     if (trace && tid == 0)
-        for (int k = it + 1; k <= max_iters; ++k) trace[(long long)p * (max_iters + 1) + k] = fp;
+        for (int k = it + 1; k <= max_iters; ++k) trace[k] = fp;
+    d.f0 = f0; d.fp = fp; d.it = it; d.nev = nev; d.st = st;
+}
+
+__global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const float* __restrict__ x, float* __restrict__ x_out,
+                                                         double* __restrict__ ws, int max_iters, double grad_tol, double max_step,
+                                                         double* __restrict__ e_start, double* __restrict__ e_end,
+                                                         int* __restrict__ iterations, int* __restrict__ evaluations,
+                                                         int* __restrict__ status, double* __restrict__ moved,
+                                                         double* __restrict__ trace) {
+    extern __shared__ double sm[];
+    __shared__ double red[8], cen[3], gg[64], sx[64], sh[64], sv[64];
+    const int tid = threadIdx.x, lane = tid & 63, p = blockIdx.x, L = t.L, A = t.A, n = 6 + t.T;
+    const Lds s = {sm, sm + 3 * L, red, cen, gg, sx, sh, sv};
+    double* H = ws + (long long)p * ((long long)n * n + 3ll * L);         // inverse Hessian [n][n], kept exactly symmetric
+    double* pos = H + n * n;                                             // the accepted conformation [L][3]
+    const float* xp = x + (long long)p * A * 3;
+    float* ob = x_out + (long long)p * A * 3;
+    for (int i = tid; i < 3 * A; i += NT) ob[i] = xp[i];
+    for (int i = tid; i < 3 * L; i += NT) {
+        const double v = (double)xp[3 * t.lig_idx[i / 3] + i % 3];
+        pos[i] = v; s.y[i] = v;
+    }
+    Descent d;
+    descend(t, xp, H, pos, s, max_iters, grad_tol, max_step, trace ? trace + (long long)p * (max_iters + 1) : nullptr, d);
     double d2 = 0.0;
     for (int i = tid; i < L; i += NT) {
         const int a = t.lig_idx[i];
@@ -372,10 +397,156 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
     if (lane == 0) red[tid >> 6] = d2;
     __syncthreads();
     if (tid == 0) {
-        e_start[p] = f0; e_end[p] = fp;
-        iterations[p] = it; evaluations[p] = nev; status[p] = st;
+        e_start[p] = d.f0; e_end[p] = d.fp;
+        iterations[p] = d.it; evaluations[p] = d.nev; status[p] = d.st;
         moved[p] = sqrt((((red[0] + red[1]) + red[2]) + red[3]) / (double)L);
     }
+}
+
+// ------------------------------------------------------------------ the Monte-Carlo search (tests/vina_search_ref.py is its definition)
+struct Philox {                                         // Philox4x32-10, the generator of sampler.hip and conformers.hip (a copy: its bits stay put)
+    uint32_t k0, k1;
+    __device__ __forceinline__ void gen(uint32_t (&c)[4]) const {
+        uint32_t a = k0, b = k1;
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ a, n1 = (uint32_t)p1;
+            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ b, n3 = (uint32_t)p0;
+            c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+            a += 0x9E3779B9u; b += 0xBB67AE85u;
+        }
+    }
+};
+
+constexpr int VS_SCALARS = 8;                                            // E_cur, E_best, E_start, best_step, accepted, evaluations, 2 spare
+constexpr int VS_MAX_K = 64, VS_MAX_BLOCKS = 65535;
+constexpr double VS_PI = 3.14159265358979323846;
+
+struct SearchArgs {
+    unsigned long long seed;
+    int pose0, step0, n_steps, steps_total, K, max_iters;
+    double grad_tol, max_step, temperature, translate_amp, rotate_amp;
+    float* x_chains; double* energy_chains; double* energy_start; int* best_step; int* accepted; int* evaluations;
+    double* trace_energy; int* trace_entity; int* trace_accept; int* trace_iterations; int* trace_status;
+};
+
+__device__ __forceinline__ long long vs_stride(int L, int T) { return (long long)(6 + T) * (6 + T) + 9ll * L + VS_SCALARS; }
+
+// One block per (pose, chain): the chain runs its steps step0 + 1 .. step0 + n_steps on its own (step 0, the start descent, when
+// step0 == 0).  Its state - cur, best [L][3], E_cur, E_best, E_start and the counters - lives in the workspace between launches, and
+// the draws depend on (seed, pose id, chain, step) alone, so a search cut into launches is the same search.  Every decision is taken
+// by all threads alike from values that are the same in every thread.
+__global__ __launch_bounds__(NT) void vina_search_kernel(const Tab t, const float* __restrict__ x, double* __restrict__ ws,
+                                                         const SearchArgs a) {
+    extern __shared__ double sm[];
+    __shared__ double red[8], cen[3], gg[64], sx[64], sh[64], sv[64];
+    const int tid = threadIdx.x, lane = tid & 63, L = t.L, A = t.A, n = 6 + t.T;
+    const int p = blockIdx.x / a.K, c = blockIdx.x - p * a.K;
+    const Lds s = {sm, sm + 3 * L, red, cen, gg, sx, sh, sv};
+    double* H = ws + (long long)blockIdx.x * vs_stride(L, t.T);
+    double* pos = H + n * n;                                             // the descent's accepted conformation
+    double* cur = pos + 3 * L;
+    double* best = cur + 3 * L;
+    double* sc = best + 3 * L;
+    const float* xp = x + (long long)p * A * 3;
+    const long long pc = blockIdx.x;
+    const Philox ph{(uint32_t)a.seed, (uint32_t)(a.seed >> 32)};
+    const uint32_t q = (uint32_t)(a.pose0 + p);
+    double e_cur = 0.0, e_best = 0.0, e_start = 0.0;
+    int best_step = 0, accepted = 0, evaluations = 0;
+    if (a.step0 > 0) {
+        e_cur = sc[0]; e_best = sc[1]; e_start = sc[2];
+        best_step = (int)sc[3]; accepted = (int)sc[4]; evaluations = (int)sc[5];
+    }
+    for (int m = a.step0 > 0 ? a.step0 + 1 : 0; m <= a.step0 + a.n_steps; ++m) {
+        int entity = 0;
+        double u4 = 0.0;
+        if (m == 0) {
+            for (int i = tid; i < 3 * L; i += NT) {
+                const double v = (double)xp[3 * t.lig_idx[i / 3] + i % 3];
+                pos[i] = v; s.y[i] = v;
+            }
+        } else {
+            uint32_t w[4] = {q, (uint32_t)c, (uint32_t)m, 0u}, w4[4] = {q, (uint32_t)c, (uint32_t)m, 1u};
+            ph.gen(w); ph.gen(w4);
+            entity = (int)(((uint64_t)w[0] * (uint64_t)(2 + t.T)) >> 32);
+            const double u1 = ((double)w[1] + 0.5) * 0x1p-32, u2 = ((double)w[2] + 0.5) * 0x1p-32, u3 = ((double)w[3] + 0.5) * 0x1p-32;
+            u4 = ((double)w4[0] + 0.5) * 0x1p-32;
+            double sl = 0.0;                                             // this lane's coordinate of the proposal s
+            if (entity < 2) {
+                const int k = lane - 3 * entity;
+                const double amp = entity == 0 ? a.translate_amp : a.rotate_amp;
+                if (k >= 0 && k < 3) sl = amp * (2.0 * (k == 0 ? u1 : (k == 1 ? u2 : u3)) - 1.0);
+            } else if (lane == 6 + entity - 2) {
+                sl = VS_PI * (2.0 * u1 - 1.0);
+            }
+            move(t, cur, s.y, cen, 1.0, sl);                             // y = move(cur, s)
+            for (int i = tid; i < 3 * L; i += NT) pos[i] = s.y[i];
+        }
+        Descent d;
+        descend(t, xp, H, pos, s, a.max_iters, a.grad_tol, a.max_step, nullptr, d);
+        evaluations += d.nev;
+        const double e_new = d.fp;
+        const bool finite = isfinite(e_new);
+        bool acc, nb;
+        if (m == 0) {
+            acc = true; nb = true;
+            e_start = e_new;
+        } else {
+            acc = finite && (e_new < e_cur || u4 < exp((e_cur - e_new) / a.temperature));
+            nb = finite && e_new < e_best;
+            if (acc) ++accepted;
+        }
+        if (acc) {
+            e_cur = e_new;
+            for (int i = tid; i < 3 * L; i += NT) cur[i] = pos[i];
+        }
+        if (nb) {
+            e_best = e_new; best_step = m;
+            for (int i = tid; i < 3 * L; i += NT) best[i] = pos[i];
+        }
+        if (tid == 0) {
+            if (a.trace_energy) a.trace_energy[pc * (a.steps_total + 1) + m] = e_new;
+            if (m > 0) {
+                const long long o = pc * a.steps_total + (m - 1);
+                if (a.trace_entity) a.trace_entity[o] = entity;
+                if (a.trace_accept) a.trace_accept[o] = acc ? 1 : 0;
+                if (a.trace_iterations) a.trace_iterations[o] = d.it;
+                if (a.trace_status) a.trace_status[o] = d.st;
+            }
+        }
+        __syncthreads();                                                 // cur is published before the next proposal reads it
+    }
+    for (int i = tid; i < 3 * L; i += NT) a.x_chains[pc * 3 * L + i] = (float)best[i];   // each thread reads what it wrote, or an earlier launch did
+    if (tid == 0) {
+        sc[0] = e_cur; sc[1] = e_best; sc[2] = e_start;
+        sc[3] = (double)best_step; sc[4] = (double)accepted; sc[5] = (double)evaluations;
+        a.energy_chains[pc] = e_best; a.energy_start[pc] = e_start;
+        a.best_step[pc] = best_step; a.accepted[pc] = accepted; a.evaluations[pc] = evaluations;
+    }
+}
+
+// One block per pose: the chain with the lowest energy (the lowest index on a tie), and x with that chain's ligand rows.
+__global__ __launch_bounds__(NT) void vina_search_select_kernel(const float* __restrict__ x, const int* __restrict__ lig_idx,
+                                                                const float* __restrict__ x_chains,
+                                                                const double* __restrict__ energy_chains, int* __restrict__ best_chain,
+                                                                double* __restrict__ energy, float* __restrict__ x_search, int K,
+                                                                int A, int L) {
+    const int tid = threadIdx.x, p = blockIdx.x;
+    int b = 0;
+    double e = energy_chains[(long long)p * K];
+    for (int c = 1; c < K; ++c) {                                        // every thread alike
+        const double v = energy_chains[(long long)p * K + c];
+        if (v < e) { e = v; b = c; }
+    }
+    const float* xp = x + (long long)p * A * 3;
+    float* ob = x_search + (long long)p * A * 3;
+    for (int i = tid; i < 3 * A; i += NT) ob[i] = xp[i];
+    __syncthreads();                                                     // the ligand rows are overwritten after the copy
+    const float* yb = x_chains + ((long long)p * K + b) * 3 * L;
+    for (int i = tid; i < 3 * L; i += NT) ob[3 * lig_idx[i / 3] + i % 3] = yb[i];
+    if (tid == 0) { best_chain[p] = b; energy[p] = e; }
 }
 
 bool aligned(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }
@@ -434,5 +605,53 @@ PD_EXPORT int pd_vina_refine(const float* x, const int* lig_idx, const unsigned 
     const Tab t = {lig_idx, type, rec_mask, lig_active, rot, rot_mask, intra_start, intra_atom, A, L, T};
     hipLaunchKernelGGL(vina_refine_kernel, dim3(P), dim3(NT), 6 * (size_t)L * sizeof(double), (hipStream_t)stream, t, x, x_refined, ws,
                        max_iters, grad_tol, max_step, energy_start, energy, iterations, evaluations, status, moved, energy_trace);
+    return pd_check_launch();
+}
+
+PD_EXPORT long long pd_vina_search_workspace_numel(int P, int K, int L, int T) {
+    if (P <= 0 || K <= 0 || L <= 0 || T < 0) return PD_ERR_ARG;
+    if (L > VR_MAX_L || T > VR_MAX_T || K > VS_MAX_K || (long long)P * K > VS_MAX_BLOCKS) return PD_ERR_UNSUPPORTED;
+    return (long long)P * K * ((long long)(6 + T) * (6 + T) + 9ll * L + VS_SCALARS);
+}
+
+PD_EXPORT int pd_vina_search(const float* x, const int* lig_idx, const unsigned char* type, const unsigned char* rec_mask,
+                             const unsigned char* lig_active, const int* rot, const unsigned* rot_mask, const int* intra_start,
+                             const int* intra_atom, int n_intra, int max_iters, double grad_tol, double max_step,
+                             unsigned long long seed, int pose0, int step0, int n_steps, int steps_total, double temperature,
+                             double translate_amp, double rotate_amp, double* ws, long long ws_numel, float* x_chains,
+                             double* energy_chains, double* energy_start, int* best_step, int* accepted, int* evaluations,
+                             double* trace_energy, int* trace_entity, int* trace_accept, int* trace_iterations, int* trace_status,
+                             int P, int K, int A, int L, int T, void* stream) {
+    const int rc = check_tables(x, lig_idx, type, rec_mask, lig_active, rot, rot_mask, intra_start, intra_atom, n_intra, P, A, L, T);
+    if (rc == PD_ERR_ARG) return rc;
+    if (!ws || !x_chains || !energy_chains || !energy_start || !best_step || !accepted || !evaluations) return PD_ERR_ARG;
+    if (max_iters < 0 || !(grad_tol >= 0.0) || !(max_step > 0.0)) return PD_ERR_ARG;
+    if (K < 1 || pose0 < 0 || step0 < 0 || n_steps < 0 || steps_total < 0 || (long long)step0 + n_steps > steps_total) return PD_ERR_ARG;
+    if (!(temperature > 0.0) || !(translate_amp >= 0.0) || !(rotate_amp >= 0.0)) return PD_ERR_ARG;
+    if (!aligned(ws, 8) || !aligned(x_chains, 4) || !aligned(energy_chains, 8) || !aligned(energy_start, 8) || !aligned(best_step, 4) ||
+        !aligned(accepted, 4) || !aligned(evaluations, 4) || !aligned(trace_energy, 8) || !aligned(trace_entity, 4) ||
+        !aligned(trace_accept, 4) || !aligned(trace_iterations, 4) || !aligned(trace_status, 4))
+        return PD_ERR_ARG;
+    if (rc != PD_OK) return rc;
+    if (K > VS_MAX_K || (long long)P * K > VS_MAX_BLOCKS || (long long)pose0 + P > 0x7fffffffll) return PD_ERR_UNSUPPORTED;
+    if (ws_numel < pd_vina_search_workspace_numel(P, K, L, T)) return PD_ERR_ARG;
+    const Tab t = {lig_idx, type, rec_mask, lig_active, rot, rot_mask, intra_start, intra_atom, A, L, T};
+    const SearchArgs a = {seed, pose0, step0, n_steps, steps_total, K, max_iters, grad_tol, max_step, temperature, translate_amp,
+                          rotate_amp, x_chains, energy_chains, energy_start, best_step, accepted, evaluations, trace_energy,
+                          trace_entity, trace_accept, trace_iterations, trace_status};
+    hipLaunchKernelGGL(vina_search_kernel, dim3(P * K), dim3(NT), 6 * (size_t)L * sizeof(double), (hipStream_t)stream, t, x, ws, a);
+    return pd_check_launch();
+}
+
+PD_EXPORT int pd_vina_search_select(const float* x, const int* lig_idx, const float* x_chains, const double* energy_chains,
+                                    int* best_chain, double* energy, float* x_search, int P, int K, int A, int L, void* stream) {
+    if (!x || !lig_idx || !x_chains || !energy_chains || !best_chain || !energy || !x_search) return PD_ERR_ARG;
+    if (P <= 0 || K <= 0 || A <= 0 || L <= 0) return PD_ERR_ARG;
+    if (!aligned(x, 4) || !aligned(lig_idx, 4) || !aligned(x_chains, 4) || !aligned(energy_chains, 8) || !aligned(best_chain, 4) ||
+        !aligned(energy, 8) || !aligned(x_search, 4))
+        return PD_ERR_ARG;
+    if (L > VR_MAX_L || A > VR_MAX_A || K > VS_MAX_K || P > VS_MAX_BLOCKS) return PD_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(vina_search_select_kernel, dim3(P), dim3(NT), 0, (hipStream_t)stream, x, lig_idx, x_chains, energy_chains, best_chain,
+                       energy, x_search, K, A, L);
     return pd_check_launch();
 }

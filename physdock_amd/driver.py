@@ -131,6 +131,29 @@ def score_refined(refine, aligned, validity, vina, refine_kwargs=None) -> dict:
     return res
 
 
+def check_search(search, refine) -> None:
+    """redock(search=): raise ValueError unless `search` is None, False, True or a dict of `VinaRefine.search` keyword arguments, and
+    when it asks for a search without `refine=` - before anything is sampled"""
+    if search is None or search is False:
+        return
+    if search is not True and not isinstance(search, dict):
+        raise ValueError(f"search= takes True or a dict of VinaRefine.search keyword arguments, got {type(search).__name__}")
+    if refine is None:
+        raise ValueError("search= needs refine= (the system's refine.VinaRefine)")
+
+
+def score_searched(search, refine, aligned, validity, vina) -> dict:
+    """redock(search=): {"searched": VinaRefine.search of the kept poses} - with `validity=` also searched["validity"], its check of
+    `x_search`, and with `vina=` "order_vina_searched": the poses' ids by their score after the search, best first"""
+    from .ranking import rank_by_score
+    res = {"searched": refine.search(aligned, **(search if isinstance(search, dict) else {}))}
+    if validity is not None:
+        res["searched"]["validity"] = validity.check(res["searched"]["x_search"])
+    if vina is not None:
+        res["order_vina_searched"] = rank_by_score({"score": res["searched"]["score"]})
+    return res
+
+
 def score_interactions(interactions, aligned, batch) -> dict:
     """redock(interactions=): {"interactions": InteractionFingerprint.fingerprint of the kept poses} and, when the batch carries the
     ground truth, "interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
@@ -204,7 +227,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None, sdf=None) -> dict:
+           conformers=None, sdf=None, search=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -260,6 +283,12 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     torsion minimisation in the rigid receptor: `x_refined`, energies, scores before and after, iterations, status, `moved`), with
     `validity=` also `refined["validity"]` (the check of `x_refined`) and with `vina=` also `order_vina_refined` (`rank_by_score` of
     the refined scores).  The returned `poses` are not replaced; nothing else changes.
+    `search` (True for the defaults, or a dict of `VinaRefine.search` keyword arguments; needs `refine=`, a missing one raises
+    ValueError before anything is sampled): the result gains `searched` = `refine.search` of the returned `poses` (the Monte-Carlo
+    global search in the rigid receptor: `x_search`, `energy`, `best_chain`, every chain's best and its counts, scores before and
+    after, `moved`), with `validity=` also `searched["validity"]` (the check of `x_search`) and with `vina=` also
+    `order_vina_searched` (`rank_by_score` of the scores after the search).  The returned `poses` are not replaced; nothing else
+    changes.
     `clusters` (a `clustering.PoseClusters` spec): the result gains `clusters` = the binding modes of the returned `poses`
     (`PoseClusters.cluster`: labels, leaders, medoids, sizes, radii, spreads, `dist`).  `metric="rmsd"` clusters their pairwise ligand RMSD
     (`ranking["dist"]` when `ranking` ran, else `pairwise_ligand_rmsd` with `ligand_symmetry=`), `metric="interactions"` clusters 1 -
@@ -270,6 +299,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     from .clustering import check_redock_prerequisites, cluster_kept_poses
     from .sdfio import check_redock_sdf, score_sdf
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+    check_search(search, refine)
     check_hydrogens(hydrogens, batch)
     check_redock_sdf(sdf, batch, hydrogens)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -392,6 +422,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_surface(surface, aligned, batch))
     if refine is not None:
         out.update(score_refined(refine, aligned, validity, vina))
+    if search:
+        out.update(score_searched(search, refine, aligned, validity, vina))
     if clusters is not None:
         out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
     if sdf is not None:
@@ -433,7 +465,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `sdf`, `surface`, `refine`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -525,11 +557,12 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None):
+                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+        check_search(search, refine)
         check_hydrogens(hydrogens, batch)
         from .sdfio import check_redock_sdf
         check_redock_sdf(sdf, batch, hydrogens)
@@ -566,6 +599,7 @@ class _RedockState:
         self.hydrogens = hydrogens
         self.surface = surface
         self.refine = refine
+        self.search = search
         self.clusters = clusters
 
     def round_args(self, rnd):
@@ -657,6 +691,8 @@ class _RedockState:
             out.update(score_surface(self.surface, aligned, self.batch))
         if self.refine is not None:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
+        if self.search:
+            out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
         if self.clusters is not None:
             from .clustering import cluster_kept_poses
             out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,

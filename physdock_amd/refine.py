@@ -15,7 +15,24 @@ for the ligand's internal geometry is needed, and the 6 + T coordinates replace 
 It stops when the largest component of the generalised gradient falls below `grad_tol` (status 0), after `max_iters` accepted steps
 (status 1), or when the line search finds no lower point (status 2).  **Two caveats.**  The weights are Vina's published ones,
 unvalidated on real complexes and not fitted to this model's poses, as for `VinaScore`; and the receptor is rigid.  Out of scope:
-receptor flexibility, a global search (Monte Carlo restarts), Cartesian relaxation.
+receptor flexibility, Cartesian relaxation.
+
+Does a better pose exist within a few angstrom?  `search(x_pred)` asks the same energy with the loop every docking program that
+carries Vina's scoring function runs (kernel `pd_vina_search`, one block per (pose, chain); tests/vina_search_ref.py is the written
+definition - the package's own, not a port of Vina's `monte_carlo`):
+
+    start                       every chain of a pose begins at `refine`'s result for that pose
+    step m = 1 .. steps         Philox4x32-10 keyed by `seed`, counters (pose id, chain, m, 0 / 1), picks one entity - the translation,
+                                the rotation or one torsion - and draws its perturbation from a cube: +- translate_amp A, a rotation
+                                vector within +- rotate_amp rad, a torsion within +- pi; the perturbed conformation is minimised
+                                from a fresh H = I; Metropolis: accepted when E falls, else with probability
+                                exp(-(E_new - E_cur) / temperature); the lowest minimum seen is kept whatever the test said
+    per pose                    the chain with the lowest energy (the lowest index on a tie)
+
+The chains' state lives on the device between launches and the draws depend on (seed, pose id, chain, step) alone, so cutting the
+steps (`steps_per_launch`) or the poses into launches changes no bit.  Not Vina's search: cube draws instead of its ball, no Hessian
+carried over between steps, no final merging of modes (`PoseClusters.binding_modes` on `x_chains` gives the modes).  A lower Vina
+energy is not a lower RMSD.  Out of scope: grid maps, receptor flexibility, feeding the search back into the sampler.
 
 `VinaRefine` holds one system's tables, built once on the host; `refine(x_pred)` and `energy(x_pred)` return device tensors and never
 synchronise.  `driver.redock(..., refine=)` reports the refinement of the kept poses; the returned poses are not replaced.
@@ -36,6 +53,9 @@ __all__ = ["VinaRefine", "rotatable_bonds", "torsion_table", "intra_pairs", "MAX
 MAX_TORSIONS = 58
 #: `status` of a refined pose
 STATUS = ("converged", "max_iters", "line_search")
+#: `search`: the most chains per pose, and the most (pose, chain) blocks of one launch - more poses go in several launches
+MAX_CHAINS = 64
+MAX_SEARCH_BLOCKS = 65535
 
 
 def _adjacency(n, bonds):
@@ -221,6 +241,86 @@ class VinaRefine:
                                     ops.ptr(out.get("energy_trace")), P, A, L, T, ops.stream()), "pd_vina_refine")
         out["score_start"] = self.vina.score(x)["score"]
         out["score"] = self.vina.score(out["x_refined"])["score"]
+        return out
+
+    def default_rotate_amp(self, x_pred: torch.Tensor, translate_amp: float = 2.0) -> float:
+        """`search`'s default rotation amplitude (rad): translate_amp / max(1, r_gyr), r_gyr the radius of gyration (A) of the active
+        ligand atoms in the FIRST pose - Vina's scaling.  One small read-back."""
+        lig = torch.from_numpy(np.asarray(self.vina.ligand_idx)[np.asarray(self.vina.lig_active) > 0].astype(np.int64)).to(x_pred.device)
+        y = x_pred[0].double()[lig]
+        r_gyr = float(((y - y.mean(0)) ** 2).sum(-1).mean().sqrt()) if len(lig) else 0.0
+        return float(translate_amp) / max(1.0, r_gyr)
+
+    def search(self, x_pred: torch.Tensor, chains: int = 8, steps: int = 20, seed: int = 0, temperature: float = 1.2,
+               translate_amp: float = 2.0, rotate_amp: Optional[float] = None, max_iters: int = 20, grad_tol: float = 1e-4,
+               max_step: float = 1.0, steps_per_launch: Optional[int] = None, pose0: int = 0, trace: bool = False) -> Dict[str, torch.Tensor]:
+        """Monte-Carlo search of every pose (module docstring; tests/vina_search_ref.py).  x_pred [P,A,3] (device) -> dict of device
+        tensors: x_search [P,A,3] (fp32; the ligand rows of the pose's best chain), energy [P] (float64), best_chain [P] (int32),
+        x_chains [P,K,A,3] (every chain's best as a full pose), energy_chains, energy_start [P,K] (float64; the latter is `refine`'s
+        energy), best_step, accepted, evaluations [P,K] (int32), moved [P] (float64: ligand RMSD from x_pred to x_search, A), score_start /
+        score [P]: `VinaScore.score` before and after, as `refine` reports them; with `trace=True` trace_energy [P,K,steps+1] (float64: E
+        after the start, then E_new of every step) and trace_entity, trace_accept, trace_iterations, trace_status [P,K,steps] (int32).
+        The pose id of x_pred[p] is pose0 + p: the same pose under the same id and seed gives the same chains wherever it stands.
+        `temperature` (kcal/mol) may be inf; `rotate_amp=None`: `default_rotate_amp` (that default reads one number back; apart from
+        it nothing is read back).  `steps_per_launch` cuts the steps into launches and changes no bit."""
+        chains, steps, pose0 = int(chains), int(steps), int(pose0)
+        if int(max_iters) < 0 or not float(grad_tol) >= 0 or not float(max_step) > 0:
+            raise ValueError(f"VinaRefine.search: max_iters={max_iters}, grad_tol={grad_tol}, max_step={max_step}")
+        if not 1 <= chains <= MAX_CHAINS or steps < 0 or pose0 < 0 or not float(temperature) > 0 or not float(translate_amp) >= 0:
+            raise ValueError(f"VinaRefine.search: chains={chains} (1 .. {MAX_CHAINS}), steps={steps}, pose0={pose0}, temperature={temperature}, "
+                             f"translate_amp={translate_amp}")
+        if rotate_amp is not None and not float(rotate_amp) >= 0:
+            raise ValueError(f"VinaRefine.search: rotate_amp={rotate_amp}")
+        if steps_per_launch is not None and int(steps_per_launch) < 1:
+            raise ValueError(f"VinaRefine.search: steps_per_launch={steps_per_launch}")
+        x, head = self._poses(x_pred, "search")
+        if rotate_amp is None:
+            rotate_amp = self.default_rotate_amp(x, translate_amp)
+        L_ = ops._lib.init()
+        P, A, L, T, K = x.shape[0], x.shape[1], self.n_atoms, self.n_torsions, chains
+        dev = x.device
+        f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)
+        i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)
+        raw = {"x_chains": torch.empty(P, K, L, 3, device=dev), "energy_chains": f64(P, K), "energy_start": f64(P, K), "best_step": i32(P, K),
+               "accepted": i32(P, K), "evaluations": i32(P, K)}
+        tr = {}
+        if trace:
+            tr = {"trace_energy": f64(P, K, steps + 1), "trace_entity": i32(P, K, steps), "trace_accept": i32(P, K, steps),
+                  "trace_iterations": i32(P, K, steps), "trace_status": i32(P, K, steps)}
+        out = {"x_search": torch.empty_like(x), "energy": f64(P), "best_chain": i32(P)}
+        cap = max(MAX_SEARCH_BLOCKS // K, 1)
+        per = steps if steps_per_launch is None else int(steps_per_launch)
+        order = ("x_chains", "energy_chains", "energy_start", "best_step", "accepted", "evaluations")
+        torder = ("trace_energy", "trace_entity", "trace_accept", "trace_iterations", "trace_status")
+        for a in range(0, P, cap):
+            b = min(a + cap, P)
+            n = b - a
+            numel = L_.pd_vina_search_workspace_numel(n, K, L, T)
+            ops.check(min(numel, 0), "pd_vina_search_workspace_numel")
+            ws = f64(numel)
+            hd = (ops.ptr(x[a:b]),) + head[1:]
+            step0 = 0
+            while True:
+                ns = min(per, steps - step0)
+                ops.check(L_.pd_vina_search(*hd, int(max_iters), float(grad_tol), float(max_step), int(seed) & 0xFFFFFFFFFFFFFFFF, pose0 + a,
+                                            step0, ns, steps, float(temperature), float(translate_amp), float(rotate_amp), ops.ptr(ws), numel,
+                                            *[ops.ptr(raw[k][a:b]) for k in order], *[ops.ptr(tr[k][a:b]) if trace else None for k in torder],
+                                            n, K, A, L, T, ops.stream()), "pd_vina_search")
+                step0 += ns
+                if step0 >= steps:
+                    break
+            ops.check(L_.pd_vina_search_select(hd[0], head[1], ops.ptr(raw["x_chains"][a:b]), ops.ptr(raw["energy_chains"][a:b]),
+                                               ops.ptr(out["best_chain"][a:b]), ops.ptr(out["energy"][a:b]), ops.ptr(out["x_search"][a:b]),
+                                               n, K, A, L, ops.stream()), "pd_vina_search_select")
+        lig = self.tables(dev)["ligand_idx"].long()
+        full = x[:, None].expand(P, K, A, 3).contiguous()
+        full[:, :, lig] = raw["x_chains"]
+        out["x_chains"] = full
+        out.update({k: raw[k] for k in order[1:]})
+        out["moved"] = ((out["x_search"][:, lig].double() - x[:, lig].double()) ** 2).sum(-1).mean(-1).sqrt()
+        out["score_start"] = self.vina.score(x)["score"]
+        out["score"] = self.vina.score(out["x_search"])["score"]
+        out.update(tr)
         return out
 
     def __repr__(self):
