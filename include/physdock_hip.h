@@ -534,6 +534,39 @@ int pd_pose_validity(const float* x, const int* lig_idx, const float* radius, co
                      const float* d13_ref, const unsigned char* far, const int* planar, pd_validity_thresholds thr,
                      unsigned long long* ws, float* val, int* worst, int* flags, int P, int A, int L, int n12, int n13, int G,
                      void* stream);
+/* Stereochemistry checks of the RECEPTOR of P poses (receptor_geometry.hip, whose header comment holds the full definition; ABI 11,
+ * additive; the thresholds are PoseBusters' ligand defaults and this package's own, unvalidated for proteins).  Tables, built once
+ * per system (physdock_amd/receptor_geometry.py): radius [A] van der Waals radii, NEGATIVE for an atom that takes no part;
+ * excl_start [A + 1] / excl_atom: per atom the partners with a HIGHER index that the clash check leaves out (up to three bonds apart,
+ * or already clashing in the reference structure); term_atoms [T][PD_RECEPTOR_TERM_WIDTH] (-1 padded) and term_ref [T], the terms
+ * in the order bonds (a, b; reference length), 1-3 pairs (the same), chiral centres (centre, a, b, c; sign +-1), peptide terms (CA, C,
+ * N', CA'; 1 = trans in the reference), planar groups (4 .. 10 atoms); res_term_start [R + 1] / res_term: the terms that hold an atom
+ * of each residue; res_atom_start [R + 1] / res_atom: its active atoms.  Per pose p:
+ *   val[p][0..3]  min, max of d / reference over the bonds, over the 1-3 pairs (fp32; 1 without terms)
+ *   val[p][4]     min over active, non-excluded pairs i < j of d / (r_i + r_j) (+inf without pairs);  worst[p] the pair, the smallest
+ *                 (i, j) on an exact tie, (-1, -1) without pairs
+ *   val[p][5]     max distance (Angstrom, double) of a group's atom to its least-squares plane;  val[p][6] max over the peptide terms
+ *                 of min(|omega|, 180 - |omega|) in degrees (double);  val[p][7] the number of centres whose signed volume has the
+ *                 wrong sign or is 0
+ *   counts[p][7]  failing terms of bit 0 bond_lengths, 1 bond_angles, 2 chirality, 3 peptide_twist, 4 cis_flip, 5 planarity and
+ *                 failing pairs of bit 6 clash;  flags[p] bit b = counts[p][b] > 0;  residue_flags [P][R], atom_clash [P][A],
+ *                 term_val [P][T] fp32, term_fail [P][T] the same bits per residue, atom (0 / 1) and term
+ * A non-finite coordinate fails every term and pair it enters.  ws: pd_receptor_geometry_workspace_numel(P, A) 64-bit words, written
+ * before they are read.  No atomics: bit-identical from launch to launch and whatever P.  pd_receptor_dihedrals: angles [P][R][7]
+ * fp32 degrees of the [R][7][4] index table (phi, psi, omega, chi1 - chi4; -1 = undefined -> NaN), computed in double.
+ * A <= 4096, R <= 4096, T <= 2^20, P <= 65535 (else PD_ERR_UNSUPPORTED).                                                        */
+#define PD_RECEPTOR_TERM_WIDTH 10
+typedef struct pd_receptor_thresholds {
+    float bond_lo, bond_hi, angle_lo, angle_hi, clash, planarity, twist, cis;
+} pd_receptor_thresholds;
+int pd_receptor_geometry_workspace_numel(int P, int A);
+int pd_receptor_geometry(const float* x, const float* radius, const int* excl_start, const int* excl_atom, const int* term_atoms,
+                         const float* term_ref, int n_bonds, int n_angles, int n_centres, int n_peptides, int n_groups,
+                         const int* res_term_start, const int* res_term, const int* res_atom_start, const int* res_atom,
+                         pd_receptor_thresholds thr, unsigned long long* ws, float* val, int* worst, int* counts, int* flags,
+                         unsigned char* residue_flags, unsigned char* atom_clash, float* term_val, unsigned char* term_fail, int P,
+                         int A, int R, void* stream);
+int pd_receptor_dihedrals(const float* x, const int* dih, float* angles, int P, int A, int R, void* stream);
 /* lDDT-PLI of P poses of one ligand in its receptor against one ground truth, maximised over the ligand's automorphisms
  * (lddt_pli.hip; ABI 11, additive).  Tables, built once per system on the host (physdock_amd/lddt_pli.py): lig_idx [L] the
  * ligand's atoms in a pose; the contacts of the ground truth in CSR form - contact_start [L+1], contact_atom [n_contacts] (pose

@@ -25,6 +25,7 @@ from .scoring import VinaScore  # noqa: F401  (Vina-style interaction score and 
 from .interactions import InteractionFingerprint  # noqa: F401  (per-residue interaction fingerprint of every pose; csrc/plif.hip)
 from .ring_interactions import RingInteractions  # noqa: F401  (pi-stacking, pi-cation and halogen bonds of every pose; csrc/plif_rings.hip)
 from .hydrogens import Hydrogens  # noqa: F401  (riding hydrogens of every pose and angle-tested hydrogen bonds; csrc/hydrogens.hip)
+from .receptor_geometry import ReceptorGeometry  # noqa: F401  (stereochemistry checks of every pose's receptor; csrc/receptor_geometry.hip)
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)

@@ -114,6 +114,11 @@ class ValidityThresholds(C.Structure):
                                          "planarity", "detached")]
 
 
+class ReceptorThresholds(C.Structure):
+    """mirror of pd_receptor_thresholds (passed by value)"""
+    _fields_ = [(k, C.c_float) for k in ("bond_lo", "bond_hi", "angle_lo", "angle_hi", "clash", "planarity", "twist", "cis")]
+
+
 class HipLibraryMissing(RuntimeError):
     pass
 
@@ -271,6 +276,9 @@ def _declare(L):
     sig("pd_dg_error_grad", p, p, p, p, p, p, d, d, p, p, i, i, i, p)
     sig("pd_embed_conformers", p, p, p, p, p, ull, i, d, d, p, ll, p, p, p, p, p, p, p, i, i, i, p)
     sig("pd_sdf_format", p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, ll, p)       # ABI 11, additive (sdf.hip)
+    sig("pd_receptor_geometry_workspace_numel", i, i)                                        # ABI 11, additive (receptor_geometry.hip)
+    sig("pd_receptor_geometry", p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, ReceptorThresholds, p, p, p, p, p, p, p, p, p, i, i, i, p)
+    sig("pd_receptor_dihedrals", p, p, p, i, i, i, p)
 
 
 def ptr(t):

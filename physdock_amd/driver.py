@@ -193,6 +193,28 @@ def score_hydrogens(hydrogens, aligned, batch) -> dict:
     return res
 
 
+def check_receptor_geometry(receptor_geometry, batch) -> None:
+    """redock(receptor_geometry=): raise ValueError unless it is a `receptor_geometry.ReceptorGeometry` over the batch's atoms"""
+    if receptor_geometry is None:
+        return
+    if not callable(getattr(receptor_geometry, "chi_recovery", None)) or not hasattr(receptor_geometry, "n_pose_atoms"):
+        raise ValueError("receptor_geometry= takes a receptor_geometry.ReceptorGeometry of the system")
+    n = int(batch["x_gt"].shape[0])
+    if receptor_geometry.n_pose_atoms != n:
+        raise ValueError(f"receptor_geometry= was built over {receptor_geometry.n_pose_atoms} pose atoms, the batch holds {n}")
+
+
+def score_receptor_geometry(receptor_geometry, aligned, batch, out) -> dict:
+    """redock(receptor_geometry=): {"receptor_geometry": val, flags, valid, counts and residue_flags of ReceptorGeometry.check of the
+    kept poses, chi_recovery = its `chi_recovery` against `x_gt` and, with `validity=`, valid_both}"""
+    found = receptor_geometry.check(aligned)
+    res = {k: found[k] for k in ("val", "flags", "valid", "counts", "residue_flags")}
+    res["chi_recovery"] = receptor_geometry.chi_recovery(aligned, x_ref=batch["x_gt"].float())
+    if "validity" in out:
+        res["valid_both"] = found["valid"] & out["validity"]["valid"]
+    return {"receptor_geometry": res}
+
+
 def conformer_pool(conformers, batch, seed, num_confs=128):
     """redock(conformers=): (ref_mol_poses [n,L,3], log) - the accepted conformers of `conformers.embed(num_confs, seed)` on the batch's
     device and their counts.  ValueError unless `conformers` is a `conformers.ConformerEnsemble` over the batch's ligand atoms, and
@@ -227,7 +249,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None, sdf=None, search=None) -> dict:
+           conformers=None, sdf=None, search=None, receptor_geometry=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -295,12 +317,18 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `interactions.pairwise(bits)` and needs `interactions=`.  The poses are walked in the order `by` names: `"confidence"` needs
     `confidence=`, `"vina"` needs `vina=`, `"vina_refined"` needs `refine=` and `vina=`; a missing prerequisite raises ValueError before
     anything is sampled.  With `vina=` the modes carry `mean_score`, with `validity=` only valid poses lead and join, and when `ranking`
-    ran `clusters["leader_rmsd"]` is the RMSD to `x_gt` of each mode's leader (NaN behind `n_clusters`).  Nothing else changes."""
+    ran `clusters["leader_rmsd"]` is the RMSD to `x_gt` of each mode's leader (NaN behind `n_clusters`).  Nothing else changes.
+    `receptor_geometry` (a `receptor_geometry.ReceptorGeometry` of the system): the result gains `receptor_geometry` = `val`, `flags`,
+    `valid`, `counts` and `residue_flags` of its `check` of the returned `poses` (bond lengths and angles, chirality, peptide twist and
+    cis flips, planarity and clashes of each pose's RECEPTOR), `chi_recovery` (its `chi_recovery` of them against `x_gt`) and, with
+    `validity=`, `valid_both` (ligand and receptor both pass).  One built over another number of atoms raises ValueError before
+    anything is sampled.  No pose is rejected for it; nothing else changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
     from .sdfio import check_redock_sdf, score_sdf
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
     check_search(search, refine)
     check_hydrogens(hydrogens, batch)
+    check_receptor_geometry(receptor_geometry, batch)
     check_redock_sdf(sdf, batch, hydrogens)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
@@ -416,6 +444,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_ring_interactions(ring_interactions, aligned, batch))
     if hydrogens is not None:
         out.update(score_hydrogens(hydrogens, aligned, batch))
+    if receptor_geometry is not None:
+        out.update(score_receptor_geometry(receptor_geometry, aligned, batch, out))
     if pool_log is not None:
         out["conformers"] = pool_log
     if surface is not None:
@@ -465,7 +495,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -557,13 +587,14 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None):
+                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
+        check_receptor_geometry(receptor_geometry, batch)
         from .sdfio import check_redock_sdf
         check_redock_sdf(sdf, batch, hydrogens)
         self.sdf = sdf
@@ -597,6 +628,7 @@ class _RedockState:
         self.interactions = interactions
         self.ring_interactions = ring_interactions
         self.hydrogens = hydrogens
+        self.receptor_geometry = receptor_geometry
         self.surface = surface
         self.refine = refine
         self.search = search
@@ -685,6 +717,8 @@ class _RedockState:
             out.update(score_ring_interactions(self.ring_interactions, aligned, self.batch))
         if self.hydrogens is not None:
             out.update(score_hydrogens(self.hydrogens, aligned, self.batch))
+        if self.receptor_geometry is not None:
+            out.update(score_receptor_geometry(self.receptor_geometry, aligned, self.batch, out))
         if self.pool_log is not None:
             out["conformers"] = self.pool_log
         if self.surface is not None:
