@@ -442,6 +442,30 @@ int pd_pairwise_rmsd(const float* x, const int* idx, const float* ref, float* D,
  * L <= 1024, M <= 65535, n <= 65535 (else PD_ERR_UNSUPPORTED).                                                              */
 int pd_sym_rmsd(const float* x, const int* idx, const float* ref, const unsigned short* perms_t, float* D, float* rmsd_ref,
                 int* best_perm_ref, int n, int A, int L, int M, void* stream);
+/* best-fit (superposed) form of pd_sym_rmsd (bestfit_rmsd.hip, whose header comment holds the kernel's structure; ABI 11, additive): the
+ * ligand-only RMSD minimised over rigid superpositions AND over the table rows - the conformer accuracy of a pose, wherever the ligand
+ * sits (RDKit's GetBestRMS).  Rectangular: rows xa [na][Aa][3] gathered through idx_a [L], columns xb [nb][Ab][3] through idx_b [L]
+ * (fp32; a NULL idx means atoms 0 .. L-1 and needs A >= L; the caller guarantees 0 <= idx < A - an entry outside is not followed and
+ * makes its structure count as not finite).  perms_t [L][M] as for pd_sym_rmsd; NULL with M = 1: the identity alone.  With a, b the two
+ * ligands centred on their unweighted centroids in float64, G their sums of squared norms and N Horn's 4x4 matrix (1987):
+ *   msd(a, b, m) = min over PROPER rotations R of (1/L) sum_k |R a[k] - b[perms[m][k]]|^2 = (G_a + G_b - 2 lambda_max(N(a, b o perms[m]))) / L
+ *   D[i,j]         (float) sqrt(max(0, min_m msd)): the float64 result rounded once; 0 for L = 1
+ *   best_perm[i,j] (nullable, int32 [na][nb]) the smallest m that attains the float64 minimum
+ *   quat[i,j]      (nullable, float64 [na][nb][4]) the unit eigenvector (w, x, y, z) of lambda_max for that m, first non-zero component
+ *                  positive: R(quat) a ~ b o perms[m]; any optimal rotation where lambda_max is degenerate (collinear atoms, L <= 2)
+ * A mirror image is not a match.  A non-finite coordinate in either structure gives NaN, -1 and NaN.  symmetric != 0 covers xb == xa (xb
+ * NULL or xa, nb == na; idx_b / Ab unused): only i < j is computed (row i fixed, row j permuted) and mirrored, the diagonal is an exact 0;
+ * best_perm and quat must then be NULL (PD_ERR_ARG).  ws: pd_bestfit_rmsd_workspace_numel(na, nb, L) = (na + nb) (3 L + 2) doubles (per
+ * structure the centred coordinates, G and a finite flag; written by the first of the two launches, read by the second).  lambda_max by
+ * cyclic Jacobi in float64, every sum in a fixed order, an exact minimum over m, no atomics: a value depends on its two structures and
+ * the table alone - not on na, nb, the launch shape or the rest of the batch - and is bit-identical from call to call.  No allocation,
+ * no synchronisation.  A NULL required pointer, a misaligned pointer (8 bytes for ws / quat, 4 for float / int, 2 for perms_t), a size
+ * < 1 or a short workspace: PD_ERR_ARG; L > 1024, M > 65535, na or nb > 65535: PD_ERR_UNSUPPORTED.  A rejected call launches nothing.
+ * tests/bestfit_rmsd_ref.py is the written definition.                                                                                */
+int pd_bestfit_rmsd_workspace_numel(int na, int nb, int L);
+int pd_bestfit_rmsd(const float* xa, const int* idx_a, const float* xb, const int* idx_b, const unsigned short* perms_t, double* ws,
+                    long long ws_numel, float* D, int* best_perm, double* quat, int na, int nb, int Aa, int Ab, int L, int M,
+                    int symmetric, void* stream);
 /* Binding modes of n poses: greedy leader clustering on a distance matrix, best pose first, as Vina, AutoDock, GNINA and rDock report
  * them (cluster.hip; ABI 11, additive; the consumer of pd_pairwise_rmsd / pd_sym_rmsd and of 1 - pd_plif_pairwise - the reference runs
  * K-means(5) of scikit-learn on the host, redocking.py:389-416).  D [n][n] symmetric with a zero diagonal; order [n] the pose ids best

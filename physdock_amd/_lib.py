@@ -246,6 +246,8 @@ def _declare(L):
     sig("pd_metrics_pae_tm", p, p, p, p, p, p, p, p, p, p, i, i, i, p)
     sig("pd_metrics_clash", p, p, p, p, p, p, p, i, p, p, i, i, i, i, p)
     sig("pd_sym_rmsd", p, p, p, p, p, p, p, i, i, i, i, p)                               # ABI 11, additive (sym_rmsd.hip)
+    sig("pd_bestfit_rmsd_workspace_numel", i, i, i)                                      # ABI 11, additive (bestfit_rmsd.hip)
+    sig("pd_bestfit_rmsd", p, p, p, p, p, p, ll, p, p, p, i, i, i, i, i, i, i, p)
     sig("pd_pose_validity_workspace_numel", i, i)                                    # ABI 11, additive (validity.hip)
     sig("pd_pose_validity", p, p, p, p, p, p, p, p, p, p, p, ValidityThresholds, p, p, p, p, i, i, i, i, i, i, p)
     sig("pd_lddt_pli_counts", p, p, p, p, p, p, p, f, f, f, f, p, i, i, i, i, i, p)         # ABI 11, additive (lddt_pli.hip)

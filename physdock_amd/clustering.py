@@ -7,7 +7,8 @@ head's, the Vina score's, the refined score's - "the best pose of each mode" is 
 
 The distance is the (symmetry-corrected) pairwise ligand RMSD of `ranking.pairwise_ligand_rmsd`, or 1 - the Tanimoto similarity of
 `InteractionFingerprint.pairwise` (`metric="interactions"`: poses that touch the same residues in the same ways share a mode, and
-`cutoff` is then a Tanimoto distance in 0 .. 1).
+`cutoff` is then a Tanimoto distance in 0 .. 1), or the best-fit ligand RMSD of `bestfit.BestFitRmsd.pairwise` (`metric="conformer"`:
+poses with the same internal conformation share a mode, wherever they sit).
 
 `cluster` returns device tensors and never reads back: `labels` int32 [n] (-1 for an invalid pose), `dist_to_leader` fp32 [n], and per
 mode, in arrays of length n of which the first `n_clusters` entries count (behind them ids are -1, sizes 0, floats NaN): `leader`,
@@ -31,12 +32,12 @@ from . import ops
 
 MAX_POSES = 8192                      # PD_POSE_CLUSTERS_MAX_POSES
 ORDERS = (None, "confidence", "vina", "vina_refined")
-METRICS = ("rmsd", "interactions")
+METRICS = ("rmsd", "interactions", "conformer")
 _PER_MODE = ("leader", "size", "radius", "medoid", "spread", "mean_score")
 
 
 class PoseClusters:
-    """An immutable spec: `cutoff` (A for `metric="rmsd"`, a Tanimoto distance for `"interactions"`), `by` - the order `redock` walks
+    """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"`), `by` - the order `redock` walks
     the poses in (None: pose ids; "confidence", "vina", "vina_refined": the result's `order_confidence`, `order_vina`,
     `order_vina_refined`) - and `metric`.  `cluster` and `binding_modes` take their order from the caller."""
 
@@ -128,7 +129,8 @@ class PoseClusters:
             raise ValueError(f"PoseClusters.binding_modes: x_pred must be [P,A,3], got {tuple(getattr(x_pred, 'shape', ()))}")
         if self.metric != "rmsd":
             raise ValueError("PoseClusters.binding_modes clusters on the ligand RMSD; for metric='interactions' give "
-                             "cluster() the matrix 1 - InteractionFingerprint.pairwise(bits)")
+                             "cluster() the matrix 1 - InteractionFingerprint.pairwise(bits), for metric='conformer' "
+                             "BestFitRmsd.pairwise(x)")
         P = x_pred.shape[0]
         if not 1 <= P <= MAX_POSES:
             raise ValueError(f"PoseClusters.binding_modes: {P} poses; the kernel takes 1 .. {MAX_POSES}")
@@ -172,7 +174,7 @@ class PoseClusters:
                      spread=float(cols["spread"][k]), mean_score=float(cols["mean_score"][k])) for k in range(K)]
 
 
-def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None) -> None:
+def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None, conformer_rmsd=None) -> None:
     """redock(clusters=): raise ValueError for what the spec needs and the call lacks - before any sampling"""
     if clusters is None:
         return
@@ -180,6 +182,8 @@ def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=N
         raise ValueError(f"clusters= takes a PoseClusters, got {type(clusters).__name__}")
     if clusters.metric == "interactions" and interactions is None:
         raise ValueError("clusters=PoseClusters(metric='interactions') needs interactions=")
+    if clusters.metric == "conformer" and conformer_rmsd is None:
+        raise ValueError("clusters=PoseClusters(metric='conformer') needs conformer_rmsd=")
     if clusters.by == "confidence" and confidence is None:
         raise ValueError("clusters=PoseClusters(by='confidence') needs confidence=")
     if clusters.by == "vina" and vina is None:
@@ -197,6 +201,8 @@ def cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=None, li
         else:
             from .ranking import pairwise_ligand_rmsd
             D = pairwise_ligand_rmsd(aligned, ligand_idx, symmetry=ligand_symmetry)[0]
+    elif clusters.metric == "conformer":
+        D = out["conformer_rmsd"]["pairwise"]          # the modes by internal conformation instead of by placement
     else:
         D = 1.0 - interactions.pairwise(out["interactions"]["bits"])
     scores = out["vina"]["score"] if "vina" in out else None       # mean_score of a mode, whatever order is walked

@@ -23,7 +23,9 @@ stereocentre's four neighbours: a start can end with the fourth on the wrong sid
 rejected, not repaired (about a quarter of the starts on the test ligands).  Out of scope: ETKDG's torsion preferences,
 an MMFF clean-up, macrocycle handling, hydrogens, parity with RDKit.  Limits: L <= 128, at most 64 centres, C <= 4096.
 
-`ConformerEnsemble` holds one ligand's tables, built once on the host; `embed` and `error` return device tensors.
+`ConformerEnsemble` holds one ligand's tables, built once on the host; `embed` and `error` return device tensors.  `embed(...,
+prune_rms=)` drops near-duplicates by their best-fit RMSD and `coverage(poses, x_ref)` measures whether the pool contains a reference
+conformer (`bestfit.BestFitRmsd`).
 `driver.redock(..., physics_correction=True, conformers=)` takes the pool from `embed` when no `ref_mol_poses` is given.
 """
 from __future__ import annotations
@@ -245,15 +247,30 @@ class ConformerEnsemble:
         return out
 
     def embed(self, C: int, seed: int, max_iters: int = 400, grad_tol: float = 1e-4, keep: Optional[str] = "ok", device=None,
-              start: Optional[torch.Tensor] = None, box: Optional[float] = None) -> Dict[str, torch.Tensor]:
+              start: Optional[torch.Tensor] = None, box: Optional[float] = None, prune_rms: Optional[float] = None,
+              symmetry=None) -> Dict[str, torch.Tensor]:
         """C conformers -> dict of device tensors: x [C,L,3] (fp32, centred; a rejected row is zeros), ok [C] (uint8), err [C] (float64,
         E at the end of stage 2), max_violation [C] (float64, A, in 3-D), iterations and status [C,2] (int32 per stage; `STATUS`), x4 and
         grad4 [C,L,4] (float64: the point stage 2 ended at, before the projection, whether accepted or not, and dE/dx there).
         Conformer c depends on (seed, c) only, not on C.  `start` [C,L,4] replaces the random start, `box` the half-width of its cube.
         Nothing is read back unless `keep="ok"`, which adds `poses`, the accepted rows compacted in order (one read of their number);
-        `keep=None` leaves it out."""
+        `keep=None` leaves it out.
+        `prune_rms` (A; what ETKDG users know as pruneRmsThresh): near-duplicates leave the pool.  The best-fit RMSD of every pair
+        (`bestfit.BestFitRmsd(symmetry=symmetry).pairwise(x)`) goes through the greedy leader walk of
+        `PoseClusters(cutoff=prune_rms).cluster(D, valid=ok)` in conformer order: `kept` [C] (uint8: accepted and a leader) and
+        `duplicate_of` [C] (int32: the leader a dropped duplicate lies within prune_rms of, -1 for leaders and rejected rows) are added
+        and `poses` holds the kept rows only.  Without the keyword nothing changes."""
         if keep not in ("ok", None):
             raise ValueError(f"ConformerEnsemble.embed: keep={keep!r}; \"ok\" or None")
+        if prune_rms is not None:
+            prune_rms = float(prune_rms)
+            if not 0.0 <= prune_rms < float("inf"):
+                raise ValueError(f"ConformerEnsemble.embed: prune_rms={prune_rms}; expected a finite value >= 0")
+            if symmetry is not None and getattr(symmetry, "n_atoms", None) != self.n_atoms:
+                raise ValueError(f"ConformerEnsemble.embed: symmetry= is over {getattr(symmetry, 'n_atoms', None)} atoms, the ligand "
+                                 f"has {self.n_atoms}")
+        elif symmetry is not None:
+            raise ValueError("ConformerEnsemble.embed: symmetry= is the table of prune_rms=; give both")
         C = int(C)
         if not 1 <= C <= MAX_CONFORMERS:
             raise ValueError(f"ConformerEnsemble.embed: {C} conformers; the kernel takes 1 .. {MAX_CONFORMERS}")
@@ -284,9 +301,34 @@ class ConformerEnsemble:
         tail = ws.view(C, -1)[:, 16 * L * L:]             # the workspace's tail: the final 4-D point and its gradient
         out["x4"] = tail[:, :4 * L].reshape(C, L, 4).clone()
         out["grad4"] = tail[:, 4 * L:8 * L].reshape(C, L, 4).clone()
+        if prune_rms is not None:
+            from .bestfit import BestFitRmsd
+            from .clustering import PoseClusters
+            got = PoseClusters(cutoff=prune_rms).cluster(BestFitRmsd(symmetry=symmetry).pairwise(out["x"]), valid=out["ok"])
+            ids = torch.arange(C, dtype=torch.int32, device=device)
+            mine = got["leader"][got["labels"].clamp(min=0).long()]          # each labelled conformer's leader
+            lead = (got["labels"] >= 0) & (mine == ids)
+            out["kept"] = lead.to(torch.uint8)
+            out["duplicate_of"] = torch.where((got["labels"] >= 0) & ~lead, mine, torch.full_like(mine, -1))
         if keep == "ok":
-            out["poses"] = out["x"][out["ok"].bool()]
+            out["poses"] = out["x"][(out["kept"] if prune_rms is not None else out["ok"]).bool()]
         return out
+
+    def coverage(self, poses: torch.Tensor, x_ref: torch.Tensor, symmetry=None) -> Dict[str, torch.Tensor]:
+        """Does the pool contain the reference conformer?  poses [C,L,3] (device; `embed(...)["poses"]`), x_ref [L,3] -> `rmsd` fp32 [C]
+        (the best-fit RMSD of every conformer to x_ref, `bestfit.BestFitRmsd.to_reference`), `best` fp32 [1] (the coverage: their
+        minimum, NaN without a finite one) and `best_index` int64 [1] (-1 then).  Nothing is read back."""
+        from .bestfit import BestFitRmsd
+        if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or tuple(poses.shape[1:]) != (self.n_atoms, 3) or poses.shape[0] < 1:
+            raise ValueError(f"ConformerEnsemble.coverage: poses must be [C >= 1, {self.n_atoms}, 3], got "
+                             f"{tuple(getattr(poses, 'shape', ()))}")
+        if not isinstance(x_ref, torch.Tensor) or tuple(x_ref.shape) != (self.n_atoms, 3):
+            raise ValueError(f"ConformerEnsemble.coverage: x_ref must be [{self.n_atoms}, 3], got {tuple(getattr(x_ref, 'shape', ()))}")
+        r = BestFitRmsd(symmetry=symmetry).cross(poses, x_ref[None])["D"][:, 0]
+        key = torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r)
+        first = (key == key.min()).to(torch.int8).argmax(0, keepdim=True)                   # the first of equal minima
+        best = r[first]
+        return {"rmsd": r, "best": best, "best_index": torch.where(torch.isnan(best), torch.full_like(first, -1), first)}
 
     def __repr__(self):
         return f"ConformerEnsemble(n_atoms={self.n_atoms}, n_centres={self.n_centres}, box={self.box:.2f})"

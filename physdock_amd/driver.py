@@ -215,6 +215,41 @@ def score_receptor_geometry(receptor_geometry, aligned, batch, out) -> dict:
     return {"receptor_geometry": res}
 
 
+def check_conformer_rmsd(conformer_rmsd, batch) -> None:
+    """redock(conformer_rmsd=): raise ValueError unless it is a `bestfit.BestFitRmsd` over the batch's ligand atoms"""
+    if conformer_rmsd is None:
+        return
+    if not callable(getattr(conformer_rmsd, "to_reference", None)) or not hasattr(conformer_rmsd, "ligand_idx"):
+        raise ValueError("conformer_rmsd= takes a bestfit.BestFitRmsd of the ligand")
+    n = int(ligand_atom_mask(batch).sum())
+    if conformer_rmsd.n_atoms is not None and conformer_rmsd.n_atoms != n:
+        raise ValueError(f"conformer_rmsd= was built over {conformer_rmsd.n_atoms} ligand atoms, the batch's ligand holds {n}")
+
+
+def score_conformer_rmsd(conformer_rmsd, aligned, batch, ligand_idx, pool=None) -> dict:
+    """redock(conformer_rmsd=): {"conformer_rmsd": pairwise [n,n] (BestFitRmsd.pairwise of the kept poses), to_gt [n] (their best-fit
+    RMSD to `x_gt`: the conformer accuracy, wherever the ligand sits) and, with a template pool [C,L,3], nearest_template /
+    nearest_template_rmsd [n] (`cross` of the poses with the pool) and pool_to_gt (a scalar tensor: the pool's coverage of `x_gt`)}.
+    A spec without `ligand_idx` is given the ligand atoms of the poses."""
+    lig = ligand_idx.long()
+    whole = conformer_rmsd.ligand_idx is not None
+    x = aligned if whole else aligned[:, lig]
+    res = {"pairwise": conformer_rmsd.pairwise(x)}
+    gt = batch["x_gt"].float() if "x_gt" in batch else None
+    if gt is not None:
+        res["to_gt"] = conformer_rmsd.to_reference(x, gt if whole else gt[lig])["rmsd"]
+    if pool is not None:
+        pool = pool.to(aligned.device).float()
+        near = conformer_rmsd.cross(x, pool)
+        res["nearest_template"], res["nearest_template_rmsd"] = near["nearest"], near["nearest_rmsd"]
+        if gt is not None:
+            from .bestfit import BestFitRmsd
+            r = BestFitRmsd(symmetry=conformer_rmsd.symmetry).cross(pool, gt[lig][None])["D"][:, 0]
+            best = torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r).min()
+            res["pool_to_gt"] = torch.where(torch.isinf(best), torch.full_like(best, float("nan")), best)
+    return {"conformer_rmsd": res}
+
+
 def conformer_pool(conformers, batch, seed, num_confs=128):
     """redock(conformers=): (ref_mol_poses [n,L,3], log) - the accepted conformers of `conformers.embed(num_confs, seed)` on the batch's
     device and their counts.  ValueError unless `conformers` is a `conformers.ConformerEnsemble` over the batch's ligand atoms, and
@@ -249,7 +284,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None, sdf=None, search=None, receptor_geometry=None) -> dict:
+           conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -322,13 +357,22 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `valid`, `counts` and `residue_flags` of its `check` of the returned `poses` (bond lengths and angles, chirality, peptide twist and
     cis flips, planarity and clashes of each pose's RECEPTOR), `chi_recovery` (its `chi_recovery` of them against `x_gt`) and, with
     `validity=`, `valid_both` (ligand and receptor both pass).  One built over another number of atoms raises ValueError before
-    anything is sampled.  No pose is rejected for it; nothing else changes."""
+    anything is sampled.  No pose is rejected for it; nothing else changes.
+    `conformer_rmsd` (a `bestfit.BestFitRmsd` of the ligand): the result gains `conformer_rmsd` = `pairwise` (the best-fit ligand RMSD of
+    every two returned `poses`: superposed on each other and corrected for the spec's symmetry table - their difference in CONFORMATION,
+    wherever they sit), `to_gt` [n] (each pose's best-fit RMSD to `x_gt`) and, with a template pool in use (`ref_mol_poses` or
+    `conformers=`), `nearest_template` / `nearest_template_rmsd` [n] (the pool conformer each pose is closest to) and `pool_to_gt` (a
+    scalar tensor: the best-fit RMSD of the closest pool conformer to `x_gt`, the pool's coverage).  `clusters=PoseClusters(
+    metric="conformer")` clusters `pairwise` and needs it; with `sdf=` the records gain the item `conformer_rmsd` (`to_gt`).  A spec over
+    another number of ligand atoms raises ValueError before anything is sampled.  Nothing else changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
     from .sdfio import check_redock_sdf, score_sdf
-    check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+    check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
+                               conformer_rmsd=conformer_rmsd)
     check_search(search, refine)
     check_hydrogens(hydrogens, batch)
     check_receptor_geometry(receptor_geometry, batch)
+    check_conformer_rmsd(conformer_rmsd, batch)
     check_redock_sdf(sdf, batch, hydrogens)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
@@ -454,6 +498,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_refined(refine, aligned, validity, vina))
     if search:
         out.update(score_searched(search, refine, aligned, validity, vina))
+    if conformer_rmsd is not None:
+        out.update(score_conformer_rmsd(conformer_rmsd, aligned, batch, ligand_idx, ref_mol_poses))
     if clusters is not None:
         out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
     if sdf is not None:
@@ -495,7 +541,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -587,14 +633,18 @@ class _RedockState:
                  align_weights=None, ranking=True, seed=None, sampler_kwargs=None, infer_meta_data=None, reuse_conditioning=True,
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
-                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None):
+                 ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
+                 conformer_rmsd=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
-        check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions)
+        check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
+                                   conformer_rmsd=conformer_rmsd)
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
         check_receptor_geometry(receptor_geometry, batch)
+        check_conformer_rmsd(conformer_rmsd, batch)
+        self.conformer_rmsd = conformer_rmsd
         from .sdfio import check_redock_sdf
         check_redock_sdf(sdf, batch, hydrogens)
         self.sdf = sdf
@@ -727,6 +777,8 @@ class _RedockState:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
         if self.search:
             out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
+        if self.conformer_rmsd is not None:
+            out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, self.batch, self.ligand_idx, self.ref_mol_poses))
         if self.clusters is not None:
             from .clustering import cluster_kept_poses
             out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,

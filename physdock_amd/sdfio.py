@@ -447,7 +447,8 @@ def redock_items(out) -> Dict[str, object]:
     """the data items of redock(sdf=) from what the same call computed, in this order: `pose` (the index into `poses`), with
     `confidence=` `ranking_confidence`, with `vina=` `vina_score` (`vina["score"]`), with `validity=` `valid` (`validity["valid"]`),
     with the ground truth and `ranking` `ligand_rmsd` (`ranking["rmsd_all"]`) and, with `lddt_pli=`, `lddt_pli`
-    (`ranking["lddt_pli_all"]`), with `clusters=` `cluster` (`clusters["labels"]`)"""
+    (`ranking["lddt_pli_all"]`), with `clusters=` `cluster` (`clusters["labels"]`), with `conformer_rmsd=` and the ground truth
+    `conformer_rmsd` (`conformer_rmsd["to_gt"]`)"""
     n = int(out["poses"].shape[0])
     items: Dict[str, object] = {"pose": torch.arange(n, dtype=torch.int32, device=out["poses"].device)}
     if "confidence" in out:
@@ -462,6 +463,8 @@ def redock_items(out) -> Dict[str, object]:
             items["lddt_pli"] = out["ranking"]["lddt_pli_all"]
     if "clusters" in out:
         items["cluster"] = out["clusters"]["labels"]
+    if "to_gt" in out.get("conformer_rmsd", {}):
+        items["conformer_rmsd"] = out["conformer_rmsd"]["to_gt"]
     return items
 
 
