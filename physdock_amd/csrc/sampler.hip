@@ -647,7 +647,7 @@ __global__ __launch_bounds__(256) void dit_bounds_rows_kernel(const float* __res
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const float* tb = tab + (long long)b * 6 * C;
     const float* Wb = wstack + (long long)b * (C + 2 * hidden) * C;
-    const int nw0 = n0 + wave * BR_ROWS;                              // this wave's weight rows nw0 .. nw0 + 15
+    const int nw0 = n0 + wave * BR_ROWS;                              // this wave's weight rows nw0 .. nw0 + 7
     float pv2[BR_ROWS], pvs[BR_ROWS], pa2[BR_ROWS], pas[BR_ROWS], pb2[BR_ROWS], pbs[BR_ROWS];
 #pragma unroll
     for (int i = 0; i < BR_ROWS; ++i) pv2[i] = pvs[i] = pa2[i] = pas[i] = pb2[i] = pbs[i] = 0.f;
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(256) void dit_bounds_rows_kernel(const float* __res
             const int col = (v == 0 ? 0 : v == 1 ? C : v == 2 ? 3 * C : 4 * C) + k0 + kk;
             lt[v][kk][r] = (r0 + r < nrows && k0 + kk < C) ? tb[(long long)(r0 + r) * ld + col] : 0.f;
         }
-        // ... and this wave's 3 x 16 weight rows of the chunk: coalesced 128-byte row segments; rows that do not exist read as zero
+        // ... and this wave's 3 x 8 weight rows of the chunk: coalesced 128-byte row segments; rows that do not exist read as zero
         // (a zero row adds nothing to any sum), so the inner loop carries no conditionals
         for (int i = lane; i < 3 * BR_ROWS * BR_KC; i += 64) {
             const int kk = i % BR_KC, rw = (i / BR_KC) % BR_ROWS, m = i / (BR_KC * BR_ROWS);

@@ -82,6 +82,80 @@ def test_fused_downscale_pool_vs_float64_and_two_launches(B, chunks_kind, N):
     tr.assert_within_bound("segment_pool", f"{chunks_kind} B={B}", out2.cpu(), tr.segment_pool64(ud64, ts, s), pool_bound)
 
 
+@pytest.mark.parametrize("where", ["first", "last"])
+def test_over_full_block_writes_nan_into_its_own_tokens_only(where):
+    """The loud-failure contract of csrc/pool.hip: a block whose tpb tokens hold more than 64 atoms (the token table lives in device
+    memory, so the entry point cannot refuse it) writes NaN into exactly its tokens' rows; every other block's rows are what the
+    same launch gives once the group is trimmed to 64 atoms.  The trimmed table keeps ba and every other token at the same atom
+    offsets (first group: it starts 6 atoms later; last group: it ends 6 atoms earlier), so the other blocks stage the same rows
+    and take the same operand scale.  The kernel clamps its reads to 64 rows: nothing is read or written out of bounds."""
+    from physdock_amd import ops
+    from physdock_amd.packing import split2_f16
+    gen = g(11)
+    B, N, Cin, tpb, SENT = 2, 64, 128, 4, -7777.0
+    full = [20, 18, 17, 15]                                   # 70 atoms in one group of tpb tokens
+    rest = [5, 9, 3, 7, 10, 1, 0, 12]
+    chunks = torch.tensor(full + rest if where == "first" else rest + full)
+    T = int(chunks.numel())
+    grp = slice(0, 4) if where == "first" else slice(T - 4, T)
+    others = torch.ones(T, dtype=torch.bool)
+    others[grp] = False
+    ts_over = torch.zeros(T + 1, dtype=torch.int32)
+    ts_over[1:] = torch.cumsum(chunks, 0).to(torch.int32)
+    ts_fit = ts_over.clone()
+    if where == "first":
+        ts_fit[0] += 6
+    else:
+        ts_fit[-1] -= 6
+    assert int(ts_over[grp.stop] - ts_over[grp.start]) == 70 and int(ts_fit[grp.stop] - ts_fit[grp.start]) == 64
+    assert torch.equal(ts_over[1:-1], ts_fit[1:-1]) and (ts_fit[1:] >= ts_fit[:-1]).all()
+    for t0 in range(0, T, tpb):                              # every other group fits
+        assert t0 == grp.start or int(ts_over[t0 + tpb] - ts_over[t0]) <= 64
+    A_real = int(ts_over[-1])
+    A = (A_real + 63) // 64 * 64
+    assert int(ts_over[grp.start]) + 64 <= A_real            # the clamped tile lies inside the real atoms
+    ba = (torch.randn(B, A, Cin, generator=gen) * torch.exp(0.7 * torch.randn(B, A, 1, generator=gen)) * 3).contiguous()
+    ba[:, A_real:] = float("nan")                            # never read
+    W = torch.randn(N, Cin, generator=gen) / math.sqrt(Cin)
+    bias = 0.3 * torch.randn(N, generator=gen)
+    s = torch.randn(T, N, generator=gen)
+    L = ops._lib.init()
+    bad, Wd, bd, sd = ba.cuda(), W.cuda(), bias.cuda(), s.cuda()
+    w2p, w2i = split2_f16(Wd)
+
+    def launch(ts):
+        tsd = ts.cuda()
+        out = torch.full((B * T + 1, N), SENT, device="cuda")              # one row behind the output
+        ops.check(L.pd_downscale_pool(ops.ptr(bad), w2p.data_ptr(), ops.ptr(w2i), ops.ptr(bd), ops.ptr(tsd), ops.ptr(sd), ops.ptr(out), B, A, T, Cin, N,
+                                      tpb, ops.stream()), "pool")
+        torch.cuda.synchronize()
+        assert (out[-1] == SENT).all(), "the row behind the output was written"
+        o = out[:-1].reshape(B, T, N).cpu()
+        assert not (o == SENT).any()
+        return o
+
+    over, fit = launch(ts_over), launch(ts_fit)
+    assert torch.isfinite(fit).all()
+    assert torch.isnan(over[:, grp]).all()
+    assert torch.isfinite(over[:, others]).all()
+    assert torch.equal(over[:, others], fit[:, others])
+    # the trimmed launch is an ordinary one: its rows are the float64 pooling
+    u = torch.nn.functional.silu(torch.nan_to_num(ba.double()) @ W.double().T + bias.double())
+    ref = torch.stack([u[:, int(ts_fit[t]):int(ts_fit[t + 1])].sum(1) / (float(ts_fit[t + 1] - ts_fit[t]) + 1e-3) + s[t].double() for t in range(T)], 1)
+    assert float((fit.double() - ref).abs().max()) <= 1e-4 * max(1.0, float((ref - s.double()[None]).abs().mean()))
+
+
+def test_more_than_32_tokens_per_block_is_refused():
+    from physdock_amd import ops
+    L = ops._lib.init()
+    d = torch.zeros(64 * 128, device="cuda")
+    out = torch.full((4 * 64,), -7777.0, device="cuda")
+    args = (ops.ptr(d), ops.ptr(d), ops.ptr(d), None, ops.ptr(d), None, ops.ptr(out), 1, 64, 4, 128, 64)
+    assert L.pd_downscale_pool(*args, 33, ops.stream()) == -3           # PD_ERR_UNSUPPORTED
+    torch.cuda.synchronize()
+    assert (out == -7777.0).all()
+
+
 def test_unsupported_shapes_are_refused_not_mangled():
     from physdock_amd import ops
     L = ops._lib.init()
