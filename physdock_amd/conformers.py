@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .scoring import _bond_list
+from .scoring import _bond_list, _host
 from .validity import DEFAULT_RADIUS, VDW_RADII
 
 __all__ = ["ConformerEnsemble", "bounds_from_bonds", "smooth_bounds", "MAX_ATOMS", "MAX_CENTRES", "MAX_CONFORMERS", "STATUS", "STAGES"]
@@ -49,12 +49,6 @@ STATUS = ("converged", "max_iters", "line_search")
 STAGES = ((1.0, 0.1), (0.2, 1.0))
 TOL_12, TOL_13, TOL_PLANAR, TOL_14, VDW_SCALE, UP_FAR = 0.01, 0.04, 0.05, 0.05, 0.7, 1000.0
 VOL_RANGE, VOL_MIN = (0.6, 1.4), 0.1
-
-
-def _host(a, dtype):
-    if isinstance(a, torch.Tensor):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a, dtype=dtype)
 
 
 def bounds_from_bonds(n_atoms: int, bonds, x_ref, elements, planar_groups=()):
@@ -216,15 +210,8 @@ class ConformerEnsemble:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            t = dict(lo=up(self.lo), up=up(self.up), centres=up(self.centres), vol_lo=up(self.vol_lo), vol_hi=up(self.vol_hi))
-            self._tables[device] = t
-        return t
+        names = ("lo", "up", "centres", "vol_lo", "vol_hi")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def _head(self, device):
         t = self.tables(device)

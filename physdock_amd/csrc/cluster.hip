@@ -23,11 +23,6 @@ constexpr int PC_BLOCK = 1024;
 constexpr int PC_WAVES = PC_BLOCK / 64;
 constexpr int PC_FREE = -1, PC_INVALID = -2;      // labels in LDS while the walk runs; both leave as -1
 
-__device__ __forceinline__ int pc_wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(PC_BLOCK) void pc_assign_kernel(const float* __restrict__ D, const int* __restrict__ order, float cutoff,
                                                             const unsigned char* __restrict__ valid, int* __restrict__ labels,
@@ -65,7 +60,7 @@ __global__ __launch_bounds__(PC_BLOCK) void pc_assign_kernel(const float* __rest
                     rmax = fmaxf(rmax, d);
                 }
             }
-            cnt = pc_wave_sum_int(cnt);
+            cnt = wave_sum(cnt);
             rmax = wave_max(rmax);
             if ((tid & 63) == 0) {
                 red_n[k & 1][tid >> 6] = cnt;

@@ -134,20 +134,12 @@ __device__ __forceinline__ float pd_pow2_scale(float amax) {
 
 __device__ __forceinline__ int pd_frag_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
+#include "reduce.h"      // wave_sum / wave_max / wave_min / wave_or, block_sum_det, block_sum_d / block_max_d
 
 // Exact minimum of (value, index) pairs: a key holds the bits of a NON-NEGATIVE float in its high word and an index in its low
-// word, so keys are ordered as the pairs are and the smallest index wins a tie (sym_rmsd.hip, validity.hip)
+// word, so keys are ordered as the pairs are and the smallest index wins a tie (sym_rmsd.hip, validity.hip, receptor_geometry.hip)
 typedef unsigned long long pd_u64;
+constexpr pd_u64 PD_KEY_NONE = ((pd_u64)0x7f800000u << 32) | 0xffffffffu;      // (+inf, no pair)
 __device__ __forceinline__ pd_u64 pd_key_min(pd_u64 a, pd_u64 b) { return a < b ? a : b; }
 __device__ __forceinline__ pd_u64 pd_wave_key_min(pd_u64 k) {
 #pragma unroll

@@ -23,18 +23,6 @@ __device__ __forceinline__ float dist2_rn(float dx, float dy, float dz) {     //
     return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
 }
 
-template <int NT>
-__device__ __forceinline__ double block_sum_det(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // ------------------------------------------------------------------ cal_lddt (loss.py:320-372)
 // block = (tile of LA atoms, pose b); the T centres of the pose and of x_gt are staged LC at a time, every lane reads them as
 // LDS broadcasts.  lddt[b][a] = sum_t w_t score_t / sum_t w_t, w = ((d_gt < 30) nuc + (d_gt < 15) (1 - nuc)) polymer,

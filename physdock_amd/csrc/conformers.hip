@@ -25,11 +25,14 @@
 // kept exactly symmetric) lives in the caller's workspace, whose 8 x 4 L tail receives the final 4-D point and its gradient (the first
 // 2 x 4 L doubles; ConformerEnsemble.embed returns them as x4 / grad4, the rest is not touched).
 #include "common.h"
+#include "geom3.h"
+#include "philox.h"
 #include "physdock_hip.h"
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == 256, "block_sum_d / block_max_d / threads_per_atom of reduce.h are the four-wave forms");
 constexpr int DG_MAX_L = PD_DG_MAX_ATOMS, DG_MAX_CENTRES = PD_DG_MAX_CENTRES, DG_MAX_C = PD_DG_MAX_CONFORMERS;
 constexpr double FUNCTOL = 1e-4, MOVETOL = 1e-7, EPS_ = 3e-8, MAXSTEP = 100.0;
 constexpr double ACCEPT_VIOLATION = 0.1, ACCEPT_W = 0.1;
@@ -40,55 +43,15 @@ struct Tab {
     int L, n_centres;
 };
 
-struct Philox {                                         // Philox4x32-10, the generator of sampler.hip (a copy: its bits stay put)
-    uint32_t k0, k1;
-    __device__ __forceinline__ void gen(uint32_t (&c)[4]) const {
-        uint32_t a = k0, b = k1;
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ a, n1 = (uint32_t)p1;
-            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ b, n3 = (uint32_t)p0;
-            c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-            a += 0x9E3779B9u; b += 0xBB67AE85u;
-        }
-    }
-};
-
-// deterministic block reductions (fixed tree) of doubles; the result is returned to every thread
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double block_max_d(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
-__device__ __forceinline__ int threads_per_atom(int L) {
-    int t = 16;
-    while (t > 1 && t * L > NT) t >>= 1;
-    return t;
-}
-
-struct V3 { double x, y, z; };
+using V3 = Vec3;
+// difference of the first three coordinates of two atoms of a four-stride point
 __device__ __forceinline__ V3 sub3(const double* p, int a, int c) { return {p[4 * a] - p[4 * c], p[4 * a + 1] - p[4 * c + 1], p[4 * a + 2] - p[4 * c + 2]}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
 // E of the point p (LDS, [L][4]) - returned to every thread - and, if g != nullptr, its gradient g [L][4] (LDS or global).  Must be
 // called by all NT threads; ends with a barrier after which g is complete.
 __device__ double error_grad(const Tab& T, const double* p, double* g, double w_chi, double w_4d, double* red) {
     const int L = T.L;
-    const int tpa = threads_per_atom(L), sub = threadIdx.x & (tpa - 1);
+    const int tpa = threads_per_atom(L, 16), sub = threadIdx.x & (tpa - 1);
     const int a = threadIdx.x / tpa;                     // one pass covers every atom: L <= PD_DG_MAX_ATOMS = NT / 2, so tpa >= 2 and tpa * L <= NT
     double gx = 0.0, gy = 0.0, gz = 0.0, gw = 0.0, e = 0.0;
     if (a < L) {

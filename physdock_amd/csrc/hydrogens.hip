@@ -44,6 +44,7 @@
 // and on no launch dimension: results are bit-identical from run to run, whatever P is and wherever a pose sits.  No allocation, no
 // synchronisation.
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -61,16 +62,6 @@ constexpr double ROTOR_STEP = 0.52359877559829887;     // 30 degrees
 constexpr double TINY = 1.0e-6;
 static_assert(PD_HBOND_KINDS == 2 && PD_HBOND_THRESHOLDS == 2, "the counts the header documents");
 
-struct Vec3 {
-    double x, y, z;
-};
-__device__ __forceinline__ Vec3 sub(Vec3 a, Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 add(Vec3 a, Vec3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ Vec3 neg(Vec3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ double dot(Vec3 a, Vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ Vec3 cross(Vec3 a, Vec3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ Vec3 load3(const float* p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
-__device__ __forceinline__ bool finite3(Vec3 v) { return isfinite(v.x) && isfinite(v.y) && isfinite(v.z); }
 // v / |v|; ok goes false when |v| is below TINY or not a number
 __device__ __forceinline__ Vec3 unit(Vec3 v, bool& ok) {
     const double n = sqrt(dot(v, v));
@@ -114,17 +105,6 @@ __device__ __forceinline__ bool place_row(const float* xp, int A, int par, const
     if (!ok) return false;
     h = {p.x + len * d.x, p.y + len * d.y, p.z + len * d.z};
     return true;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
 }
 
 __global__ __launch_bounds__(PLACE_BLOCK) void hydrogens_place_kernel(const float* __restrict__ x, const int* __restrict__ parent,

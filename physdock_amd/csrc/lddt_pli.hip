@@ -29,11 +29,6 @@ constexpr int LDDT_LDS_CAND = 4096;    // candidates whose totals the select ker
 static_assert(LDDT_TILE == PD_LDDT_PLI_TILE && LDDT_LDS_CAND == PD_LDDT_PLI_LDS_CAND, "the constants the header documents");
 static_assert(64 * LDDT_CPT < 256, "a wave's count must fit the 8-bit field of the packed reduction");
 
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 struct lddt_thresholds { float t[4]; };
 
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(256) void lddt_pli_counts_kernel(const float* __res
 #pragma unroll
                 for (int t = 0; t < 4; ++t) packed += (have[e] && diff < thr.t[t]) ? 1u << (8 * t) : 0u;
             }
-            packed = wave_sum_u32(packed);
+            packed = wave_sum(packed);
             unsigned* r = red[step++ & 1];     // two buffers: the readers of one step are done before the step after the next stores
             if ((tid & 63) == 0) r[tid >> 6] = packed;
             __syncthreads();
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(256) void lddt_pli_select_kernel(const int* __restr
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const int s = (int)wave_sum_u32((unsigned)c4[t]);
+        const int s = (int)wave_sum((unsigned)c4[t]);
         if ((tid & 63) == 0) redc[tid >> 6][t] = s;
     }
     __syncthreads();

@@ -4,7 +4,7 @@
 // second pass adds them in a fixed order in float64, so a call gives the same bits every time (no floating-point atomics).
 // Masked entries keep the reference's arithmetic: it MULTIPLIES by the mask, so a non-finite coordinate poisons the sum even where
 // the mask is zero (0 * NaN = NaN); the kernels that skip masked pairs add 0 * (x + y + z) of every coordinate they load.
-#include "common.h"
+#include "loss_common.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -22,26 +22,6 @@ __device__ __forceinline__ float lddt_eps4(float d) {
     const float e = __builtin_amdgcn_exp2f(-PD_LOG2E * d);
     return __builtin_amdgcn_rcpf(fmaf(1.6487212707f, e, 1.f)) + __builtin_amdgcn_rcpf(fmaf(2.7182818285f, e, 1.f)) +
            __builtin_amdgcn_rcpf(fmaf(7.3890560989f, e, 1.f)) + __builtin_amdgcn_rcpf(fmaf(54.598150033f, e, 1.f));
-}
-
-// sum of one float64 per thread of an NT-thread block by a fixed tree (same bits every run); result in every thread
-template <int NT>
-__device__ __forceinline__ double block_sum_det(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-// mean_b (t_b^2 + sd^2) / (t_b sd)^2 in float64
-__device__ __forceinline__ double mean_edm_scale(const float* __restrict__ t_hat, int B, double sd, double* sh) {
-    double v = 0;
-    for (int b = threadIdx.x; b < B; b += 256) { const double t = t_hat[b]; v += (t * t + sd * sd) / ((t * sd) * (t * sd)); }
-    return block_sum_det<256>(v, sh) / B;
 }
 
 // ------------------------------------------------------------------ smooth lDDT (loss.py:162-181)

@@ -7,7 +7,7 @@
 // Each launcher reads its upstream scale from device memory (term weight x upstream gradient x finite flag, formed by the caller):
 // a zero scale writes / adds an exact zero, never 0 * NaN, so a skipped non-finite term adds no gradient.  The x launchers write
 // (accumulate = 0) or add to (accumulate = 1) one g_x; the caller fixes the launch order.
-#include "common.h"
+#include "loss_common.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -33,24 +33,6 @@ __device__ __forceinline__ float dsig4(const Sig4& s) {
     return (fmaf(-s.s0, s.s0, s.s0) + fmaf(-s.s1, s.s1, s.s1)) + (fmaf(-s.s2, s.s2, s.s2) + fmaf(-s.s3, s.s3, s.s3));
 }
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }     // torch.sign: 0 at 0
-
-template <int NT>
-__device__ __forceinline__ double block_sum_det(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
-__device__ __forceinline__ double mean_edm_scale(const float* __restrict__ t_hat, int B, double sd, double* sh) {
-    double v = 0;
-    for (int b = threadIdx.x; b < B; b += 256) { const double t = t_hat[b]; v += (t * t + sd * sd) / ((t * sd) * (t * sd)); }
-    return block_sum_det<256>(v, sh) / B;
-}
 
 // ------------------------------------------------------------------ smooth lDDT (loss.py:162-181)
 // d loss / d x_bi = (1/B) / (1e-9 + sum m) * sum_j 2 m_ij eps'(delta_ij) sign(delta_ij) (x_i - x_j) / d_ij  (m symmetric).

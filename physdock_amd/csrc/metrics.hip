@@ -65,18 +65,6 @@ __device__ __forceinline__ void expect2(const float v[4], const float c[4], cons
     et = row16_sum(st) * inv;
 }
 
-template <int NT>
-__device__ __forceinline__ double block_sum_det(double v, double* sh) {
-    __syncthreads();
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
-
 // ------------------------------------------------------------------ pLDDT (compute_plddt)
 // rows = P * A atoms, 16 rows per wave iteration; atom_plddts = 100 sum_k softmax(l)_k (k + 0.5) / nb
 template <bool VEC>

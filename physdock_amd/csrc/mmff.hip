@@ -17,6 +17,7 @@
 // Positions live in LDS; the BFGS vectors and the dense inverse Hessian (dim^2 doubles, dim = 3 L <= a few hundred)
 // live in a global workspace that stays L2-resident.  The whole relaxation is one launch and part of the step-loop graph.
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -34,33 +35,15 @@ constexpr double ELE_K = 332.0716;
 constexpr double ELE_BUF = 0.05;
 constexpr int NT = 256;
 
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double norm(V3 a) { return sqrt(dot(a, a)); }
-__device__ __forceinline__ V3 ld(const double* p, int a) { return {p[3 * a], p[3 * a + 1], p[3 * a + 2]}; }
-__device__ __forceinline__ double clip1(double c) { return c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c); }
+static_assert(NT == 256, "block_sum_d / block_max_d / threads_per_atom of reduce.h are the four-wave forms");
 
-// deterministic block reductions (fixed tree) of doubles; the result is returned to every thread
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double block_max_d(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
+using V3 = Vec3;                                       // geom3.h, with operators for the gradient formulas
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return add(a, b); }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return sub(a, b); }
+__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ double norm(V3 a) { return sqrt(dot(a, a)); }
+__device__ __forceinline__ V3 ld(const double* p, int a) { return load3(p + 3 * a); }
+__device__ __forceinline__ double clip1(double c) { return c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c); }
 
 // cos(theta) at j and its gradient with respect to the three points
 struct Ang { double c, la, lb; V3 gi, gj, gk; };
@@ -157,13 +140,6 @@ __device__ V3 bonded_term(const pd_mmff_terms& T, int kind, int t, int slot, con
     return dEdc * pick4(slot, dr1, gj, gk, dr4);
 }
 
-// threads that share one atom's terms: the largest power of two <= NT / L, at most 8 (lanes of one wave, adjacent)
-__device__ __forceinline__ int threads_per_atom(int L) {
-    int t = 8;
-    while (t > 1 && t * L > NT) t >>= 1;
-    return t;
-}
-
 // MMFF94 energy of the conformation p (LDS, [L][3]) - returned to every thread - and, if g != nullptr, its gradient
 // g[3 L] (any address space reachable by generic pointers).  Must be called by all NT threads.
 // An atom's incident bonded terms and its non-bonded row are dealt round-robin to `tpa` adjacent lanes, whose partial
@@ -171,7 +147,7 @@ __device__ __forceinline__ int threads_per_atom(int L) {
 // threads busy instead of 32 (one evaluation 100 -> ~20 us; the relaxation is a chain of ~15 of them per sampler step).
 __device__ double energy_grad(const pd_mmff_terms& T, const double* p, double* g, double* red) {
     const int L = T.n_atoms;
-    const int tpa = threads_per_atom(L), sub = threadIdx.x & (tpa - 1);
+    const int tpa = threads_per_atom(L, 8), sub = threadIdx.x & (tpa - 1);      // at most 8 lanes share one atom's terms
     double e_own = 0.0;
     const int a_step = NT / tpa;
     const int a_end = (L + a_step - 1) / a_step * a_step;          // whole passes: every lane takes part in the shuffles below

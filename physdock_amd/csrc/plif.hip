@@ -76,11 +76,6 @@ __device__ __forceinline__ float plif_distance(float ax, float ay, float az, flo
 // one fp32 division of two integers; 1 where the denominator is 0
 __device__ __forceinline__ float plif_ratio(int num, int den) { return den == 0 ? 1.f : (float)num / (float)den; }
 
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ __launch_bounds__(256) void plif_ligand_kernel(const float* __restrict__ x, const int* __restrict__ lig_idx,
                                                          const unsigned char* __restrict__ type,
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(256) void plif_residue_kernel(const unsigned char* 
     }
 #pragma unroll
     for (int k = 0; k < PD_PLIF_KINDS; ++k) {
-        const int s = wave_sum_int(cnt[k]);
+        const int s = wave_sum(cnt[k]);
         if ((tid & 63) == 0) red[tid >> 6][k] = s;
     }
     __syncthreads();
@@ -190,7 +185,7 @@ __global__ __launch_bounds__(256) void plif_compare_kernel(const unsigned char* 
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const int s = wave_sum_int(c[k]);
+        const int s = wave_sum(c[k]);
         if ((tid & 63) == 0) red[tid >> 6][k] = s;
     }
     __syncthreads();

@@ -47,6 +47,7 @@
 // integer sums are reduced, so the order does not matter; every value depends on its own pose alone and on no launch dimension:
 // results are bit-identical from run to run, whatever P is and wherever a pose sits.  No allocation, no synchronisation.
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -69,13 +70,6 @@ struct RingThresholds {
     double stack_dist, stack_offset, pication_dist, pication_offset, halogen_dist, cos_parallel, cos_t, cos_halogen;
 };
 
-struct Vec3 {
-    double x, y, z;
-};
-__device__ __forceinline__ Vec3 sub(Vec3 a, Vec3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dot(Vec3 a, Vec3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ Vec3 load3(const double* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ Vec3 load3(const float* p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
 // a degenerate ring reports the normal 0
 __device__ __forceinline__ bool ring_ok(Vec3 n) { return dot(n, n) > 0.5; }
 
@@ -100,17 +94,6 @@ __device__ __forceinline__ bool halogen_bond(Vec3 X, Vec3 Cc, Vec3 j, const Ring
     const Vec3 u = sub(Cc, X), w = sub(j, X);
     const double d2 = dot(w, w);
     return sqrt(d2) < t.halogen_dist && dot(u, w) / sqrt(dot(u, u) * d2) < t.cos_halogen;
-}
-
-__device__ __forceinline__ int wave_or(int b) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) b |= __shfl_xor(b, o);
-    return b;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(FRAME_BLOCK) void plif_rings_frame_kernel(const float* __restrict__ x, const int* __restrict__ ring_start,

@@ -41,6 +41,7 @@
 // rg_terms_kernel: one thread per (term, pose).  rg_reduce_kernel: one block per pose, minima / maxima / integer sums (any order gives
 // the same bits) and the residue bytes through the two CSRs.  rg_dihedral_kernel: one thread per (residue, angle, pose).
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -51,10 +52,7 @@ constexpr int RG_MAX_T = 1 << 20;      // terms
 constexpr int RG_WIDTH = 10;           // atoms per term row (PD_RECEPTOR_TERM_WIDTH of the header)
 constexpr int RG_TILE = 256;
 static_assert(RG_WIDTH == PD_RECEPTOR_TERM_WIDTH, "the row width the header documents");
-constexpr pd_u64 KEY_NONE = ((pd_u64)0x7f800000u << 32) | 0xffffffffu;      // (+inf, no pair)
 constexpr double RAD2DEG = 57.295779513082320876798154814105;
-
-__device__ __forceinline__ bool finite3(float a, float b, float c) { return isfinite(a) && isfinite(b) && isfinite(c); }
 
 __device__ __forceinline__ bool excluded(const int* __restrict__ excl_start, const int* __restrict__ excl_atom, int i, int j) {
     const int lo = i < j ? i : j, hi = i < j ? j : i;
@@ -113,19 +111,14 @@ __global__ __launch_bounds__(RG_TILE) void rg_clash_kernel(const float* __restri
     }
     if (i < A) {
         const unsigned lo = best_j < i ? best_j : i, hi = best_j < i ? i : best_j;
-        akey[(long long)p * A + i] = best_j < 0 ? KEY_NONE : ((pd_u64)__float_as_uint(best) << 32) | (lo << 12) | hi;
+        akey[(long long)p * A + i] = best_j < 0 ? PD_KEY_NONE : ((pd_u64)__float_as_uint(best) << 32) | (lo << 12) | hi;
         acount[(long long)p * A + i] = count;
         atom_clash[(long long)p * A + i] = (unsigned char)bit;
     }
 }
 
-struct d3 { double x, y, z; };
-__device__ __forceinline__ d3 sub(const d3 a, const d3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ d3 cross(const d3 a, const d3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(const d3 a, const d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
 // position of atom a of a pose in double; ok turns false when a < 0 or a coordinate is not finite
-__device__ __forceinline__ d3 load(const float* __restrict__ xp, int a, bool& ok) {
+__device__ __forceinline__ Vec3 load(const float* __restrict__ xp, int a, bool& ok) {
     if (a < 0) { ok = false; return {0.0, 0.0, 0.0}; }
     const float u = xp[3 * a], v = xp[3 * a + 1], w = xp[3 * a + 2];
     ok = ok && finite3(u, v, w);
@@ -135,25 +128,12 @@ __device__ __forceinline__ d3 load(const float* __restrict__ xp, int a, bool& ok
 // the dihedral of four atoms in degrees (double), NaN where it is not defined
 __device__ __forceinline__ double dihedral_deg(const float* __restrict__ xp, const int* __restrict__ idx) {
     bool ok = true;
-    const d3 p0 = load(xp, idx[0], ok), p1 = load(xp, idx[1], ok), p2 = load(xp, idx[2], ok), p3 = load(xp, idx[3], ok);
+    const Vec3 p0 = load(xp, idx[0], ok), p1 = load(xp, idx[1], ok), p2 = load(xp, idx[2], ok), p3 = load(xp, idx[3], ok);
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     if (!ok) return nan;
-    const d3 b1 = sub(p1, p0), b2 = sub(p2, p1), b3 = sub(p3, p2), m = cross(b1, b2), n = cross(b2, b3);
+    const Vec3 b1 = sub(p1, p0), b2 = sub(p2, p1), b3 = sub(p3, p2), m = cross(b1, b2), n = cross(b2, b3);
     if (!(dot(m, m) >= 1e-12) || !(dot(n, n) >= 1e-12)) return nan;
     return atan2(sqrt(dot(b2, b2)) * dot(b1, n), dot(m, n)) * RAD2DEG;
-}
-
-// one Jacobi rotation of the symmetric 3x3 matrix in the (p, q) plane (validity.hip)
-__device__ __forceinline__ void jacobi(double& app, double& aqq, double& apq, double& arp, double& arq) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
 }
 
 // largest distance of a group's atoms to its least-squares plane, in double; 0 for a group without a plane, +inf for one with a
@@ -165,7 +145,7 @@ __device__ __forceinline__ double group_planarity(const float* __restrict__ xp, 
 #pragma unroll 1
     for (int e = 0; e < RG_WIDTH; ++e) {
         if (grp[e] < 0) continue;
-        const d3 v = load(xp, grp[e], ok);
+        const Vec3 v = load(xp, grp[e], ok);
         cx += v.x; cy += v.y; cz += v.z;
         ++n;
     }
@@ -176,11 +156,12 @@ __device__ __forceinline__ double group_planarity(const float* __restrict__ xp, 
 #pragma unroll 1
     for (int e = 0; e < RG_WIDTH; ++e) {
         if (grp[e] < 0) continue;
-        const d3 v = load(xp, grp[e], ok);
+        const Vec3 v = load(xp, grp[e], ok);
         const double dx = v.x - cx, dy = v.y - cy, dz = v.z - cz;
         c00 += dx * dx; c11 += dy * dy; c22 += dz * dz; c01 += dx * dy; c02 += dx * dz; c12 += dy * dz;
     }
     c00 /= n; c11 /= n; c22 /= n; c01 /= n; c02 /= n; c12 /= n;
+    // (this tail is also in validity.hip: as a shared function it changes the instructions of both kernels)
     double a00 = c00, a11 = c11, a22 = c22, a01 = c01, a02 = c02, a12 = c12;
 #pragma unroll 1
     for (int sweep = 0; sweep < 10; ++sweep) {
@@ -205,7 +186,7 @@ __device__ __forceinline__ double group_planarity(const float* __restrict__ xp, 
 #pragma unroll 1
     for (int e = 0; e < RG_WIDTH; ++e) {
         if (grp[e] < 0) continue;
-        const d3 v = load(xp, grp[e], ok);
+        const Vec3 v = load(xp, grp[e], ok);
         out = fmax(out, fabs(nx * (v.x - cx) + ny * (v.y - cy) + nz * (v.z - cz)) * inv);
     }
     return out;
@@ -235,7 +216,7 @@ __global__ __launch_bounds__(256) void rg_terms_kernel(const float* __restrict__
         fail = (q >= (bond ? thr.bond_lo : thr.angle_lo) && q <= (bond ? thr.bond_hi : thr.angle_hi)) ? 0 : (bond ? 1 : 2);
     } else if (t < off.o[2]) {
         bool ok = true;
-        const d3 c = load(xp, at[0], ok), va = sub(load(xp, at[1], ok), c), vb = sub(load(xp, at[2], ok), c), ve = sub(load(xp, at[3], ok), c);
+        const Vec3 c = load(xp, at[0], ok), va = sub(load(xp, at[1], ok), c), vb = sub(load(xp, at[2], ok), c), ve = sub(load(xp, at[3], ok), c);
         const double sv = dot(va, cross(vb, ve)) * (double)term_ref[t];
         value = ok ? (float)sv : -INF;
         fail = (ok && sv > 0.0) ? 0 : 4;
@@ -255,17 +236,6 @@ __global__ __launch_bounds__(256) void rg_terms_kernel(const float* __restrict__
     }
     term_val[(long long)p * T + t] = value;
     term_fail[(long long)p * T + t] = (unsigned char)fail;
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_add(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void rg_reduce_kernel(const float* __restrict__ term_val, const unsigned char* __restrict__ term_fail,
@@ -296,7 +266,7 @@ __global__ __launch_bounds__(256) void rg_reduce_kernel(const float* __restrict_
 #pragma unroll
         for (int k = 0; k < 6; ++k) c[k] += (b >> k) & 1;
     }
-    pd_u64 key = KEY_NONE;
+    pd_u64 key = PD_KEY_NONE;
     for (int a = tid; a < A; a += 256) {
         key = pd_key_min(key, akey[(long long)p * A + a]);
         c[6] += acount[(long long)p * A + a];
@@ -310,7 +280,7 @@ __global__ __launch_bounds__(256) void rg_reduce_kernel(const float* __restrict_
     }
     f[0] = wave_min(f[0]); f[1] = wave_max(f[1]); f[2] = wave_min(f[2]); f[3] = wave_max(f[3]); f[4] = wave_max(f[4]); f[5] = wave_max(f[5]);
 #pragma unroll
-    for (int k = 0; k < 7; ++k) c[k] = wave_add(c[k]);
+    for (int k = 0; k < 7; ++k) c[k] = wave_sum(c[k]);
     key = pd_wave_key_min(key);
     if ((tid & 63) == 0) {
 #pragma unroll
@@ -334,8 +304,8 @@ __global__ __launch_bounds__(256) void rg_reduce_kernel(const float* __restrict_
     v[0] = f[0]; v[1] = f[1]; v[2] = f[2]; v[3] = f[3];
     v[4] = __uint_as_float((unsigned)(key >> 32)); v[5] = f[4]; v[6] = f[5]; v[7] = (float)c[2];
     const unsigned pair = (unsigned)key;
-    worst[2 * p] = key == KEY_NONE ? -1 : (int)(pair >> 12);
-    worst[2 * p + 1] = key == KEY_NONE ? -1 : (int)(pair & (RG_MAX_A - 1));
+    worst[2 * p] = key == PD_KEY_NONE ? -1 : (int)(pair >> 12);
+    worst[2 * p + 1] = key == PD_KEY_NONE ? -1 : (int)(pair & (RG_MAX_A - 1));
     int fl = 0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) {

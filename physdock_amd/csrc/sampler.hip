@@ -3,25 +3,12 @@
 // utils/tensor_utils.py:545-586,724-778).  Host-known schedule scalars (t_hat, c_in, ...)
 // are passed by value, so the whole loop is capturable into one hipGraph.
 #include "common.h"
+#include "philox.h"
 #include "physdock_hip.h"
 
 namespace {
 
-// ------------------------------------------------------------------ Philox4x32-10
-struct Philox {
-    uint32_t k0, k1;
-    __device__ __forceinline__ void round(uint32_t (&c)[4], uint32_t ka, uint32_t kb) const {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ ka, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ kb, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-    }
-    __device__ __forceinline__ void gen(uint32_t (&c)[4]) const {
-        uint32_t a = k0, b = k1;
-#pragma unroll
-        for (int i = 0; i < 10; ++i) { round(c, a, b); a += 0x9E3779B9u; b += 0xBB67AE85u; }
-    }
-};
+// ------------------------------------------------------------------ uniform and normal draws from Philox4x32-10 (philox.h)
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ void normals4(const Philox& ph, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, float (&n)[4]) {
     uint32_t c[4] = {c0, c1, c2, c3};

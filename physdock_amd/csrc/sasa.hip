@@ -61,11 +61,6 @@ constexpr float REACH_REL = 1.0001220703125f;     // 1 + 2^-13
 constexpr float REACH_ABS = 0.01f;
 static_assert(LIST == 256 && PD_SASA_MAX_POINTS == 1024 && PD_SASA_TOTALS == 8, "the numbers the header documents");
 
-__device__ __forceinline__ int sasa_wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float sasa_dist2(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
@@ -182,8 +177,8 @@ __global__ __launch_bounds__(256) void sasa_point_kernel(const float* __restrict
         n_free += has && !(flag[m] & 1) ? 1 : 0;
         n_bound += has && flag[m] == 0 ? 1 : 0;
     }
-    n_free = sasa_wave_sum_int(n_free);
-    n_bound = sasa_wave_sum_int(n_bound);
+    n_free = wave_sum(n_free);
+    n_bound = wave_sum(n_bound);
     if (lane == 0) red[wave][0] = n_free, red[wave][1] = n_bound;
     __syncthreads();
     if (tid == 0) {
@@ -223,7 +218,7 @@ __global__ __launch_bounds__(256) void sasa_pose_kernel(const unsigned char* __r
         residue_buried[(long long)p * R + r] = sum;
         n_res += sum > 0.f ? 1 : 0;
     }
-    n_res = sasa_wave_sum_int(n_res);
+    n_res = wave_sum(n_res);
     if (lane == 0) red[wave] = n_res;
     if (wave == 0) {                                                 // the receptor total, ascending atoms, 64 at a time
         float sum = 0.f;

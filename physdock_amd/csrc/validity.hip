@@ -24,6 +24,7 @@
 // inside the ligand (fp32; column 7 in double: one thread per group, eigenvalues by cyclic Jacobi on the 3x3 covariance, the normal
 // as the largest cross product of two rows of C - lambda I) and the flags.
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -34,7 +35,6 @@ constexpr int VAL_GROUP = 8;           // atoms per planar group (rows of `plana
 constexpr int VAL_MAX_A = 1 << 22;     // pose atoms: 22 bits of the key
 constexpr int REC_TILE = 256;          // pose atoms per block of the receptor kernel (PD_VALIDITY_REC_TILE of the header)
 static_assert(REC_TILE == PD_VALIDITY_REC_TILE, "the workspace size the header documents");
-constexpr pd_u64 KEY_NONE = ((pd_u64)0x7f800000u << 32) | 0xffffffffu;      // (+inf, no pair)
 
 __device__ __forceinline__ float dist(const f32x4 a, const f32x4 b) {
     const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
@@ -52,12 +52,6 @@ __device__ __forceinline__ void stage_ligand(f32x4* sm, const float* __restrict_
     }
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-
 __global__ __launch_bounds__(REC_TILE) void validity_receptor_kernel(const float* __restrict__ x, const int* __restrict__ lig_idx,
                                                                     const float* __restrict__ radius,
                                                                     const unsigned char* __restrict__ rec_mask,
@@ -70,7 +64,7 @@ __global__ __launch_bounds__(REC_TILE) void validity_receptor_kernel(const float
     stage_ligand(sm, xp, lig_idx, radius, lig_active, L);
     __syncthreads();
     const int j = tile * REC_TILE + tid;
-    pd_u64 kr = KEY_NONE, kd = KEY_NONE;   // (ratio, a, j) and (distance, -)
+    pd_u64 kr = PD_KEY_NONE, kd = PD_KEY_NONE;   // (ratio, a, j) and (distance, -)
     if (j < A && rec_mask[j]) {
         const f32x4 xj = {xp[3 * j], xp[3 * j + 1], xp[3 * j + 2], 0.f};
         const float rj = radius[j];
@@ -98,20 +92,6 @@ __global__ __launch_bounds__(REC_TILE) void validity_receptor_kernel(const float
     }
 }
 
-// one Jacobi rotation of the symmetric 3x3 matrix in the (p, q) plane: app, aqq the diagonal entries, apq the entry it annihilates,
-// arp, arq the entries of the third row.  Values only (the eigenvector comes from a cross product below): no indexing, no stack.
-__device__ __forceinline__ void jacobi(double& app, double& aqq, double& apq, double& arp, double& arq) {
-    if (apq == 0.0) return;
-    const double theta = (aqq - app) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double rp = c * arp - s * arq, rq = s * arp + c * arq;
-    arp = rp; arq = rq;
-}
-
 // largest distance (Angstrom) of a group's atoms to its least-squares plane, in double; 0 for a group without a plane
 __device__ __forceinline__ double group_planarity(const f32x4* sm, const int* __restrict__ grp) {
     double cx = 0.0, cy = 0.0, cz = 0.0;
@@ -136,6 +116,7 @@ __device__ __forceinline__ double group_planarity(const f32x4* sm, const int* __
         c00 += dx * dx; c11 += dy * dy; c22 += dz * dz; c01 += dx * dy; c02 += dx * dz; c12 += dy * dz;
     }
     c00 /= n; c11 /= n; c22 /= n; c01 /= n; c02 /= n; c12 /= n;
+    // (this tail is also in receptor_geometry.hip: as a shared function it changes the instructions of both kernels)
     double a00 = c00, a11 = c11, a22 = c22, a01 = c01, a02 = c02, a12 = c12;
 #pragma unroll 1
     for (int sweep = 0; sweep < 10; ++sweep) {          // cyclic Jacobi converges quadratically: 3x3 is done after five or six
@@ -201,7 +182,7 @@ __global__ __launch_bounds__(256) void validity_pose_kernel(const float* __restr
         if (xa[3] > 0.f && xb[3] > 0.f) clash = fminf(clash, dist(xa, xb) / (xa[3] + xb[3]));
     }
     if (tid < G) plane = (float)group_planarity(sm, planar + tid * VAL_GROUP);
-    pd_u64 kr = KEY_NONE, kd = KEY_NONE;
+    pd_u64 kr = PD_KEY_NONE, kd = PD_KEY_NONE;
     for (int t = tid; t < ntiles; t += 256) {
         kr = pd_key_min(kr, ws[((long long)p * ntiles + t) * 2]);
         kd = pd_key_min(kd, ws[((long long)p * ntiles + t) * 2 + 1]);
@@ -227,8 +208,8 @@ __global__ __launch_bounds__(256) void validity_pose_kernel(const float* __restr
     const unsigned pair = (unsigned)kr;
     float* v = val + (long long)p * 8;
     v[0] = lo12; v[1] = hi12; v[2] = lo13; v[3] = hi13; v[4] = clash; v[5] = rec; v[6] = rec_d; v[7] = plane;
-    worst[2 * p] = kr == KEY_NONE ? -1 : (int)(pair >> 22);
-    worst[2 * p + 1] = kr == KEY_NONE ? -1 : (int)(pair & (VAL_MAX_A - 1));
+    worst[2 * p] = kr == PD_KEY_NONE ? -1 : (int)(pair >> 22);
+    worst[2 * p + 1] = kr == PD_KEY_NONE ? -1 : (int)(pair & (VAL_MAX_A - 1));
     int f = 0;
     if (lo12 < thr.bond_lo || hi12 > thr.bond_hi) f |= 1;
     if (lo13 < thr.angle_lo || hi13 > thr.angle_hi) f |= 2;

@@ -33,6 +33,7 @@
 // chain's scalars, which is what makes a search resumable launch by launch.  LDS: 6 L doubles is 48 KB at L = 1024, with the 2 KB of
 // static scratch inside the 64 KB a workgroup may have; the chains are latency-bound float64 VALU work, as the refinement is.
 #include "common.h"
+#include "philox.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -51,17 +52,6 @@ struct Tab {
     const int* rot; const unsigned* rot_mask; const int* intra_start; const int* intra_atom;
     int A, L, T;
 };
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
 
 // one pair at distance r: its weighted energy and d energy / d r
 __device__ __forceinline__ void pair_energy(double r, double rsum, unsigned ti, unsigned tj, double& e, double& de) {
@@ -133,8 +123,8 @@ __device__ void evaluate(const Tab& t, const float* __restrict__ xp, const doubl
                 }
             }
         }
-        ei = wave_sum_d(ei); ea = wave_sum_d(ea);
-        gx = wave_sum_d(gx); gyy = wave_sum_d(gyy); gz = wave_sum_d(gz);
+        ei = wave_sum(ei); ea = wave_sum(ea);
+        gx = wave_sum(gx); gyy = wave_sum(gyy); gz = wave_sum(gz);
         if (lane == 0) { gy[3 * i] = gx; gy[3 * i + 1] = gyy; gy[3 * i + 2] = gz; }
         e_inter += ei; e_intra += ea;                                   // ascending atoms of this wave
     }
@@ -151,7 +141,7 @@ __device__ void centroid(const double* y, int L, double* cen) {
     if (wave < 3) {
         double s = 0.0;
         for (int i = lane; i < L; i += 64) s += y[3 * i + wave];
-        s = wave_sum_d(s);
+        s = wave_sum(s);
         if (lane == 0) cen[wave] = s / (double)L;
     }
     __syncthreads();
@@ -182,7 +172,7 @@ __device__ void generalised(const Tab& t, const double* y, const double* gy, dou
                 acc += gy[3 * i] * (uy * vz - uz * vy) + gy[3 * i + 1] * (uz * vx - ux * vz) + gy[3 * i + 2] * (ux * vy - uy * vx);
             }
         }
-        acc = wave_sum_d(acc);
+        acc = wave_sum(acc);
         if (lane == 0) gg[c] = acc;
     }
     __syncthreads();
@@ -283,14 +273,14 @@ __device__ __forceinline__ void descend(const Tab& t, const float* __restrict__ 
     const double f0 = fp;
     int it = 0, nev = 1, st = 1;
     if (trace && tid == 0) trace[0] = fp;
-    if (wave_max_d(fabs(g)) < grad_tol) st = 0;
+    if (wave_max(fabs(g)) < grad_tol) st = 0;
     while (st == 1 && it < max_iters) {
         // ---------------- the line search (Numerical Recipes lnsrch)
-        const double s = sqrt(wave_sum_d(xi * xi));
+        const double s = sqrt(wave_sum(xi * xi));
         if (s > max_step) xi *= max_step / s;
-        const double slope = wave_sum_d(xi * g);
+        const double slope = wave_sum(xi * g);
         if (!(slope < 0.0)) { st = 2; break; }
-        const double lam_min = MOVETOL / wave_max_d(fabs(xi));
+        const double lam_min = MOVETOL / wave_max(fabs(xi));
         double lam = 1.0, lam2 = 0.0, val2 = 0.0, fnew = fp;
         bool ok = false;
         for (int ls = 0; ls < 1000; ++ls) {
@@ -327,7 +317,7 @@ __device__ __forceinline__ void descend(const Tab& t, const float* __restrict__ 
         const double step = lam * xi, g_old = g;
         generalised(t, y, gy, cen, gg);                                  // (its barriers also publish pos)
         g = lane < n ? gg[lane] : 0.0;
-        if (wave_max_d(fabs(g)) < grad_tol) { st = 0; break; }
+        if (wave_max(fabs(g)) < grad_tol) { st = 0; break; }
         // ---------------- BFGS update of the inverse Hessian
         const double dg = g - g_old;
         double hdg = 0.0;
@@ -335,8 +325,8 @@ __device__ __forceinline__ void descend(const Tab& t, const float* __restrict__ 
             const double v = __shfl(dg, j);
             if (lane < n) hdg += H[j * n + lane] * v;
         }
-        double fac = wave_sum_d(dg * step);
-        const double fae = wave_sum_d(dg * hdg), sdg = wave_sum_d(dg * dg), sxi = wave_sum_d(step * step);
+        double fac = wave_sum(dg * step);
+        const double fae = wave_sum(dg * hdg), sdg = wave_sum(dg * dg), sxi = wave_sum(step * step);
         __syncthreads();                                                 // every wave has read H
         if (fac > sqrt(EPS_ * sdg * sxi)) {
             fac = 1.0 / fac;
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
         d2 += dx * dx + dy * dy + dz * dz;
         ob[3 * a] = (float)pos[3 * i]; ob[3 * a + 1] = (float)pos[3 * i + 1]; ob[3 * a + 2] = (float)pos[3 * i + 2];
     }
-    d2 = wave_sum_d(d2);
+    d2 = wave_sum(d2);
     if (lane == 0) red[tid >> 6] = d2;
     __syncthreads();
     if (tid == 0) {
@@ -404,21 +394,6 @@ __global__ __launch_bounds__(NT) void vina_refine_kernel(const Tab t, const floa
 }
 
 // ------------------------------------------------------------------ the Monte-Carlo search (tests/vina_search_ref.py is its definition)
-struct Philox {                                         // Philox4x32-10, the generator of sampler.hip and conformers.hip (a copy: its bits stay put)
-    uint32_t k0, k1;
-    __device__ __forceinline__ void gen(uint32_t (&c)[4]) const {
-        uint32_t a = k0, b = k1;
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-            const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ a, n1 = (uint32_t)p1;
-            const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ b, n3 = (uint32_t)p0;
-            c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-            a += 0x9E3779B9u; b += 0xBB67AE85u;
-        }
-    }
-};
-
 constexpr int VS_SCALARS = 8;                                            // E_cur, E_best, E_start, best_step, accepted, evaluations, 2 spare
 constexpr int VS_MAX_K = 64, VS_MAX_BLOCKS = 65535;
 constexpr double VS_PI = 3.14159265358979323846;

@@ -492,16 +492,9 @@ class Hydrogens(_ByteRows):
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernels' tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in ("parent", "ref", "mode", "length", "a", "b", "side", "group_h", "acc", "racc_start", "lig_acc_slot", "polar",
-                           "rh_start", "polar_slot", "ligand_idx")}
-            self._tables[device] = t
-        return t
+        names = ("parent", "ref", "mode", "length", "a", "b", "side", "group_h", "acc", "racc_start", "lig_acc_slot", "polar", "rh_start",
+                 "polar_slot", "ligand_idx")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def _poses(self, x_pred, what):
         if x_pred.dim() != 3 or x_pred.shape[1] != self.n_pose_atoms or x_pred.shape[2] != 3:

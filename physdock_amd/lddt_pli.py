@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .scoring import _host
 from .symmetry import MAX_ATOMS, MAX_PERMS
 
 __all__ = ["LddtPli", "DEFAULT_RADIUS", "DEFAULT_THRESHOLDS", "MAX_ATOMS", "MAX_PERMS", "MAX_CONTACTS", "CONTACT_TILE", "LDS_CANDIDATES"]
@@ -40,10 +41,6 @@ DEFAULT_THRESHOLDS = (0.5, 1.0, 2.0, 4.0)
 MAX_CONTACTS, CONTACT_TILE, LDS_CANDIDATES = (1 << 29) - 1, 512, 4096
 
 _TABLES = ("ligand_idx", "contact_start", "contact_atom", "contact_dist", "cand_start", "cand_atom", "slot_t")
-
-
-def _host(t, dtype):
-    return np.asarray(t.detach().cpu() if isinstance(t, torch.Tensor) else t, dtype=dtype)
 
 
 class LddtPli:
@@ -147,16 +144,12 @@ class LddtPli:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernels' tables on `device` (uploaded once; slot_t as int16 storage of its unsigned 16-bit entries)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in _TABLES if k != "slot_t"}
-            t["slot_t"] = torch.from_numpy(self.slot_t.view(np.int16)).to(device)
-            t["atom_contacts"] = torch.from_numpy(self.atom_contacts).to(device)
-            self._tables[device] = t
-        return t
+        def make(up):
+            t = {k: up(getattr(self, k)) for k in _TABLES if k != "slot_t"}
+            t["slot_t"] = up(self.slot_t.view(np.int16))
+            t["atom_contacts"] = up(self.atom_contacts)
+            return t
+        return ops.cached_upload(self._tables, device, make)
 
     def score(self, x_pred: torch.Tensor) -> dict:
         """x_pred [P,A,3] (device) -> dict of device tensors: lddt_pli [P] fp32; conserved [P,4] int32 (the chosen permutation's

@@ -10,6 +10,7 @@ import math
 import os
 import threading
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -17,6 +18,24 @@ from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SILU, OUT_BIASFRAG, OUT_
                    OUT_TRANSPOSED, AttnArgs, GemmArgs, check, ptr, stream)
 
 RMS, LN = 0, 1
+
+
+def resolve_device(device) -> torch.device:
+    """`device` as a torch.device that can key a cache: a bare "cuda" becomes the current device, everything else passes through"""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def cached_upload(cache: dict, device, make):
+    """cache[resolve_device(device)], built on first use by make(up): up(array) is the contiguous numpy array as a tensor on the
+    device.  The `tables(device)` of every per-system table class: what `make` returns is uploaded once per device."""
+    device = resolve_device(device)
+    t = cache.get(device)
+    if t is None:
+        t = cache[device] = make(lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device))
+    return t
 
 _CONST = {}
 _CONST_LOCK = threading.Lock()

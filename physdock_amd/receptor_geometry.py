@@ -490,16 +490,8 @@ class ReceptorGeometry:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernels' tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device) for k in _DEVICE_KEYS}
-            t["chi_ref"] = torch.from_numpy(np.ascontiguousarray(self.chi_ref)).to(device)
-            t["pi_periodic"] = torch.from_numpy(np.ascontiguousarray(self.pi_periodic)).to(device)
-            self._tables[device] = t
-        return t
+        names = (*_DEVICE_KEYS, "chi_ref", "pi_periodic")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def _poses(self, x_pred, what):
         if x_pred.dim() != 3 or x_pred.shape[1] != self.n_pose_atoms or x_pred.shape[2] != 3:

@@ -176,16 +176,9 @@ class VinaRefine:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-            t = dict(self.vina.tables(device), rot=up(self.rot), rot_mask=up(self.rot_mask.view(np.int32)),
-                     intra_start=up(self.intra_start), intra_atom=up(self.intra_atom))
-            self._tables[device] = t
-        return t
+        return ops.cached_upload(self._tables, device, lambda up: dict(
+            self.vina.tables(device), rot=up(self.rot), rot_mask=up(self.rot_mask.view(np.int32)), intra_start=up(self.intra_start),
+            intra_atom=up(self.intra_atom)))
 
     def _poses(self, x_pred, what):
         if x_pred.dim() != 3 or x_pred.shape[1] != self.n_pose_atoms or x_pred.shape[2] != 3:

@@ -305,16 +305,8 @@ class RingInteractions(_ByteRows):
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in ("types", "charges", "ligand_idx", "lig_active", "res_start", "res_atom", "ring_start", "ring_atom", "ring_residue",
-                           "halogens")}
-            self._tables[device] = t
-        return t
+        names = ("types", "charges", "ligand_idx", "lig_active", "res_start", "res_atom", "ring_start", "ring_atom", "ring_residue", "halogens")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def fingerprint(self, x_pred: torch.Tensor) -> Dict[str, torch.Tensor]:
         """x_pred [P,A,3] (device) -> dict of device tensors: bits uint8 [P,R] (bit k = kind k of `RING_KIND_NAMES` between the ligand

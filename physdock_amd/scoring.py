@@ -317,15 +317,8 @@ class VinaScore:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in ("types", "ligand_idx", "rec_mask", "lig_active")}
-            self._tables[device] = t
-        return t
+        names = ("types", "ligand_idx", "rec_mask", "lig_active")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def score(self, x_pred: torch.Tensor, forces: bool = False) -> Dict[str, torch.Tensor]:
         """x_pred [P,A,3] (device) -> dict of device tensors: score [P] (kcal/mol, lower is better), inter [P] (before the division by

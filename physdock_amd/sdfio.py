@@ -190,14 +190,7 @@ class SdfTemplate:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(getattr(self, k)).to(device) for k in ("tmpl", "map", "atom")}
-            self._tables[device] = t
-        return t
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in ("tmpl", "map", "atom")})
 
     @staticmethod
     def items(properties, n_poses: int, device=None):

@@ -188,15 +188,8 @@ class BuriedSurface:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in ("cls", "radius", "unit", "ligand_idx", "polar", "res_start", "res_atom")}
-            self._tables[device] = t
-        return t
+        names = ("cls", "radius", "unit", "ligand_idx", "polar", "res_start", "res_atom")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def measure(self, x_pred: torch.Tensor) -> Dict[str, torch.Tensor]:
         """x_pred [P,A,3] (device) -> dict of device tensors: free_points int32 [P,L], buried_points int32 [P,A], per_atom fp32 [P,L],

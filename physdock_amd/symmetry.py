@@ -16,6 +16,7 @@ from typing import Iterable, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import ops
 from .chirality import symmetry_classes
 
 __all__ = ["automorphisms", "LigandSymmetry", "MAX_ATOMS", "MAX_PERMS"]
@@ -148,14 +149,7 @@ class LigandSymmetry:
 
     def table(self, device) -> torch.Tensor:
         """the packed table on `device`: int16 storage [n_atoms, n_perms] of the unsigned 16-bit entries"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = torch.from_numpy(self._packed.view(np.int16)).to(device).contiguous()
-            self._tables[device] = t
-        return t
+        return ops.cached_upload(self._tables, device, lambda up: up(self._packed.view(np.int16)))
 
     def __repr__(self):
         return f"LigandSymmetry(n_atoms={self.n_atoms}, n_perms={self.n_perms}, complete={self.complete})"

@@ -189,15 +189,8 @@ class PoseValidity:
     # ------------------------------------------------------------------ device side
     def tables(self, device) -> Dict[str, torch.Tensor]:
         """the kernel's tables on `device` (uploaded once)"""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        t = self._tables.get(device)
-        if t is None:
-            t = {k: torch.from_numpy(np.ascontiguousarray(getattr(self, k))).to(device)
-                 for k in ("ligand_idx", "radius", "rec_mask", "lig_active", "pair12", "d12_ref", "pair13", "d13_ref", "far", "planar")}
-            self._tables[device] = t
-        return t
+        names = ("ligand_idx", "radius", "rec_mask", "lig_active", "pair12", "d12_ref", "pair13", "d13_ref", "far", "planar")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
     def check(self, x_pred: torch.Tensor) -> Dict[str, torch.Tensor]:
         """x_pred [P,A,3] (device) -> dict of device tensors: valid [P] bool, flags [P] int32 (bit mask in CHECK_NAMES order),

@@ -156,6 +156,25 @@ def test_host_tables_against_the_naive_loops(name):
     assert t.n_candidates == int(r["cand_start"][-1]) and t.symmetry_complete is True
 
 
+def test_tables_are_uploaded_once_per_device_with_the_host_dtypes():
+    from physdock_amd import ops
+    assert ops.resolve_device("cpu") == torch.device("cpu")
+    assert ops.resolve_device(torch.device("cuda", 0)) == torch.device("cuda", 0)
+    r = cases.reference("ring")
+    t = tables_of(r)
+    d = t.tables("cpu")
+    assert t.tables(torch.device("cpu")) is d and list(t._tables) == [torch.device("cpu")]
+    L, M, n, c = len(r["lig"]), len(r["table_perms"]), int(r["start"][-1]), int(r["cand_start"][-1])
+    want = {"ligand_idx": (torch.int32, (L,)), "contact_start": (torch.int32, (L + 1,)), "contact_atom": (torch.int32, (n,)),
+            "contact_dist": (torch.float32, (n,)), "cand_start": (torch.int32, (L + 1,)), "cand_atom": (torch.int32, (c,)),
+            "slot_t": (torch.int16, (L, M)), "atom_contacts": (torch.int32, (L,))}
+    assert list(d) == list(want)
+    for k, (dtype, shape) in want.items():
+        assert d[k].dtype == dtype and tuple(d[k].shape) == shape and d[k].is_contiguous(), k
+        host = t.slot_t.view(np.int16) if k == "slot_t" else getattr(t, k)
+        assert np.array_equal(d[k].numpy(), host), k
+
+
 def test_masked_atoms_are_left_out_of_the_tables():
     r = cases.reference("masked")
     t = tables_of(r)
