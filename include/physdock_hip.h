@@ -1073,6 +1073,41 @@ int pd_metrics_clash(const float* x_pred, const float* a_mask, const int* chain,
                      const float* ptm, const float* iptm, int tm_stride, long long* has_clash, float* ranking, int B, int A,
                      int n_chain, int skip_self_pairs, void* stream);
 
+/* ---- Gaussian shape and feature overlap (shape_overlap.hip; additive exports of ABI 11) -----------------------------
+ * First-order Gaussian overlap (Grant, Gallardo & Pickup 1996) of molecules that need no atom correspondence; float64 from the fp32
+ * coordinates, ordered sums, no atomics: bit-identical from launch to launch and whatever else is in the batch.
+ * tests/shape_overlap_ref.py is the written definition.  A "side" is n structures of one molecule: L named atoms with the exponents
+ * alpha [L] (DEVICE doubles, kappa / R_i^2) and F features in CSR form (feat_start [F+1], feat_atom: indices 0 .. L-1 into the named
+ * atoms, feat_kind [F] in 0 .. 5); features are Gaussians of the exponent color_alpha.  The caller guarantees every index is inside
+ * its array (physdock_amd/shape.py checks them on the host).  L, F <= 1024, n <= 65535 per side, A <= 2^22.
+ * pd_shape_prepare : ws (pd_shape_workspace_numel(n, L, F) = n (3 L + 3 F + 2) doubles) = per structure the atoms [L][3], the
+ *                    feature points [F][3] (the mean of the members) and (O_AA, C_AA); both NaN when a named atom is not finite.
+ * pd_shape_overlap : sides a (rows) and b (columns) as prepared, with the lengths of their workspaces.  o_ab, c_ab double [n,C],
+ *                    shape_tanimoto, color_tanimoto, combo float [n,C]; atom_share double [n,L] (C == 1 only): each row atom's part
+ *                    of o_ab.  Every output may be NULL.  pairwise != 0 needs the same side twice: the columns >= row are computed and
+ *                    mirrored.  A NaN structure gives NaN in its whole row / column.
+ * pd_shape_overlay : L, M <= 256.  Maximises O(move(A, s), B) over rigid motions from five starts (principal axes aligned and turned
+ *                    by 180 degrees about none, the first, second, third axis; the pose as it stands) with the minimiser of
+ *                    pd_vina_refine at zero torsions.  ws: pd_shape_overlay_workspace_numel(n, C, L) = 5 n C (16 + 3 L) doubles.  Per
+ *                    (row, column): transform double [7] = the unit quaternion (w, x, y, z), w >= 0, and t with x' = R x + t;
+ *                    x_fit double [L][3] (nullable) = the row's atoms as the minimiser left them; scores float [3]
+ *                    (shape, colour, combo at the optimum); overlap, overlap_start (in place) double; best_start, iterations,
+ *                    evaluations, status (0 converged / 1 max_iters / 2 line search) int32 of the winning start.
+ * PD_ERR_ARG / PD_ERR_UNSUPPORTED before anything is launched for NULL required pointers, sizes out of range or a short workspace. */
+long long pd_shape_workspace_numel(int n, int L, int F);
+int pd_shape_prepare(const float* x, const int* lig_idx, const double* alpha, const int* feat_start, const int* feat_atom,
+                     const int* feat_kind, double color_alpha, double* ws, long long ws_numel, int n, int A, int L, int F, void* stream);
+int pd_shape_overlap(const double* ws_a, long long ws_a_numel, const double* alpha_a, const int* kind_a, int n, int L, int Fa,
+                     const double* ws_b, long long ws_b_numel, const double* alpha_b, const int* kind_b, int C, int M, int Fb,
+                     double color_alpha, int pairwise, double* o_ab, double* c_ab, float* shape_tanimoto, float* color_tanimoto,
+                     float* combo, double* atom_share, void* stream);
+long long pd_shape_overlay_workspace_numel(int n, int C, int L);
+int pd_shape_overlay(const double* ws_a, long long ws_a_numel, const double* alpha_a, const int* kind_a, int n, int L, int Fa,
+                     const double* ws_b, long long ws_b_numel, const double* alpha_b, const int* kind_b, int C, int M, int Fb,
+                     double color_alpha, int max_iters, double grad_tol, double max_step, double* ws, long long ws_numel,
+                     double* transform, double* x_fit, float* scores, double* overlap, double* overlap_start, int* best_start, int* iterations,
+                     int* evaluations, int* status, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

@@ -281,6 +281,11 @@ def _declare(L):
     sig("pd_receptor_geometry_workspace_numel", i, i)                                        # ABI 11, additive (receptor_geometry.hip)
     sig("pd_receptor_geometry", p, p, p, p, p, p, i, i, i, i, i, p, p, p, p, ReceptorThresholds, p, p, p, p, p, p, p, p, p, i, i, i, p)
     sig("pd_receptor_dihedrals", p, p, p, i, i, i, p)
+    sig("pd_shape_workspace_numel", i, i, i, restype=ll)                                     # ABI 11, additive (shape_overlap.hip)
+    sig("pd_shape_prepare", p, p, p, p, p, p, d, p, ll, i, i, i, i, p)
+    sig("pd_shape_overlap", p, ll, p, p, i, i, i, p, ll, p, p, i, i, i, d, i, p, p, p, p, p, p, p)
+    sig("pd_shape_overlay_workspace_numel", i, i, i, restype=ll)
+    sig("pd_shape_overlay", p, ll, p, p, i, i, i, p, ll, p, p, i, i, i, d, i, d, d, p, ll, p, p, p, p, p, p, p, p, p, p)
 
 
 def ptr(t):

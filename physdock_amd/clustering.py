@@ -8,7 +8,8 @@ head's, the Vina score's, the refined score's - "the best pose of each mode" is 
 The distance is the (symmetry-corrected) pairwise ligand RMSD of `ranking.pairwise_ligand_rmsd`, or 1 - the Tanimoto similarity of
 `InteractionFingerprint.pairwise` (`metric="interactions"`: poses that touch the same residues in the same ways share a mode, and
 `cutoff` is then a Tanimoto distance in 0 .. 1), or the best-fit ligand RMSD of `bestfit.BestFitRmsd.pairwise` (`metric="conformer"`:
-poses with the same internal conformation share a mode, wherever they sit).
+poses with the same internal conformation share a mode, wherever they sit), or 1 - the shape Tanimoto of
+`shape.ShapeOverlap.pairwise` (`metric="shape"`: poses that fill the same volume share a mode; `cutoff` is then that distance in 0 .. 1).
 
 `cluster` returns device tensors and never reads back: `labels` int32 [n] (-1 for an invalid pose), `dist_to_leader` fp32 [n], and per
 mode, in arrays of length n of which the first `n_clusters` entries count (behind them ids are -1, sizes 0, floats NaN): `leader`,
@@ -32,12 +33,12 @@ from . import ops
 
 MAX_POSES = 8192                      # PD_POSE_CLUSTERS_MAX_POSES
 ORDERS = (None, "confidence", "vina", "vina_refined")
-METRICS = ("rmsd", "interactions", "conformer")
+METRICS = ("rmsd", "interactions", "conformer", "shape")
 _PER_MODE = ("leader", "size", "radius", "medoid", "spread", "mean_score")
 
 
 class PoseClusters:
-    """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"`), `by` - the order `redock` walks
+    """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"` and `"shape"`), `by` - the order `redock` walks
     the poses in (None: pose ids; "confidence", "vina", "vina_refined": the result's `order_confidence`, `order_vina`,
     `order_vina_refined`) - and `metric`.  `cluster` and `binding_modes` take their order from the caller."""
 
@@ -174,7 +175,8 @@ class PoseClusters:
                      spread=float(cols["spread"][k]), mean_score=float(cols["mean_score"][k])) for k in range(K)]
 
 
-def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None, conformer_rmsd=None) -> None:
+def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None, conformer_rmsd=None,
+                               shape=None) -> None:
     """redock(clusters=): raise ValueError for what the spec needs and the call lacks - before any sampling"""
     if clusters is None:
         return
@@ -184,6 +186,8 @@ def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=N
         raise ValueError("clusters=PoseClusters(metric='interactions') needs interactions=")
     if clusters.metric == "conformer" and conformer_rmsd is None:
         raise ValueError("clusters=PoseClusters(metric='conformer') needs conformer_rmsd=")
+    if clusters.metric == "shape" and shape is None:
+        raise ValueError("clusters=PoseClusters(metric='shape') needs shape=")
     if clusters.by == "confidence" and confidence is None:
         raise ValueError("clusters=PoseClusters(by='confidence') needs confidence=")
     if clusters.by == "vina" and vina is None:
@@ -203,6 +207,8 @@ def cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=None, li
             D = pairwise_ligand_rmsd(aligned, ligand_idx, symmetry=ligand_symmetry)[0]
     elif clusters.metric == "conformer":
         D = out["conformer_rmsd"]["pairwise"]          # the modes by internal conformation instead of by placement
+    elif clusters.metric == "shape":
+        D = 1.0 - out["shape"]["pairwise"]["shape_tanimoto"]   # poses that fill the same volume (unit diagonal: zero distance)
     else:
         D = 1.0 - interactions.pairwise(out["interactions"]["bits"])
     scores = out["vina"]["score"] if "vina" in out else None       # mean_score of a mode, whatever order is walked

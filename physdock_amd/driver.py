@@ -284,7 +284,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None) -> dict:
+           conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -364,11 +364,20 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `conformers=`), `nearest_template` / `nearest_template_rmsd` [n] (the pool conformer each pose is closest to) and `pool_to_gt` (a
     scalar tensor: the best-fit RMSD of the closest pool conformer to `x_gt`, the pool's coverage).  `clusters=PoseClusters(
     metric="conformer")` clusters `pairwise` and needs it; with `sdf=` the records gain the item `conformer_rmsd` (`to_gt`).  A spec over
-    another number of ligand atoms raises ValueError before anything is sampled.  Nothing else changes."""
+    another number of ligand atoms raises ValueError before anything is sampled.  Nothing else changes.
+    `shape` (a `shape.ShapeOverlap` of the ligand, or `(ShapeOverlap, (other_spec, y_ref))` to compare with another molecule's
+    structure y_ref [A',3] in the ground truth's frame; the default reference is the ligand of `x_gt` with the same spec): the result
+    gains `shape` = `shape_tanimoto`, `color_tanimoto`, `combo` [n] of the returned `poses` to the reference (Gaussian shape and feature
+    overlap, in place) and `pairwise` (`ShapeOverlap.pairwise` of them), and `order_shape` = the pose ids by descending combo
+    (`rank_by_score` of its negative; valid poses first with `validity=`).  `clusters=PoseClusters(metric="shape")` clusters 1 -
+    `pairwise["shape_tanimoto"]` and needs it; with `sdf=` the records gain the items `shape_tanimoto` and `tanimoto_combo`.  A spec
+    over another number of atoms raises ValueError before anything is sampled.  Nothing else changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
+    from .shape import check_redock_shape, score_shape
     from .sdfio import check_redock_sdf, score_sdf
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                               conformer_rmsd=conformer_rmsd)
+                               conformer_rmsd=conformer_rmsd, shape=shape)
+    check_redock_shape(shape, batch)
     check_search(search, refine)
     check_hydrogens(hydrogens, batch)
     check_receptor_geometry(receptor_geometry, batch)
@@ -500,6 +509,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_searched(search, refine, aligned, validity, vina))
     if conformer_rmsd is not None:
         out.update(score_conformer_rmsd(conformer_rmsd, aligned, batch, ligand_idx, ref_mol_poses))
+    if shape is not None:
+        out.update(score_shape(shape, aligned, batch, ligand_idx, out))
     if clusters is not None:
         out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
     if sdf is not None:
@@ -541,7 +552,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `shape`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -634,12 +645,15 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None):
+                 conformer_rmsd=None, shape=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                                   conformer_rmsd=conformer_rmsd)
+                                   conformer_rmsd=conformer_rmsd, shape=shape)
+        from .shape import check_redock_shape
+        check_redock_shape(shape, batch)
+        self.shape = shape
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
         check_receptor_geometry(receptor_geometry, batch)
@@ -779,6 +793,9 @@ class _RedockState:
             out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
         if self.conformer_rmsd is not None:
             out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, self.batch, self.ligand_idx, self.ref_mol_poses))
+        if self.shape is not None:
+            from .shape import score_shape
+            out.update(score_shape(self.shape, aligned, self.batch, self.ligand_idx, out))
         if self.clusters is not None:
             from .clustering import cluster_kept_poses
             out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,

@@ -441,7 +441,8 @@ def redock_items(out) -> Dict[str, object]:
     `confidence=` `ranking_confidence`, with `vina=` `vina_score` (`vina["score"]`), with `validity=` `valid` (`validity["valid"]`),
     with the ground truth and `ranking` `ligand_rmsd` (`ranking["rmsd_all"]`) and, with `lddt_pli=`, `lddt_pli`
     (`ranking["lddt_pli_all"]`), with `clusters=` `cluster` (`clusters["labels"]`), with `conformer_rmsd=` and the ground truth
-    `conformer_rmsd` (`conformer_rmsd["to_gt"]`)"""
+    `conformer_rmsd` (`conformer_rmsd["to_gt"]`), with `shape=` `shape_tanimoto` and `tanimoto_combo` (`shape["shape_tanimoto"]`,
+    `shape["combo"]`)"""
     n = int(out["poses"].shape[0])
     items: Dict[str, object] = {"pose": torch.arange(n, dtype=torch.int32, device=out["poses"].device)}
     if "confidence" in out:
@@ -458,6 +459,9 @@ def redock_items(out) -> Dict[str, object]:
         items["cluster"] = out["clusters"]["labels"]
     if "to_gt" in out.get("conformer_rmsd", {}):
         items["conformer_rmsd"] = out["conformer_rmsd"]["to_gt"]
+    if "shape" in out:
+        items["shape_tanimoto"] = out["shape"]["shape_tanimoto"]
+        items["tanimoto_combo"] = out["shape"]["combo"]
     return items
 
 
