@@ -1108,6 +1108,45 @@ int pd_shape_overlay(const double* ws_a, long long ws_a_numel, const double* alp
                      double* transform, double* x_fit, float* scores, double* overlap, double* overlap_start, int* best_start, int* iterations,
                      int* evaluations, int* status, void* stream);
 
+/* ---- Torsion fingerprint and torsion-fingerprint deviation TFD (torsion.hip; additive exports of ABI 11) --------------
+ * The ligand's torsion angles per pose and the TFD between poses (after Schulz-Gasch, Schaerfer, Guba & Rarey 2012; the package's own
+ * definition: tests/torsion_ref.py and physdock_amd/torsions.py, which builds the tables).  Float64 from the fp32 coordinates, fixed
+ * order sums, an exact minimum over the table rows, no atomics: a value depends on its own structures and the tables alone and is
+ * bit-identical whatever the batch.  Tables (all on the DEVICE): quads int32 [Q][4], the Q distinct quadruples of ligand atoms
+ * 0 .. L-1 (the closure of the base quadruples under the symmetry table; a quadruple and its reverse are one); the fingerprint's T
+ * entries as qstart int32 [T+1] (entry t owns the base quadruples qstart[t] .. qstart[t+1]-1 of Nq), w double [T] (weights >= 0 with a
+ * positive sum) and inv_max_dev double [T] (1 / max_dev in 1 / degree); image uint16 [Nq][M], m fastest: the id in 0 .. Q-1 of base
+ * quadruple qb seen through table row m, image[qb][0] its own id.  The caller guarantees that every index lies inside its array; one
+ * that does not is never followed and counts as an angle that does not exist (NaN).
+ * pd_torsion_prepare   : x fp32 [n][A][3] gathered through lig_idx int32 [L] (NULL: atoms 0 .. L-1, needs A >= L) -> ws double [n][Q]
+ *                        (pd_torsion_workspace_numel(n, Q) = n Q), the IUPAC dihedral of each quadruple in degrees,
+ *                        atan2(|b2| b1.(b2 x b3), (b1 x b2).(b2 x b3)) 180 / pi; NaN when a coordinate is not finite or
+ *                        |b1 x b2|^2 <= 1e-12 |b1|^2 |b2|^2 (or the same on the other side).  angles_deg (nullable, float [n][Nq]; needs
+ *                        image): the angle of every base quadruple rounded once to fp32.
+ * pd_torsion_tfd       : rows ws_a [na][Q] against columns ws_b [nb][Q] as prepared.  dev_t = min(1, mean over the entry's quadruples
+ *                        of the circular distance of the row's angle at image[qb][0] and the column's at image[qb][m], times
+ *                        inv_max_dev[t]); TFD(m) = sum_t w_t dev_t / sum_t w_t, NaN when an angle it names is; D float [na][nb] = the
+ *                        float64 min over m rounded once (a NaN never wins; NaN when every m is NaN; exactly 0 when T = 0, where the
+ *                        workspaces and tables may be NULL), best_perm (nullable, int32 [na][nb]) the smallest m that attains it or -1.
+ *                        symmetric != 0 covers ws_b == ws_a (NULL or ws_a, nb == na): i < j is computed (row i fixed, row j permuted)
+ *                        and mirrored, the diagonal is an exact 0, or NaN for a structure one of whose own angles is NaN; best_perm
+ *                        must then be NULL.  One 256-thread block per (row, tile of TJ columns), the angles in LDS: TJ = 64 (M <= 4),
+ *                        16 (M <= 16), 4 (M <= 64) or 1, quartered until (TJ + 1) (Q | 1) doubles fit 65280 bytes (64 up to Q = 125,
+ *                        16 up to 479, 4 up to 1631, 1 up to 4079; for Q = 4080 .. 4096 TJ = 1 and the row stays in global memory).
+ * pd_torsion_deviation : rows ws_a [na][Q] against ONE prepared reference ws_ref [Q] at table row rows[i] (int32 [na]; NULL: row 0)
+ *                        -> dev float [na][T], the dev_t above: which bond is wrong.  NaN for an entry that names a NaN angle and for
+ *                        a row outside 0 .. M-1 (the -1 of best_perm).  T = 0 writes nothing.
+ * L <= 1024, T <= 1024, Q <= 4096, Nq <= 9216, M <= 65535, 65535 structures per side: else PD_ERR_UNSUPPORTED.  A NULL required
+ * pointer, a misaligned pointer, a size < 1 or a short workspace: PD_ERR_ARG.  A rejected call launches nothing.                    */
+int pd_torsion_workspace_numel(int n, int Q);
+int pd_torsion_prepare(const float* x, const int* lig_idx, const int* quads, const unsigned short* image, double* ws, long long ws_numel,
+                       float* angles_deg, int n, int A, int L, int Q, int Nq, int M, void* stream);
+int pd_torsion_tfd(const double* ws_a, const double* ws_b, const int* qstart, const double* w, const double* inv_max_dev,
+                   const unsigned short* image, float* D, int* best_perm, int na, int nb, int Q, int T, int Nq, int M, int symmetric,
+                   void* stream);
+int pd_torsion_deviation(const double* ws_a, const double* ws_ref, const int* rows, const int* qstart, const double* inv_max_dev,
+                         const unsigned short* image, float* dev, int na, int Q, int T, int Nq, int M, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

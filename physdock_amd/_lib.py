@@ -284,6 +284,10 @@ def _declare(L):
     sig("pd_shape_workspace_numel", i, i, i, restype=ll)                                     # ABI 11, additive (shape_overlap.hip)
     sig("pd_shape_prepare", p, p, p, p, p, p, d, p, ll, i, i, i, i, p)
     sig("pd_shape_overlap", p, ll, p, p, i, i, i, p, ll, p, p, i, i, i, d, i, p, p, p, p, p, p, p)
+    sig("pd_torsion_workspace_numel", i, i)                                                  # ABI 11, additive (torsion.hip)
+    sig("pd_torsion_prepare", p, p, p, p, p, ll, p, i, i, i, i, i, i, p)
+    sig("pd_torsion_tfd", p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p)
+    sig("pd_torsion_deviation", p, p, p, p, p, p, p, i, i, i, i, i, p)
     sig("pd_shape_overlay_workspace_numel", i, i, i, restype=ll)
     sig("pd_shape_overlay", p, ll, p, p, i, i, i, p, ll, p, p, i, i, i, d, i, d, d, p, ll, p, p, p, p, p, p, p, p, p, p)
 

@@ -33,12 +33,12 @@ from . import ops
 
 MAX_POSES = 8192                      # PD_POSE_CLUSTERS_MAX_POSES
 ORDERS = (None, "confidence", "vina", "vina_refined")
-METRICS = ("rmsd", "interactions", "conformer", "shape")
+METRICS = ("rmsd", "interactions", "conformer", "shape", "torsion")
 _PER_MODE = ("leader", "size", "radius", "medoid", "spread", "mean_score")
 
 
 class PoseClusters:
-    """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"` and `"shape"`), `by` - the order `redock` walks
+    """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"` and `"shape"`, a TFD in 0 .. 1 for `"torsion"`), `by` - the order `redock` walks
     the poses in (None: pose ids; "confidence", "vina", "vina_refined": the result's `order_confidence`, `order_vina`,
     `order_vina_refined`) - and `metric`.  `cluster` and `binding_modes` take their order from the caller."""
 
@@ -176,7 +176,7 @@ class PoseClusters:
 
 
 def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None, conformer_rmsd=None,
-                               shape=None) -> None:
+                               shape=None, torsions=None) -> None:
     """redock(clusters=): raise ValueError for what the spec needs and the call lacks - before any sampling"""
     if clusters is None:
         return
@@ -188,6 +188,8 @@ def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=N
         raise ValueError("clusters=PoseClusters(metric='conformer') needs conformer_rmsd=")
     if clusters.metric == "shape" and shape is None:
         raise ValueError("clusters=PoseClusters(metric='shape') needs shape=")
+    if clusters.metric == "torsion" and torsions is None:
+        raise ValueError("clusters=PoseClusters(metric='torsion') needs torsions=")
     if clusters.by == "confidence" and confidence is None:
         raise ValueError("clusters=PoseClusters(by='confidence') needs confidence=")
     if clusters.by == "vina" and vina is None:
@@ -207,6 +209,8 @@ def cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=None, li
             D = pairwise_ligand_rmsd(aligned, ligand_idx, symmetry=ligand_symmetry)[0]
     elif clusters.metric == "conformer":
         D = out["conformer_rmsd"]["pairwise"]          # the modes by internal conformation instead of by placement
+    elif clusters.metric == "torsion":
+        D = out["torsions"]["pairwise"]                # the modes by torsion angles: the cutoff is a TFD in 0 .. 1
     elif clusters.metric == "shape":
         D = 1.0 - out["shape"]["pairwise"]["shape_tanimoto"]   # poses that fill the same volume (unit diagonal: zero distance)
     else:

@@ -198,15 +198,6 @@ __global__ __launch_bounds__(256) void bestfit_prepare_kernel(const float* __res
     }
 }
 
-struct bf_key { u64 v; unsigned m; };       // (bits of a non-negative double, table row): ordered as the pair is
-__device__ __forceinline__ bf_key bf_key_min(bf_key a, bf_key b) { return (a.v < b.v || (a.v == b.v && a.m <= b.m)) ? a : b; }
-__device__ __forceinline__ bf_key bf_key_xor(bf_key k, int o) {
-    bf_key r;
-    r.v = ((u64)__shfl_xor((unsigned)(k.v >> 32), o) << 32) | __shfl_xor((unsigned)k.v, o);
-    r.m = __shfl_xor(k.m, o);
-    return r;
-}
-
 __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restrict__ ws, const unsigned short* __restrict__ perms_t,
                                                           float* __restrict__ D, int* __restrict__ best_perm, double* __restrict__ quat,
                                                           int na, int nb, int L, int M, int TJ, int symmetric) {
@@ -238,7 +229,7 @@ __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restr
         Gsum = row[n3] + c[n3];
         finite = row[n3 + 1] != 0.0 && c[n3 + 1] != 0.0;
     }
-    bf_key best = {~0ull, 0xffffffffu};
+    pd_dkey best = {~0ull, 0xffffffffu};
     if (finite) {
         for (int m = g; m < M; m += G) {
             double S[9];
@@ -246,17 +237,17 @@ __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restr
             const double lam = bf_lambda_max<false>(S, nullptr);
             double msd = (Gsum - 2.0 * lam) / (double)L;
             if (!(msd > 0.0)) msd = 0.0;
-            bf_key k = {(u64)__double_as_longlong(msd), (unsigned)m};
-            best = bf_key_min(best, k);
+            pd_dkey k = {(u64)__double_as_longlong(msd), (unsigned)m};
+            best = pd_dkey_min(best, k);
         }
     }
-    for (int o = (G < 64 ? G : 64) >> 1; o > 0; o >>= 1) best = bf_key_min(best, bf_key_xor(best, o));
+    for (int o = (G < 64 ? G : 64) >> 1; o > 0; o >>= 1) best = pd_dkey_min(best, pd_dkey_xor(best, o));
     if (G == 256) {
         if ((tid & 63) == 0) { red_v[tid >> 6] = best.v; red_m[tid >> 6] = best.m; }
         __syncthreads();
         best.v = red_v[0]; best.m = red_m[0];
 #pragma unroll
-        for (int w = 1; w < 4; ++w) { bf_key k = {red_v[w], red_m[w]}; best = bf_key_min(best, k); }
+        for (int w = 1; w < 4; ++w) { pd_dkey k = {red_v[w], red_m[w]}; best = pd_dkey_min(best, k); }
     }
     if (g != 0 || j >= nb) return;
     if (symmetric && j <= i) {
@@ -287,8 +278,6 @@ __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restr
     }
 }
 
-inline bool bf_misaligned(const void* p, size_t a) { return p && ((size_t)p % a) != 0; }
-
 }  // namespace
 
 PD_EXPORT int pd_bestfit_rmsd_workspace_numel(int na, int nb, int L) {
@@ -307,8 +296,8 @@ PD_EXPORT int pd_bestfit_rmsd(const float* xa, const int* idx_a, const float* xb
         return PD_ERR_ARG;
     }
     if (!idx_a && Aa < L) return PD_ERR_ARG;
-    if (bf_misaligned(xa, 4) || bf_misaligned(xb, 4) || bf_misaligned(idx_a, 4) || bf_misaligned(idx_b, 4) || bf_misaligned(perms_t, 2) ||
-        bf_misaligned(ws, 8) || bf_misaligned(D, 4) || bf_misaligned(best_perm, 4) || bf_misaligned(quat, 8))
+    if (pd_misaligned(xa, 4) || pd_misaligned(xb, 4) || pd_misaligned(idx_a, 4) || pd_misaligned(idx_b, 4) || pd_misaligned(perms_t, 2) ||
+        pd_misaligned(ws, 8) || pd_misaligned(D, 4) || pd_misaligned(best_perm, 4) || pd_misaligned(quat, 8))
         return PD_ERR_ARG;
     if (L > BF_MAX_L || M > BF_MAX_M || na > BF_MAX_N || nb > BF_MAX_N) return PD_ERR_UNSUPPORTED;
     if (ws_numel < ((long long)na + nb) * bf_ws_stride(L)) return PD_ERR_ARG;

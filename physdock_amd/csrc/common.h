@@ -149,3 +149,17 @@ __device__ __forceinline__ pd_u64 pd_wave_key_min(pd_u64 k) {
     }
     return k;
 }
+
+// The same for a NON-NEGATIVE double and a table row, which no longer fit one word: compared as the pair is, the smaller row wins a tie;
+// v = ~0 holds no value (bestfit_rmsd.hip, torsion.hip).  pd_dkey_xor: the key of lane ^ o.
+struct pd_dkey { pd_u64 v; unsigned m; };
+__device__ __forceinline__ pd_dkey pd_dkey_min(pd_dkey a, pd_dkey b) { return (a.v < b.v || (a.v == b.v && a.m <= b.m)) ? a : b; }
+__device__ __forceinline__ pd_dkey pd_dkey_xor(pd_dkey k, int o) {
+    pd_dkey r;
+    r.v = ((pd_u64)__shfl_xor((unsigned)(k.v >> 32), o) << 32) | __shfl_xor((unsigned)k.v, o);
+    r.m = __shfl_xor(k.m, o);
+    return r;
+}
+
+// host side of an entry point: is the non-NULL pointer p off its alignment a?
+static inline bool pd_misaligned(const void* p, size_t a) { return p && ((size_t)p % a) != 0; }

@@ -284,7 +284,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            sampler_kwargs: Optional[dict] = None, infer_meta_data=None, reuse_conditioning: bool = True, confidence=None,
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
-           conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None) -> dict:
+           conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
+           torsions=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -371,13 +372,21 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     overlap, in place) and `pairwise` (`ShapeOverlap.pairwise` of them), and `order_shape` = the pose ids by descending combo
     (`rank_by_score` of its negative; valid poses first with `validity=`).  `clusters=PoseClusters(metric="shape")` clusters 1 -
     `pairwise["shape_tanimoto"]` and needs it; with `sdf=` the records gain the items `shape_tanimoto` and `tanimoto_combo`.  A spec
-    over another number of atoms raises ValueError before anything is sampled.  Nothing else changes."""
+    over another number of atoms raises ValueError before anything is sampled.  Nothing else changes.
+    `torsions` (a `torsions.TorsionFingerprint` of the ligand): the result gains `torsions` = `pairwise` (the torsion-fingerprint deviation
+    TFD of every two returned `poses`, in 0 .. 1), `to_gt` [n] and `deviation` [n,T] (each pose's TFD to `x_gt` and the normalised
+    deviation of every entry of the fingerprint: which bond is wrong) and, with a template pool in use, `nearest_template` /
+    `nearest_template_tfd` [n].  `clusters=PoseClusters(metric="torsion")` clusters `pairwise` and needs it; with `sdf=` the records gain
+    the item `tfd` (`to_gt`).  A spec over another number of ligand atoms raises ValueError before anything is sampled.  Nothing else
+    changes."""
     from .clustering import check_redock_prerequisites, cluster_kept_poses
     from .shape import check_redock_shape, score_shape
+    from .torsions import check_redock_torsions, score_torsions
     from .sdfio import check_redock_sdf, score_sdf
     check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                               conformer_rmsd=conformer_rmsd, shape=shape)
+                               conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions)
     check_redock_shape(shape, batch)
+    check_redock_torsions(torsions, batch)
     check_search(search, refine)
     check_hydrogens(hydrogens, batch)
     check_receptor_geometry(receptor_geometry, batch)
@@ -511,6 +520,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         out.update(score_conformer_rmsd(conformer_rmsd, aligned, batch, ligand_idx, ref_mol_poses))
     if shape is not None:
         out.update(score_shape(shape, aligned, batch, ligand_idx, out))
+    if torsions is not None:
+        out.update(score_torsions(torsions, aligned, batch, ligand_idx, ref_mol_poses))
     if clusters is not None:
         out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
     if sdf is not None:
@@ -552,7 +563,7 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `shape`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
+    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `shape`, `torsions`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
     keyword arguments of `redock` shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
@@ -645,15 +656,18 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None):
+                 conformer_rmsd=None, shape=None, torsions=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
         #  the group's - _redock_group passes them to the sampler)
         from .clustering import check_redock_prerequisites
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                                   conformer_rmsd=conformer_rmsd, shape=shape)
+                                   conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions)
         from .shape import check_redock_shape
         check_redock_shape(shape, batch)
         self.shape = shape
+        from .torsions import check_redock_torsions
+        check_redock_torsions(torsions, batch)
+        self.torsions = torsions
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
         check_receptor_geometry(receptor_geometry, batch)
@@ -796,6 +810,9 @@ class _RedockState:
         if self.shape is not None:
             from .shape import score_shape
             out.update(score_shape(self.shape, aligned, self.batch, self.ligand_idx, out))
+        if self.torsions is not None:
+            from .torsions import score_torsions
+            out.update(score_torsions(self.torsions, aligned, self.batch, self.ligand_idx, self.ref_mol_poses))
         if self.clusters is not None:
             from .clustering import cluster_kept_poses
             out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,
