@@ -26,29 +26,15 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _ligand_sides as sides
 from . import ops
+from ._ligand_sides import MAX_STRUCTURES
 
 __all__ = ["BestFitRmsd", "MAX_ATOMS", "MAX_STRUCTURES", "quat_apply"]
 
 #: limits of the kernel (csrc/bestfit_rmsd.hip)
 MAX_ATOMS = 1024
-MAX_STRUCTURES = 65535
-
-
-def _host_idx(idx, what):
-    """an index list as a host int64 array [L], or None"""
-    if idx is None:
-        return None
-    if isinstance(idx, torch.Tensor):
-        if idx.dtype.is_floating_point or idx.dtype == torch.bool:
-            raise ValueError(f"BestFitRmsd: {what} must hold integer atom indices, got {idx.dtype}")
-        idx = idx.detach().cpu().numpy()
-    a = np.asarray(idx)
-    if a.dtype.kind not in "iu" or a.ndim != 1 or a.shape[0] < 1:
-        raise ValueError(f"BestFitRmsd: {what} must be a non-empty 1-D list of integer atom indices")
-    if int(a.min()) < 0:
-        raise ValueError(f"BestFitRmsd: {what} holds a negative index")
-    return a.astype(np.int64)
+_WHO = dict(name="BestFitRmsd", takes="the kernel takes", max_atoms=MAX_ATOMS)      # for the messages and checks of _ligand_sides
 
 
 def quat_apply(quat: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
@@ -70,7 +56,7 @@ class BestFitRmsd:
     __slots__ = ("ligand_idx", "symmetry", "n_atoms", "_idx")
 
     def __init__(self, ligand_idx=None, symmetry=None):
-        idx = _host_idx(ligand_idx, "ligand_idx")
+        idx = sides.host_idx(ligand_idx, "ligand_idx", "BestFitRmsd")
         if symmetry is not None and not (hasattr(symmetry, "table") and hasattr(symmetry, "n_atoms")):
             raise ValueError(f"BestFitRmsd: symmetry= takes a symmetry.LigandSymmetry, got {type(symmetry).__name__}")
         n = None if idx is None else int(idx.shape[0])
@@ -94,13 +80,9 @@ class BestFitRmsd:
     @property
     def symmetry_complete(self) -> bool:
         """False: the table was cut, every value is an upper bound"""
-        return True if self.symmetry is None else bool(self.symmetry.complete)
-
+        return sides.symmetry_complete(self.symmetry)
 
     # ------------------------------------------------------------------ plumbing
-    def _own_idx(self):
-        return None if self.ligand_idx is None else np.asarray(self.ligand_idx, dtype=np.int64)
-
     def _device_idx(self, idx, device):
         if idx is None:
             return None
@@ -130,12 +112,7 @@ class BestFitRmsd:
         return D, bp, q
 
     def _cross(self, x, targets, target_idx, detail):
-        ia = self._own_idx()
-        xa, L = _structures(x, "x", ia, self.n_atoms)
-        ib = _host_idx(target_idx, "target_idx")
-        if ib is None and ia is not None and isinstance(targets, torch.Tensor) and targets.dim() == 3 and targets.shape[1] != L:
-            ib = ia                                           # whole poses as targets: the ligand sits where it sits in x
-        xb, _ = _structures(targets, "targets", ib, L, device=xa.device)
+        xa, ia, xb, ib, L = sides.sides(self, x, targets, target_idx, **_WHO)
         D, bp, q = self._launch(xa, ia, xb, ib, L, False, detail)
         return D, bp, q, ia, ib, L
 
@@ -147,11 +124,8 @@ class BestFitRmsd:
         `detail=True` also `best_perm` int32 [n,C] and `quat` float64 [n,C,4] (R(quat) pose ~ target o perm).  The rows are fixed, the
         targets permuted.  Nothing is read back."""
         D, bp, q, _, _, _ = self._cross(x, targets, target_idx, detail)
-        key = torch.where(torch.isnan(D), torch.full_like(D, float("inf")), D)
-        near = torch.argmin(key, dim=1)
-        first = (key == key.gather(1, near[:, None])).to(torch.int8).argmax(1)      # the first of equal minima, whatever argmin picked
-        near_r = D.gather(1, first[:, None])[:, 0]
-        out = {"D": D, "nearest": torch.where(torch.isnan(near_r), torch.full_like(first, -1), first), "nearest_rmsd": near_r}
+        near, near_r = sides.nearest(D)
+        out = {"D": D, "nearest": near, "nearest_rmsd": near_r}
         if detail:
             out.update(best_perm=bp, quat=q)
         return out
@@ -172,28 +146,7 @@ class BestFitRmsd:
     def pairwise(self, x: torch.Tensor) -> torch.Tensor:
         """x [n,A,3] -> D fp32 [n,n], symmetric with an exact zero diagonal (pose i fixed, pose j permuted for i < j, mirrored);
         `PoseClusters.cluster` takes it as it is"""
-        ia = self._own_idx()
-        xa, L = _structures(x, "x", ia, self.n_atoms)
+        ia = sides.own_idx(self)
+        xa, L = sides.structures(x, "x", ia, self.n_atoms, **_WHO)
         return self._launch(xa, ia, None, None, L, True, False)[0]
 
-
-def _structures(x, what, idx, L, device=None):
-    """x [n,A,3] -> (fp32 contiguous device tensor, L) after the host checks: idx (host int64 or None: the structure is the ligand
-    itself) stays inside the A atoms and names L of them (L None: whatever it names)"""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
-        raise ValueError(f"BestFitRmsd: {what} must be a floating-point tensor [n,A,3], got {tuple(getattr(x, 'shape', ()))}")
-    n, A = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= n <= MAX_STRUCTURES:
-        raise ValueError(f"BestFitRmsd: {n} structures in {what}; the kernel takes 1 .. {MAX_STRUCTURES}")
-    have = A if idx is None else int(idx.shape[0])
-    if L is not None and have != L:
-        raise ValueError(f"BestFitRmsd: {what} names {have} ligand atoms, expected {L}")
-    if idx is not None and int(idx.max()) >= A:
-        raise ValueError(f"BestFitRmsd: an index of {what} ({int(idx.max())}) leaves its {A} atoms")
-    if not 1 <= have <= MAX_ATOMS:
-        raise ValueError(f"BestFitRmsd: {have} ligand atoms; the kernel takes 1 .. {MAX_ATOMS}")
-    if device is not None and not x.is_cuda:
-        x = x.to(device)                                      # targets may come from the host, as redock's template pool may
-    if not x.is_cuda or (device is not None and x.device != device):
-        raise ValueError(f"BestFitRmsd: {what} must be on the GPU{'' if device is None else ' of the poses'}, got a tensor on {x.device}")
-    return x.float().contiguous(), have

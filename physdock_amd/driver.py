@@ -30,7 +30,13 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from . import ops
+from .clustering import check_redock_prerequisites, cluster_kept_poses
 from .model import weighted_rigid_align
+from .pdbio import PdbTemplate
+from .ranking import rank_poses
+from .sdfio import check_redock_sdf, score_sdf
+from .shape import check_redock_shape, score_shape
+from .torsions import check_redock_torsions, score_torsions
 
 
 def ligand_atom_mask(batch: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -379,158 +385,41 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `nearest_template_tfd` [n].  `clusters=PoseClusters(metric="torsion")` clusters `pairwise` and needs it; with `sdf=` the records gain
     the item `tfd` (`to_gt`).  A spec over another number of ligand atoms raises ValueError before anything is sampled.  Nothing else
     changes."""
-    from .clustering import check_redock_prerequisites, cluster_kept_poses
-    from .shape import check_redock_shape, score_shape
-    from .torsions import check_redock_torsions, score_torsions
-    from .sdfio import check_redock_sdf, score_sdf
-    check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                               conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions)
-    check_redock_shape(shape, batch)
-    check_redock_torsions(torsions, batch)
-    check_search(search, refine)
-    check_hydrogens(hydrogens, batch)
-    check_receptor_geometry(receptor_geometry, batch)
-    check_conformer_rmsd(conformer_rmsd, batch)
-    check_redock_sdf(sdf, batch, hydrogens)
+    keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
+    st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
-    pool_log = None
-    if physics_correction and ref_mol_poses is None and conformers is not None:
-        ref_mol_poses, pool_log = conformer_pool(conformers, batch, seed)
-    if physics_correction and ref_mol_poses is None:
-        raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
-                         "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
-    batch = dict(batch)
-    if ref_mol_poses is not None:            # the reference accepts host conformers (`.to(device)`, model.py:185)
-        ref_mol_poses = ref_mol_poses.to(batch["x_gt"].device)
-    is_lig = ligand_atom_mask(batch)
-    ligand_idx = torch.nonzero(is_lig).flatten().to(torch.int32)
-    accept: List[torch.Tensor] = []
-    reject: deque = deque([], maxlen=max_samples)
-    ligand_templates: List[torch.Tensor] = []
-    reference_templates: List[torch.Tensor] = []
-    factor = float(mmff_gamma_0_factor_start)
-    log = []
-    kw = dict(sampler_kwargs or {})
-    n_mol = _mol_num_atoms(ref_mol) if ref_mol is not None else None
-    ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(is_lig.sum()))     # redocking.py:195-196
     reuse = bool(reuse_conditioning and getattr(model, "supports_conditioning_reuse", False))
-    cond = None
-    conf_sz = None                           # confidence=: (s, z) of the most recent sampler call
     for rnd in range(max_rounds):
-        if rnd > 0 and not physics_correction:
+        if not st.begin_round(rnd):
             break
-        if rnd >= 1 and "batch_msa_feat" in batch:
-            if rnd >= batch["batch_msa_feat"].shape[0]:
-                raise ValueError(f"batch_msa_feat holds {batch['batch_msa_feat'].shape[0]} re-sampled MSAs, round {rnd} needs "
-                                 "its own (the reference loads num_recycles = max_rounds of them, redocking.py:83)")
-            batch["msa_feat"] = batch["batch_msa_feat"][rnd]
-            cond = None                      # a re-sampled MSA: this round's trunk is its own
-        templates = torch.stack(ligand_templates + reference_templates, 0) if rnd > 0 else None
-        call = dict(num_sample=num_samples_per_round, steps=steps, mmff_gamma_0_factor=factor, align_ref_pos=rnd > 0,
-                    ref_mol=None if ref_mol_num_error else ref_mol, ref_mol_poses=templates,
-                    use_ref_mol_poses=rnd != 0 and physics_correction,
-                    ode_step_scale_eta=1.5 if ref_mol_num_error else 1.0,
-                    karras_noise_schedule_power=karras_noise_schedule_power)
+        call = dict(num_sample=num_samples_per_round, steps=steps, mmff_gamma_0_factor=st.factor, align_ref_pos=rnd > 0,
+                    ref_mol=st.sampler_ref_mol, ref_mol_poses=st.templates, use_ref_mol_poses=rnd != 0 and physics_correction,
+                    ode_step_scale_eta=st.eta, karras_noise_schedule_power=karras_noise_schedule_power)
         if seed is not None:
             call.update(seed=seed + rnd)
-        call.update(kw)
+        call.update(st.kw)
         if reuse and "conditioning" not in call and "return_conditioning" not in call:
-            if cond is not None:
-                call.update(conditioning=cond)
-            elif physics_correction and rnd + 1 < max_rounds and "batch_msa_feat" not in batch:
+            if st.cond is not None:
+                call.update(conditioning=st.cond)
+            elif st.later_round_shares_conditioning(rnd):
                 call.update(return_conditioning=True)
         want_sz = confidence is not None and call.get("conditioning") is None and not call.get("return_conditioning")
         if want_sz:
             call.update(return_conditioning=True)
         with torch.no_grad():
-            x_pred = model.sample_diffusion(batch, **call)
+            x_pred = model.sample_diffusion(st.batch, **call)
+        got = None
         if isinstance(x_pred, tuple):
             x_pred, got = x_pred
             if confidence is not None:
-                conf_sz = got[2:]
-            if not want_sz:
-                cond = got
+                st.conf_sz = got[2:]
+            if want_sz:
+                got = None                   # asked for the confidence head alone: not kept for later rounds
         elif confidence is not None and call.get("conditioning") is not None:
-            conf_sz = call["conditioning"][2:]
-        if rnd + 1 >= max_rounds:            # no later round can take it: the shared conditioning (clones of a [A,c], ap [A,A,c], s,
-            cond = None                      # z [T,T,128] - hundreds of MB at large crops, per StreamPool replica) is released here
-        # accept / reject (redocking.py:303-317): on the device when a ChiralityReference is given (one kernel, one [B]
-        # mask to the host), else through the injected per-pose callable (which needs the poses on the host)
-        dev_ok, n_invalid = _device_accept(x_pred, chirality, validity if validity_filter else None) if physics_correction else (None, None)
-        x_cpu = x_pred.cpu() if (physics_correction and accept_fn is not None) else x_pred
-        flags = []
-        for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
-            ok = True
-            if dev_ok is not None:
-                ok = bool(dev_ok[b])
-            if ok and physics_correction and accept_fn is not None:
-                ok = bool(accept_fn(xc))
-            flags.append(ok)
-            if ok:
-                ligand_templates.append(x[is_lig])
-                accept.append(x)
-            else:
-                reject.append(x)
-        log.append({"round": rnd, "gamma_factor": factor, "accepted": int(sum(flags)), "sampled": len(flags),
-                    "templates": 0 if templates is None else int(templates.shape[0])})
-        if n_invalid is not None:
-            log[-1]["invalid"] = n_invalid
-        if physics_correction:
-            factor = next_gamma_factor(factor, any(flags))
-            if len(accept) >= max_samples:
-                cond = None                  # accept count reached: the shared conditioning is released with the loop
-                break
-            used = select_reference_templates(x_pred, ligand_idx, ref_mol_poses, max_samples - len(ligand_templates))
-            reference_templates = [ref_mol_poses[i] for i in used.tolist()]
-    n_accepted = len(accept)
-    if len(accept) < num_samples_per_round:
-        accept = accept + list(reject)
-    poses = torch.stack(accept[:max_samples], 0)
-    w = align_weights if align_weights is not None else pocket_align_weights(batch, use_pocket)
-    x_gt = batch["x_gt"].float()
-    aligned = weighted_rigid_align(x_gt[None].expand(poses.shape[0], -1, -1).contiguous(), poses, w)
-    out = {"poses": aligned, "accepted": n_accepted, "rounds": log, "gamma_factor": factor, "ranking": None}
-    if ranking:
-        from .ranking import rank_poses
-        out["ranking"] = rank_poses(poses, x_gt, w, is_lig, symmetry=ligand_symmetry, lddt_pli=lddt_pli)
-    if confidence is not None:
-        out.update(score_kept_poses(confidence, batch, conf_sz, aligned))
-    if validity is not None:
-        out.update(score_validity(validity, aligned, out))
-    if vina is not None:
-        out.update(score_vina(vina, aligned, out))
-    if interactions is not None:
-        out.update(score_interactions(interactions, aligned, batch))
-    if ring_interactions is not None:
-        out.update(score_ring_interactions(ring_interactions, aligned, batch))
-    if hydrogens is not None:
-        out.update(score_hydrogens(hydrogens, aligned, batch))
-    if receptor_geometry is not None:
-        out.update(score_receptor_geometry(receptor_geometry, aligned, batch, out))
-    if pool_log is not None:
-        out["conformers"] = pool_log
-    if surface is not None:
-        out.update(score_surface(surface, aligned, batch))
-    if refine is not None:
-        out.update(score_refined(refine, aligned, validity, vina))
-    if search:
-        out.update(score_searched(search, refine, aligned, validity, vina))
-    if conformer_rmsd is not None:
-        out.update(score_conformer_rmsd(conformer_rmsd, aligned, batch, ligand_idx, ref_mol_poses))
-    if shape is not None:
-        out.update(score_shape(shape, aligned, batch, ligand_idx, out))
-    if torsions is not None:
-        out.update(score_torsions(torsions, aligned, batch, ligand_idx, ref_mol_poses))
-    if clusters is not None:
-        out.update(cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=interactions, ligand_symmetry=ligand_symmetry))
-    if sdf is not None:
-        out.update(score_sdf(sdf, aligned, out))
-    if infer_meta_data is not None:
-        from .pdbio import PdbTemplate
-        out["pdb_blocks"] = PdbTemplate(infer_meta_data).blocks(aligned)
-        out["receptor_pdb_blocks"] = PdbTemplate(infer_meta_data, receptor_only=True).blocks(aligned)
-    return out
+            st.conf_sz = call["conditioning"][2:]
+        st.consume(rnd, x_pred, got)
+    return st.result()
 
 
 def conditioning_s_z(sz, T: int):
@@ -563,8 +452,8 @@ def score_kept_poses(confidence, batch, sz, poses) -> dict:
 def redock_many(model, systems, *, streams: Optional[int] = None, group: Optional[int] = None, **common) -> List[dict]:
     """The loop over systems of the reference's drivers (`redocking.py:128-154`: one `redocking(...)` call per input system;
     `screening.py:100-116`: one receptor x many ligands) on ONE GPU.  `systems`: an iterable of feature dicts, or of
-    `(batch, per_system_kwargs)` pairs (`ref_mol`, `ref_mol_poses`, `chirality`, `ligand_symmetry`, `validity`, `lddt_pli`, `vina`, `interactions`, `ring_interactions`, `hydrogens`, `receptor_geometry`, `conformer_rmsd`, `shape`, `torsions`, `conformers`, `sdf`, `surface`, `refine`, `search`, `clusters`, `infer_meta_data` ... differ per system); `common`:
-    keyword arguments of `redock` shared by all.  Results in input order.
+    `(batch, per_system_kwargs)` pairs (any keyword of `redock`: what differs per system); `common`: keyword arguments of `redock`
+    shared by all.  Results in input order.
 
     Rounds of few samples cannot fill an MI355X (20 samples per round, the drivers' setting: 70 % of the per-pose rate of a 64-sample
     call), and the systems are independent, so by default two of them are in flight on two HIP streams whenever a round has fewer
@@ -648,7 +537,9 @@ def _needs_host_relax(model, batch, ref_mol, kw) -> bool:
 
 
 class _RedockState:
-    """one system's state in redock_many's lockstep round loop: redock's per-system bookkeeping, round by round"""
+    """one system's redocking run, round by round: the per-system rules of `redock` and of redock_many's lockstep round loop - their
+    callers build the sampler call, sample, and hand the poses to `consume`.  `pbatch`: the system's prepared batch, padded to its
+    group (`PhysDock._pad_to_group`); None for a single system, which samples from `batch`."""
 
     def __init__(self, batch, pbatch, *, ref_mol=None, ref_mol_poses=None, accept_fn=None, chirality=None, physics_correction=False,
                  max_samples=5, max_rounds=10, num_samples_per_round=5, mmff_gamma_0_factor_start=6.0, use_pocket=True,
@@ -657,32 +548,26 @@ class _RedockState:
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
                  conformer_rmsd=None, shape=None, torsions=None):
-        # (the keywords of redock, no others: a misspelt one raises TypeError as it does there; steps and the schedule power are
-        #  the group's - _redock_group passes them to the sampler)
-        from .clustering import check_redock_prerequisites
+        # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
+        #  power go to the sampler from the caller)
+        vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
                                    conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions)
-        from .shape import check_redock_shape
         check_redock_shape(shape, batch)
-        self.shape = shape
-        from .torsions import check_redock_torsions
         check_redock_torsions(torsions, batch)
-        self.torsions = torsions
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
         check_receptor_geometry(receptor_geometry, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
-        self.conformer_rmsd = conformer_rmsd
-        from .sdfio import check_redock_sdf
         check_redock_sdf(sdf, batch, hydrogens)
-        self.sdf = sdf
         self.pool_log = None
         if physics_correction and ref_mol_poses is None and conformers is not None:
             ref_mol_poses, self.pool_log = conformer_pool(conformers, batch, seed)
         if physics_correction and ref_mol_poses is None:
             raise ValueError("physics correction needs reference conformers (ref_mol_poses [C,L,3]); the reference generates "
                              "them with RDKit ETKDG (redocking.py:231-243), which this build does not include")
-        self.batch, self.pbatch = dict(batch), dict(pbatch)
+        self.batch, self.pbatch = dict(batch), None if pbatch is None else dict(pbatch)
+        # (the reference accepts host conformers: `.to(device)`, model.py:185)
         self.ref_mol_poses = ref_mol_poses.to(batch["x_gt"].device) if ref_mol_poses is not None else None
         self.is_lig = ligand_atom_mask(batch)
         self.ligand_idx = torch.nonzero(self.is_lig).flatten().to(torch.int32)
@@ -692,61 +577,53 @@ class _RedockState:
         self.log = []
         self.kw = dict(sampler_kwargs or {})
         n_mol = _mol_num_atoms(ref_mol) if ref_mol is not None else None
-        self.ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(self.is_lig.sum()))
-        self.ref_mol, self.accept_fn, self.chirality, self.pc = ref_mol, accept_fn, chirality, physics_correction
-        self.max_samples, self.max_rounds, self.nspr = max_samples, max_rounds, num_samples_per_round
-        self.use_pocket, self.align_weights, self.ranking, self.seed = use_pocket, align_weights, ranking, seed
-        self.infer_meta_data, self.reuse = infer_meta_data, reuse_conditioning
-        self.cond, self.done, self.templates = None, False, None
-        self.confidence, self.conf_sz = confidence, None
-        self.ligand_symmetry = ligand_symmetry
-        self.validity, self.validity_filter = validity, bool(validity_filter)
-        self.lddt_pli = lddt_pli
-        self.vina = vina
-        self.interactions = interactions
-        self.ring_interactions = ring_interactions
-        self.hydrogens = hydrogens
-        self.receptor_geometry = receptor_geometry
-        self.surface = surface
-        self.refine = refine
-        self.search = search
-        self.clusters = clusters
+        ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(self.is_lig.sum()))     # redocking.py:195-196
+        self.sampler_ref_mol, self.eta = (None, 1.5) if ref_mol_num_error else (ref_mol, 1.0)      # ... :292,296
+        self.cond = None                     # the conditioning that rounds with the same features share
+        self.conf_sz = None                  # confidence=: (s, z) of the most recent sampler call, set by the caller
+        self.done, self.templates = False, None
 
-    def round_args(self, rnd):
-        """this round's per-system arguments of sample_diffusion_many (redock's `call`), or None when the system is done"""
-        if self.done or (rnd > 0 and not self.pc):
+    def begin_round(self, rnd) -> bool:
+        """does round `rnd` run?  If so, its MSA is in place (`batch`, and `pbatch` at the group's token count) and `templates` is
+        its template stack"""
+        if self.done or (rnd > 0 and not self.physics_correction):
             self.done = True
-            return None
+            return False
         if rnd >= 1 and "batch_msa_feat" in self.batch:
             if rnd >= self.batch["batch_msa_feat"].shape[0]:
                 raise ValueError(f"batch_msa_feat holds {self.batch['batch_msa_feat'].shape[0]} re-sampled MSAs, round {rnd} needs "
                                  "its own (the reference loads num_recycles = max_rounds of them, redocking.py:83)")
             msa = self.batch["batch_msa_feat"][rnd]
             self.batch["msa_feat"] = msa
-            pt = self.pbatch["target_feat"].shape[0] - msa.shape[1]        # the group-padded token count
-            self.pbatch["msa_feat"] = torch.nn.functional.pad(msa.float(), (0, 0, 0, pt)).contiguous()
-            self.cond = None
+            if self.pbatch is not None:
+                pt = self.pbatch["target_feat"].shape[0] - msa.shape[1]        # the group-padded token count
+                self.pbatch["msa_feat"] = torch.nn.functional.pad(msa.float(), (0, 0, 0, pt)).contiguous()
+            self.cond = None                 # a re-sampled MSA: this round's trunk is its own
         self.templates = torch.stack(self.ligand_templates + self.reference_templates, 0) if rnd > 0 else None
-        want_cond = (self.reuse and self.cond is None and self.pc and rnd + 1 < self.max_rounds and "batch_msa_feat" not in self.batch)
-        return dict(factor=self.factor, ref_mol=None if self.ref_mol_num_error else self.ref_mol, ref_mol_poses=self.templates,
-                    eta=1.5 if self.ref_mol_num_error else 1.0, seed=self.kw.get("seed", (self.seed + rnd) if self.seed is not None else 0),
-                    sample_offset=self.kw.get("sample_offset", 0), noise=self.kw.get("noise"), cond=self.cond if self.reuse else None,
-                    want_cond=want_cond)
+        return True
+
+    def later_round_shares_conditioning(self, rnd) -> bool:
+        """can a round after `rnd` take this round's conditioning (there is one, and it sees the same features)?"""
+        return self.physics_correction and rnd + 1 < self.max_rounds and "batch_msa_feat" not in self.batch
 
     def consume(self, rnd, x_pred, cond):
-        """redock's accept / reject, adaptive factor and template pool for this round's poses"""
-        if cond is not None and self.reuse:
+        """this round's poses: accept / reject (redocking.py:303-317), the log entry, the adaptive factor and the template pool of the
+        next round; `cond`: the conditioning the sampler returned for later rounds, or None"""
+        if cond is not None and self.reuse_conditioning:
             self.cond = cond
-        if rnd + 1 >= self.max_rounds:
-            self.cond = None
-        dev_ok, n_invalid = _device_accept(x_pred, self.chirality, self.validity if self.validity_filter else None) if self.pc else (None, None)
-        x_cpu = x_pred.cpu() if (self.pc and self.accept_fn is not None) else x_pred
+        if rnd + 1 >= self.max_rounds:       # no later round can take it: the shared conditioning (clones of a [A,c], ap [A,A,c], s,
+            self.cond = None                 # z [T,T,128] - hundreds of MB at large crops, per StreamPool replica) is released here
+        # on the device when a ChiralityReference or a validity filter is given (one [*, B] mask to the host), and / or through the
+        # injected per-pose callable (which needs the poses on the host)
+        pc = self.physics_correction
+        dev_ok, n_invalid = _device_accept(x_pred, self.chirality, self.validity if self.validity_filter else None) if pc else (None, None)
+        x_cpu = x_pred.cpu() if (pc and self.accept_fn is not None) else x_pred
         flags = []
         for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
             ok = True
             if dev_ok is not None:
                 ok = bool(dev_ok[b])
-            if ok and self.pc and self.accept_fn is not None:
+            if ok and pc and self.accept_fn is not None:
                 ok = bool(self.accept_fn(xc))
             flags.append(ok)
             if ok:
@@ -758,10 +635,10 @@ class _RedockState:
                          "templates": 0 if self.templates is None else int(self.templates.shape[0])})
         if n_invalid is not None:
             self.log[-1]["invalid"] = n_invalid
-        if self.pc:
+        if pc:
             self.factor = next_gamma_factor(self.factor, any(flags))
             if len(self.accept) >= self.max_samples:
-                self.cond, self.done = None, True
+                self.cond, self.done = None, True        # accept count reached: the shared conditioning is released with the loop
                 return
             used = select_reference_templates(x_pred, self.ligand_idx, self.ref_mol_poses, self.max_samples - len(self.ligand_templates))
             self.reference_templates = [self.ref_mol_poses[i] for i in used.tolist()]
@@ -770,58 +647,54 @@ class _RedockState:
         if rnd + 1 >= self.max_rounds:
             self.done = True
 
-    def result(self):
-        """redock's top-up, alignment into the ground-truth frame, ranking and PDB text"""
+    def result(self) -> dict:
+        """top-up with rejected poses, alignment into the ground-truth frame, ranking, the pose scorers in their order (score_vina
+        reads out["validity"], cluster_kept_poses almost everything, score_sdf comes last) and the PDB text"""
         self.cond = None
+        batch, ligand_idx = self.batch, self.ligand_idx
         n_accepted = len(self.accept)
-        accept = self.accept + list(self.reject) if len(self.accept) < self.nspr else self.accept
+        accept = self.accept + list(self.reject) if n_accepted < self.num_samples_per_round else self.accept
         poses = torch.stack(accept[:self.max_samples], 0)
-        w = self.align_weights if self.align_weights is not None else pocket_align_weights(self.batch, self.use_pocket)
-        x_gt = self.batch["x_gt"].float()
+        w = self.align_weights if self.align_weights is not None else pocket_align_weights(batch, self.use_pocket)
+        x_gt = batch["x_gt"].float()
         aligned = weighted_rigid_align(x_gt[None].expand(poses.shape[0], -1, -1).contiguous(), poses, w)
         out = {"poses": aligned, "accepted": n_accepted, "rounds": self.log, "gamma_factor": self.factor, "ranking": None}
         if self.ranking:
-            from .ranking import rank_poses
             out["ranking"] = rank_poses(poses, x_gt, w, self.is_lig, symmetry=self.ligand_symmetry, lddt_pli=self.lddt_pli)
         if self.confidence is not None:
-            out.update(score_kept_poses(self.confidence, self.batch, self.conf_sz, aligned))
+            out.update(score_kept_poses(self.confidence, batch, self.conf_sz, aligned))
         if self.validity is not None:
             out.update(score_validity(self.validity, aligned, out))
         if self.vina is not None:
             out.update(score_vina(self.vina, aligned, out))
         if self.interactions is not None:
-            out.update(score_interactions(self.interactions, aligned, self.batch))
+            out.update(score_interactions(self.interactions, aligned, batch))
         if self.ring_interactions is not None:
-            out.update(score_ring_interactions(self.ring_interactions, aligned, self.batch))
+            out.update(score_ring_interactions(self.ring_interactions, aligned, batch))
         if self.hydrogens is not None:
-            out.update(score_hydrogens(self.hydrogens, aligned, self.batch))
+            out.update(score_hydrogens(self.hydrogens, aligned, batch))
         if self.receptor_geometry is not None:
-            out.update(score_receptor_geometry(self.receptor_geometry, aligned, self.batch, out))
+            out.update(score_receptor_geometry(self.receptor_geometry, aligned, batch, out))
         if self.pool_log is not None:
             out["conformers"] = self.pool_log
         if self.surface is not None:
-            out.update(score_surface(self.surface, aligned, self.batch))
+            out.update(score_surface(self.surface, aligned, batch))
         if self.refine is not None:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
         if self.search:
             out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
         if self.conformer_rmsd is not None:
-            out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, self.batch, self.ligand_idx, self.ref_mol_poses))
+            out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, batch, ligand_idx, self.ref_mol_poses))
         if self.shape is not None:
-            from .shape import score_shape
-            out.update(score_shape(self.shape, aligned, self.batch, self.ligand_idx, out))
+            out.update(score_shape(self.shape, aligned, batch, ligand_idx, out))
         if self.torsions is not None:
-            from .torsions import score_torsions
-            out.update(score_torsions(self.torsions, aligned, self.batch, self.ligand_idx, self.ref_mol_poses))
+            out.update(score_torsions(self.torsions, aligned, batch, ligand_idx, self.ref_mol_poses))
         if self.clusters is not None:
-            from .clustering import cluster_kept_poses
-            out.update(cluster_kept_poses(self.clusters, aligned, self.ligand_idx, out, interactions=self.interactions,
+            out.update(cluster_kept_poses(self.clusters, aligned, ligand_idx, out, interactions=self.interactions,
                                           ligand_symmetry=self.ligand_symmetry))
         if self.sdf is not None:
-            from .sdfio import score_sdf
             out.update(score_sdf(self.sdf, aligned, out))
         if self.infer_meta_data is not None:
-            from .pdbio import PdbTemplate
             out["pdb_blocks"] = PdbTemplate(self.infer_meta_data).blocks(aligned)
             out["receptor_pdb_blocks"] = PdbTemplate(self.infer_meta_data, receptor_only=True).blocks(aligned)
         return out
@@ -851,27 +724,29 @@ def _redock_group(model, items, common, confidence=None) -> List[dict]:
     steps = int(args0.get("steps", 40))
     power = args0.get("karras_noise_schedule_power", 1000)
     nspr = int(args0.get("num_samples_per_round", 5))
-    max_rounds = max(st.max_rounds for st in states)      # (each system stops at its own max_rounds: round_args / consume)
+    max_rounds = max(st.max_rounds for st in states)      # (each system stops at its own max_rounds: begin_round / consume)
     for rnd in range(max_rounds):
-        active = [(st, a) for st in states if (a := st.round_args(rnd)) is not None]
+        active = [st for st in states if st.begin_round(rnd)]
         if not active:
             break
-        sk = active[0][0].kw
+        want_cond = [st.reuse_conditioning and st.cond is None and st.later_round_shares_conditioning(rnd) for st in active]
+        noises = [st.kw.get("noise") for st in active]
         call = dict(num_sample=nspr, steps=steps, align_ref_pos=rnd > 0, karras_noise_schedule_power=power,
-                    mmff_gamma_0_factor=[a["factor"] for _, a in active], ode_step_scale_eta=[a["eta"] for _, a in active],
-                    ref_mol=[a["ref_mol"] for _, a in active], ref_mol_poses=[a["ref_mol_poses"] for _, a in active],
-                    seeds=[a["seed"] for _, a in active], sample_offsets=[a["sample_offset"] for _, a in active],
-                    conditionings=[a["cond"] for _, a in active], return_conditioning=confidence is not None or any(a["want_cond"] for _, a in active))
-        if any(a["noise"] is not None for _, a in active):
-            call.update(noises=[a["noise"] for _, a in active])
+                    mmff_gamma_0_factor=[st.factor for st in active], ode_step_scale_eta=[st.eta for st in active],
+                    ref_mol=[st.sampler_ref_mol for st in active], ref_mol_poses=[st.templates for st in active],
+                    seeds=[st.kw.get("seed", (st.seed + rnd) if st.seed is not None else 0) for st in active],
+                    sample_offsets=[st.kw.get("sample_offset", 0) for st in active], conditionings=[st.cond for st in active],
+                    return_conditioning=confidence is not None or any(want_cond))
+        if any(nz is not None for nz in noises):
+            call.update(noises=noises)
         for k in ("use_graph", "mmff_backend", "mmff_iters"):
-            if k in sk:
-                call[k] = sk[k]
+            if k in active[0].kw:
+                call[k] = active[0].kw[k]
         with torch.no_grad():
-            r = model.sample_diffusion_many([st.pbatch for st, _ in active], **call)
+            r = model.sample_diffusion_many([st.pbatch for st in active], **call)
         outs, conds = r if isinstance(r, tuple) else (r, [None] * len(active))
-        for (st, a), x, c in zip(active, outs, conds):
+        for st, want, x, c in zip(active, want_cond, outs, conds):
             if confidence is not None and c is not None:
                 st.conf_sz = c[2:]               # (s, z) at the group's padded token count: conditioning_s_z crops them
-            st.consume(rnd, x, c if a["want_cond"] else None)
+            st.consume(rnd, x, c if want else None)
     return [st.result() for st in states]

@@ -33,7 +33,9 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from . import _ligand_sides as sides
 from . import ops
+from ._ligand_sides import MAX_STRUCTURES
 from .refine import rotatable_bonds
 
 __all__ = ["TorsionFingerprint", "TorsionEntry", "ring_max_dev", "chordless_rings", "MAX_ATOMS", "MAX_ENTRIES", "MAX_QUADS", "MAX_STRUCTURES"]
@@ -42,7 +44,7 @@ __all__ = ["TorsionFingerprint", "TorsionEntry", "ring_max_dev", "chordless_ring
 MAX_ATOMS = 1024
 MAX_ENTRIES = 1024
 MAX_QUADS = 4096
-MAX_STRUCTURES = 65535
+_WHO = dict(name="TorsionFingerprint", takes="the kernels take")      # for the messages of _ligand_sides
 
 #: one entry of the fingerprint: kind "bond" / "ring", its atoms (the bond's two, the ring in canonical cyclic order), its quadruples,
 #: weight and max_dev in degrees
@@ -112,21 +114,6 @@ def _canonical(q):
     return min(q, q[::-1])
 
 
-def _host_idx(idx, what):
-    if idx is None:
-        return None
-    if isinstance(idx, torch.Tensor):
-        if idx.dtype.is_floating_point or idx.dtype == torch.bool:
-            raise ValueError(f"TorsionFingerprint: {what} must hold integer atom indices, got {idx.dtype}")
-        idx = idx.detach().cpu().numpy()
-    a = np.asarray(idx)
-    if a.dtype.kind not in "iu" or a.ndim != 1 or a.shape[0] < 1:
-        raise ValueError(f"TorsionFingerprint: {what} must be a non-empty 1-D list of integer atom indices")
-    if int(a.min()) < 0:
-        raise ValueError(f"TorsionFingerprint: {what} holds a negative index")
-    return a.astype(np.int64)
-
-
 class TorsionFingerprint:
     """An immutable spec: `n_atoms` ligand atoms, `entries` (a tuple of `TorsionEntry`), `ligand_idx` (the ligand atoms of a pose [A,3]
     in the order of the graph; None: a pose holds the ligand alone) and `symmetry` (a `symmetry.LigandSymmetry`; None: the identity).
@@ -138,7 +125,7 @@ class TorsionFingerprint:
         n = int(n_atoms)
         if not 1 <= n <= MAX_ATOMS:
             raise ValueError(f"TorsionFingerprint: {n} ligand atoms; the kernels take 1 .. {MAX_ATOMS}")
-        idx = _host_idx(ligand_idx, "ligand_idx")
+        idx = sides.host_idx(ligand_idx, "ligand_idx", "TorsionFingerprint")
         if idx is not None and idx.shape[0] != n:
             raise ValueError(f"TorsionFingerprint: ligand_idx names {idx.shape[0]} atoms, the graph has {n}")
         if symmetry is not None and not (hasattr(symmetry, "perms") and hasattr(symmetry, "n_atoms")):
@@ -260,7 +247,7 @@ class TorsionFingerprint:
     @property
     def symmetry_complete(self) -> bool:
         """False: the table was cut, every value is an upper bound"""
-        return True if self.symmetry is None else bool(self.symmetry.complete)
+        return sides.symmetry_complete(self.symmetry)
 
     @property
     def n_perms(self) -> int:
@@ -290,14 +277,11 @@ class TorsionFingerprint:
                         first=up(np.array(first, dtype=np.int64)))
         return ops.cached_upload(self._dev, device, make)
 
-    def _own_idx(self):
-        return None if self.ligand_idx is None else np.asarray(self.ligand_idx, dtype=np.int64)
-
     def _device_idx(self, idx, device):
         """idx on the device as int32; only the spec's own `ligand_idx` is cached (once per device)"""
         if idx is None:
             return None
-        own = self.ligand_idx is not None and idx.shape[0] == len(self.ligand_idx) and bool((idx == self._own_idx()).all())
+        own = self.ligand_idx is not None and idx.shape[0] == len(self.ligand_idx) and bool((idx == sides.own_idx(self)).all())
         if not own:                                           # a caller's target_idx: uploaded for this call, not kept
             return torch.from_numpy(idx.astype(np.int32)).to(device)
         return ops.cached_upload(self._idx, device, lambda up: up(idx.astype(np.int32)))
@@ -332,21 +316,12 @@ class TorsionFingerprint:
                                         1 if symmetric else 0, ops.stream()), "pd_torsion_tfd")
         return D, bp
 
-    def _sides(self, x, targets, target_idx):
-        ia = self._own_idx()
-        xa = _structures(x, "x", ia, self.n_atoms)
-        ib = _host_idx(target_idx, "target_idx")
-        if ib is None and ia is not None and isinstance(targets, torch.Tensor) and targets.dim() == 3 and targets.shape[1] != self.n_atoms:
-            ib = ia                                           # whole poses as targets: the ligand sits where it sits in x
-        xb = _structures(targets, "targets", ib, self.n_atoms, device=xa.device)
-        return xa, ia, xb, ib
-
     # ------------------------------------------------------------------ the calls
     def angles(self, x: torch.Tensor) -> torch.Tensor:
         """x [P,A,3] -> fp32 [P,Nq] degrees in (-180, 180]: the dihedral of every base quadruple, entry after entry (entry t owns the
         columns `qstart[t]` .. `qstart[t+1]`-1; its quadruples are `entries[t].quads`); NaN where there is no angle"""
-        ia = self._own_idx()
-        return self._prepare(_structures(x, "x", ia, self.n_atoms), ia, True)[1]
+        ia = sides.own_idx(self)
+        return self._prepare(sides.structures(x, "x", ia, self.n_atoms, **_WHO)[0], ia, True)[1]
 
     def entry_angles(self, x: torch.Tensor) -> torch.Tensor:
         """x [P,A,3] -> fp32 [P, number of rotatable-bond entries]: one representative angle per rotatable bond, that of its first
@@ -362,13 +337,10 @@ class TorsionFingerprint:
         wins, an all-NaN row gives -1, the smallest index wins a tie) and `nearest_tfd` fp32 [n] (NaN for such a row); with
         `detail=True` also `best_perm` int32 [n,C].  The rows are fixed, the targets permuted.  No result is read back; `target_idx` is a
         host list (a device tensor is copied to the host to be checked) and is uploaded per call."""
-        xa, ia, xb, ib = self._sides(x, targets, target_idx)
+        xa, ia, xb, ib, _ = sides.sides(self, x, targets, target_idx, **_WHO)
         D, bp = self._tfd(self._prepare(xa, ia)[0], self._prepare(xb, ib)[0], xa.shape[0], xb.shape[0], xa.device, False, detail)
-        key = torch.where(torch.isnan(D), torch.full_like(D, float("inf")), D)
-        near = torch.argmin(key, dim=1)
-        first = (key == key.gather(1, near[:, None])).to(torch.int8).argmax(1)      # the first of equal minima, whatever argmin picked
-        near_v = D.gather(1, first[:, None])[:, 0]
-        out = {"D": D, "nearest": torch.where(torch.isnan(near_v), torch.full_like(first, -1), first), "nearest_tfd": near_v}
+        near, near_v = sides.nearest(D)
+        out = {"D": D, "nearest": near, "nearest_tfd": near_v}
         if detail:
             out["best_perm"] = bp
         return out
@@ -380,7 +352,7 @@ class TorsionFingerprint:
         value)"""
         if not isinstance(x_ref, torch.Tensor) or x_ref.dim() != 2 or x_ref.shape[1] != 3:
             raise ValueError(f"TorsionFingerprint.to_reference: x_ref must be [A,3], got {tuple(getattr(x_ref, 'shape', ()))}")
-        xa, ia, xb, ib = self._sides(x, x_ref[None], None)
+        xa, ia, xb, ib, _ = sides.sides(self, x, x_ref[None], None, **_WHO)
         n, dev, T = xa.shape[0], xa.device, self.n_entries
         ws_a, ws_b = self._prepare(xa, ia)[0], self._prepare(xb, ib)[0]
         D, bp = self._tfd(ws_a, ws_b, n, 1, dev, False, True)
@@ -403,29 +375,9 @@ class TorsionFingerprint:
     def pairwise(self, x: torch.Tensor) -> torch.Tensor:
         """x [n,A,3] -> D fp32 [n,n], symmetric with an exact zero diagonal (NaN for a pose one of whose own angles is missing; pose i
         fixed, pose j permuted for i < j, mirrored); `PoseClusters.cluster` takes it as it is"""
-        ia = self._own_idx()
-        xa = _structures(x, "x", ia, self.n_atoms)
+        ia = sides.own_idx(self)
+        xa = sides.structures(x, "x", ia, self.n_atoms, **_WHO)[0]
         return self._tfd(self._prepare(xa, ia)[0], None, xa.shape[0], xa.shape[0], xa.device, True, False)[0]
-
-
-def _structures(x, what, idx, L, device=None):
-    """x [n,A,3] -> fp32 contiguous device tensor after the host checks: idx (host int64 or None: the structure is the ligand itself)
-    stays inside the A atoms and names L of them"""
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[2] != 3 or not x.dtype.is_floating_point:
-        raise ValueError(f"TorsionFingerprint: {what} must be a floating-point tensor [n,A,3], got {tuple(getattr(x, 'shape', ()))}")
-    n, A = int(x.shape[0]), int(x.shape[1])
-    if not 1 <= n <= MAX_STRUCTURES:
-        raise ValueError(f"TorsionFingerprint: {n} structures in {what}; the kernels take 1 .. {MAX_STRUCTURES}")
-    have = A if idx is None else int(idx.shape[0])
-    if have != L:
-        raise ValueError(f"TorsionFingerprint: {what} names {have} ligand atoms, expected {L}")
-    if idx is not None and int(idx.max()) >= A:
-        raise ValueError(f"TorsionFingerprint: an index of {what} ({int(idx.max())}) leaves its {A} atoms")
-    if device is not None and x.device.type == "cpu":
-        x = x.to(device)                                      # targets may come from the host, as redock's template pool may
-    if not x.is_cuda or (device is not None and x.device != device):
-        raise ValueError(f"TorsionFingerprint: {what} must be on the GPU{'' if device is None else ' of the poses'}, got a tensor on {x.device}")
-    return x.float().contiguous()
 
 
 # ------------------------------------------------------------------ redock(torsions=)

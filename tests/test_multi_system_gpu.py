@@ -378,3 +378,58 @@ def test_redock_many_groups_in_lockstep(small):
     rp = redock_many(model, [systems[i] for i in perm], group=3, **common)
     for j, i in enumerate(perm):
         assert rp[j]["rounds"] == res[i]["rounds"] and rp[j]["poses"].shape == res[i]["poses"].shape
+
+
+def _differing_leaves(a, b, path="result"):
+    """the paths at which two result trees differ: another key set, a tensor leaf that is not torch.equal (a NaN equals a NaN in the
+    same place), any other leaf that is not =="""
+    if isinstance(a, dict) or isinstance(b, dict):
+        if not (isinstance(a, dict) and isinstance(b, dict)) or set(a) != set(b):
+            return [path + ": keys"]
+        return [d for k in a for d in _differing_leaves(a[k], b[k], f"{path}[{k!r}]")]
+    if isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor):
+        if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)) or a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+            return [path + ": tensor kind"]
+        if a.dtype.is_floating_point:
+            same = bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
+        else:
+            same = torch.equal(a, b)
+        return [] if same else [path]
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)) and len(a) == len(b) and type(a) is type(b):
+        return [d for i, (u, w) in enumerate(zip(a, b)) for d in _differing_leaves(u, w, f"{path}[{i}]")]
+    return [] if a == b else [path]
+
+
+def test_a_group_of_one_returns_what_redock_returns(small):
+    """redock_many(group=1) against redock for one seeded system with physics correction, ranking and the pose scorers: the same key
+    tree, every tensor leaf torch.equal (NaN = NaN in place), every other leaf ==.  (A group of one samples bit-identically to
+    sample_diffusion, test_one_system_equals_sample_diffusion, and both callers run the same per-system rules, driver._RedockState.)
+    One leaf is cut before the comparison: sdf["bytes"] is a buffer of the records' upper bound whose bytes behind offsets[n] are
+    never written (`SdfTemplate.format`), so only the SD file itself, bytes[:offsets[n]], is compared."""
+    from physdock_amd import BestFitRmsd, PoseClusters, TorsionFingerprint
+    from physdock_amd.driver import ligand_atom_mask, redock, redock_many
+    from physdock_amd.interactions import InteractionFingerprint
+    from physdock_amd.scoring import VinaScore
+    from physdock_amd.sdfio import SdfTemplate
+    from physdock_amd.shape import ShapeOverlap, ShapeSpec
+    from physdock_amd.synthetic import make_batch, reference_conformers
+    from physdock_amd.validity import PoseValidity
+    model, cfg, P = small
+    raw = make_batch(18, 5, 6, 8, seed=70)
+    b = to_dev(raw)
+    lig = torch.nonzero(ligand_atom_mask(b)).flatten()
+    chain = [(i, i + 1) for i in range(int(lig.numel()) - 1)]
+    kw = dict(physics_correction=True, ranking=True, seed=100, ref_mol_poses=reference_conformers(raw, n_conf=6, seed=80),
+              accept_fn=lambda x: float(x[0, 0]) > 0.0, max_samples=4, max_rounds=3, num_samples_per_round=3, steps=6,
+              validity=PoseValidity.from_batch(b, chain), validity_filter=True, conformer_rmsd=BestFitRmsd(lig),
+              torsions=TorsionFingerprint.from_batch(b, chain), clusters=PoseClusters(0.5), vina=VinaScore.from_batch(b, chain),
+              interactions=InteractionFingerprint.from_batch(b, chain), shape=ShapeOverlap(ShapeSpec.from_batch(b, chain)),
+              sdf=SdfTemplate.from_batch(b, chain, title="one"))
+    solo = redock(model, b, **kw)
+    (grouped,) = redock_many(model, [b], group=1, **kw)
+    assert {"validity", "conformer_rmsd", "torsions", "clusters", "vina", "interactions", "shape", "sdf", "ranking"} <= set(solo)
+    assert solo["ranking"] is not None and len(solo["rounds"]) >= 2 and all("invalid" in r for r in solo["rounds"])
+    assert {"nearest_template", "pool_to_gt"} <= set(solo["conformer_rmsd"]) and "nearest_template_tfd" in solo["torsions"]
+    for r in (grouped, solo):
+        r["sdf"] = dict(r["sdf"], bytes=r["sdf"]["bytes"][:int(r["sdf"]["offsets"][-1])])
+    assert _differing_leaves(grouped, solo) == []
