@@ -907,6 +907,60 @@ int pd_buried_surface(const float* x, const unsigned char* cls, const float* rad
                       const unsigned char* polar, const int* res_start, const int* res_atom, float probe, int* ws_free,
                       int* free_points, int* buried_points, float* per_atom, float* totals, float* residue_buried,
                       int* interface_residues, int P, int A, int L, int R, int N, int n_points, void* stream);
+/* Pocket volume, enclosure and lining residues of P poses of one system on a lattice around the ligand (pocket.hip; ABI 11,
+ * additive; the grid method of LIGSITE, Hendlich, Rippmann & Barnickel 1997, and POVME; HEAVY ATOMS ONLY; the default spacing, probe,
+ * lining distance, reach and enclosure threshold are this package's own and have not been validated on real complexes; the reference
+ * has no counterpart).  Tables, built once per system (physdock_amd/pocket.py): cls [A] and radius [A] as pd_buried_surface takes them,
+ * lig_idx [L], the receptor atoms by residue res_start [R + 1] / res_atom [N].  tests/pocket_ref.py is the written definition.
+ *   centre     centre == NULL: the float64 mean of the active ligand atoms (cls 2) of the pose, summed in lig_idx order and rounded
+ *              once to fp32; else centre[p * centre_stride + 0 .. 2] (centre_stride 0: one centre for all poses, 3: one each).  With
+ *              snap != 0 each coordinate c becomes fl32(h * rint(c / h)), evaluated in float64.  centre_used [P][3] is what was used.
+ *   lattice    n points per axis, spacing h (fp32); in float64 o = centre - (h (n - 1)) / 2, point (i, j, k) is g = o + (i, j, k) h
+ *              and has the linear index (i n + j) n + k
+ *   predicates in float64 from the fp32 inputs, d = sqrt((dx dx + dy dy) + dz dz) without fused multiply-add:
+ *              solid(g): a receptor atom j has d(g, x_j) < radius_j + probe;  inside(g): an active ligand atom i has d(g, x_i) <
+ *              radius_i;  near(g, j): d(g, x_j) < radius_j + lining for a receptor atom j.  (The kernels decide a pair in fp32 only
+ *              outside a guard band of 2^-20 (h (n - 1) + threshold) around the threshold - derived in pocket.hip - and evaluate it
+ *              in float64 inside: the result is the float64 predicate.)
+ *   buried(g)  of the seven directions (1,0,0) (0,1,0) (0,0,1) (1,1,1) (1,1,-1) (1,-1,1) (-1,1,1) the number in which a solid point
+ *              lies within steps[d] lattice steps of g in the + sense and in the - sense; leaving the lattice is no hit.  steps is a
+ *              HOST array of seven ints, floor(reach / (h |d|)) by the caller.
+ *   pocket     not solid and buried >= min_enclosed (0 .. 7).  Pocket points form 6-connected components; a pocket point with inside is
+ *              occupied; the site is the union of the components that hold an occupied point.
+ *   classes[p][g]        0 solid, 1 free but not pocket, 2 pocket outside the site, 3 site and empty, 4 site and occupied
+ *   buried[p][g]         buried(g); 0 for a solid point
+ *   counts[p][0 .. 7]    n_solid, n_free (every non-solid point), n_pocket, n_site, n_occupied, n_ligand (non-solid points with
+ *                        inside), n_components, n_site_components
+ *   truncated[p]         1: a site point lies on a face of the lattice
+ *   values[v][p]         PD_POCKET_VALUES rows of P: 0 site_volume = n_site h^3, 1 unfilled_volume = (n_site - n_occupied) h^3, 2
+ *                        pocket_volume = n_pocket h^3 (the product in float64, rounded once), 3 filled_fraction = n_occupied / n_site,
+ *                        4 ligand_in_site = n_occupied / n_ligand (0 where the divisor is 0), 5 ligand_enclosure = the mean of
+ *                        atom_buried / 7 over the ligand atoms that have a point (0 when none has)
+ *   atom_class[p][s], atom_buried[p][s]   class and buried of the lattice point nearest ligand atom s, rint((x - o) / h) per axis in
+ *                        float64; 255 for an inactive atom and for one outside the lattice
+ *   lining_points[p][r]  the site points g with near(g, j) for at least one receptor atom j of residue r; lining_residues[p] the
+ *                        number of residues with a count above 0
+ *   ok[p]                0: a non-finite coordinate in an atom of class != 0, or a non-finite centre (a ligand without an active atom
+ *                        has one).  Then every count is 0, every float NaN (centre_used too), classes, buried, atom_class and
+ *                        atom_buried are 255 and truncated is 0.
+ * ws: pd_pocket_grid_workspace_numel(P, n, A) = P (2 n^3 + 2 n^2 ceil(n / 32)) ints (labels, marks and the two bit masks; negative:
+ * the error code).  Four launches, no allocation, no synchronisation, no floating-point atomics; "any" tests and integer sums only:
+ * bit-identical from launch to launch, independent of P and of a pose's place among the P.  PD_ERR_ARG: a required pointer is NULL
+ * (centre may be; res_atom when N == 0) or an int / float pointer is off its 4-byte alignment, a size < 1 (N >= 0, N <= A), h not
+ * positive and finite, probe or lining negative or not finite, a negative step count, min_enclosed outside 0 .. 7, a centre_stride other
+ * than 0 or 3, a short workspace.  PD_ERR_UNSUPPORTED: n outside PD_POCKET_MIN_N .. PD_POCKET_MAX_N, L > 1024, R > 4096, P > 65535, A >
+ * 2^22, h (n - 1) > 4096 A.  A rejected call launches nothing.                                                                       */
+#define PD_POCKET_MIN_N 8
+#define PD_POCKET_MAX_N 48
+#define PD_POCKET_COUNTS 8
+#define PD_POCKET_VALUES 6
+long long pd_pocket_grid_workspace_numel(int P, int n, int A);
+int pd_pocket_grid(const float* x, const unsigned char* cls, const float* radius, const int* lig_idx, const int* res_start,
+                   const int* res_atom, const float* centre, int centre_stride, int snap, float h, int n, float probe, float lining,
+                   const int* steps, int min_enclosed, int* ws, long long ws_numel, float* centre_used, unsigned char* ok,
+                   unsigned char* classes, unsigned char* buried, int* counts, unsigned char* truncated, float* values,
+                   unsigned char* atom_class, unsigned char* atom_buried, int* lining_points, int* lining_residues, int P, int A, int L,
+                   int R, int N, void* stream);
 int pd_euler(const float* x_hat, const float* x_den, const float* x_proj, const float* w, float t_hat, float eta, float dt,
              float* x_next, int B, int A, void* stream);
 int pd_timestep_embed(const float* tau, float* emb, int n, void* stream);

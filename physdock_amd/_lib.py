@@ -272,7 +272,10 @@ def _declare(L):
         i, i, i, i, i, p)
     sig("pd_hydrogen_bonds_workspace", i, i, i, i, i)
     sig("pd_buried_surface", p, p, p, p, p, p, p, p, f, p, p, p, p, p, p, p, i, i, i, i, i, i, p)       # ABI 11, additive (sasa.hip)
-    sig("pd_pose_clusters_workspace_numel", i)                                               # ABI 11, additive (cluster.hip)
+    sig("pd_pocket_grid_workspace_numel", i, i, i, restype=ll)                                # ABI 11, additive (pocket.hip)
+    sig("pd_pocket_grid", p, p, p, p, p, p, p, i, i, f, i, f, f, C.POINTER(C.c_int), i, p, ll, p, p, p, p, p, p, p, p, p, p, p,
+        i, i, i, i, i, p)
+    sig("pd_pose_clusters_workspace_numel", i)                                             # ABI 11, additive (cluster.hip)
     sig("pd_pose_clusters", p, p, f, p, p, p, ll, p, p, p, p, p, p, p, p, p, i, p)
     sig("pd_embed_conformers_workspace_numel", i, i)                                         # ABI 11, additive (conformers.hip)
     sig("pd_dg_error_grad", p, p, p, p, p, p, d, d, p, p, i, i, i, p)

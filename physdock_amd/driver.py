@@ -282,6 +282,32 @@ def score_surface(surface, aligned, batch) -> dict:
     return res
 
 
+#: what redock(pocket=) keeps of PocketGrid.measure (the byte maps are left out: maps=False)
+POCKET_KEYS = ("site_volume", "unfilled_volume", "pocket_volume", "filled_fraction", "ligand_in_site", "ligand_enclosure", "truncated",
+               "lining_residues", "ok", "counts", "atom_buried", "lining_points")
+
+
+def check_pocket(pocket, batch) -> None:
+    """redock(pocket=): raise ValueError unless `pocket` is a `pocket.PocketGrid` over the batch's atoms"""
+    if pocket is None:
+        return
+    if not callable(getattr(pocket, "measure", None)) or not hasattr(pocket, "n_pose_atoms"):
+        raise ValueError("pocket= takes a pocket.PocketGrid of the system")
+    n = int(batch["x_gt"].shape[0])
+    if pocket.n_pose_atoms != n:
+        raise ValueError(f"pocket= was built over {pocket.n_pose_atoms} pose atoms, the batch holds {n}")
+
+
+def score_pocket(pocket, aligned, batch) -> dict:
+    """redock(pocket=): {"pocket": the scalars, counts, atom_buried and lining_points of PocketGrid.measure of the kept poses} and, when
+    the batch carries the ground truth, "pocket_gt": the same of `x_gt` (one pose)"""
+    keep = lambda m: {k: m[k] for k in POCKET_KEYS}
+    res = {"pocket": keep(pocket.measure(aligned, maps=False))}
+    if "x_gt" in batch:
+        res["pocket_gt"] = keep(pocket.measure(batch["x_gt"].float()[None], maps=False))
+    return res
+
+
 def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses: Optional[torch.Tensor] = None,
            accept_fn: Optional[Callable[[torch.Tensor], bool]] = None, chirality=None, physics_correction: bool = False,
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
@@ -291,7 +317,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None) -> dict:
+           torsions=None, pocket=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -384,7 +410,13 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     deviation of every entry of the fingerprint: which bond is wrong) and, with a template pool in use, `nearest_template` /
     `nearest_template_tfd` [n].  `clusters=PoseClusters(metric="torsion")` clusters `pairwise` and needs it; with `sdf=` the records gain
     the item `tfd` (`to_gt`).  A spec over another number of ligand atoms raises ValueError before anything is sampled.  Nothing else
-    changes."""
+    changes.
+    `pocket` (a `pocket.PocketGrid` of the system): the result gains `pocket` = the scalars (`site_volume`, `unfilled_volume`,
+    `pocket_volume`, `filled_fraction`, `ligand_in_site`, `ligand_enclosure`, `truncated`, `lining_residues`, `ok`), `counts`,
+    `atom_buried` and `lining_points` of its `measure` of the returned `poses` (the cavity each pose's own receptor leaves around the
+    ligand, how much of it the ligand fills, which atoms stick out and which residues line it) and, as the batch carries `x_gt`,
+    `pocket_gt` = the same of the ground truth (one pose).  One built over another number of atoms raises ValueError before anything is
+    sampled.  Nothing else changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -547,7 +579,7 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None, torsions=None):
+                 conformer_rmsd=None, shape=None, torsions=None, pocket=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
@@ -557,6 +589,7 @@ class _RedockState:
         check_redock_torsions(torsions, batch)
         check_search(search, refine)
         check_hydrogens(hydrogens, batch)
+        check_pocket(pocket, batch)
         check_receptor_geometry(receptor_geometry, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
         check_redock_sdf(sdf, batch, hydrogens)
@@ -679,6 +712,8 @@ class _RedockState:
             out["conformers"] = self.pool_log
         if self.surface is not None:
             out.update(score_surface(self.surface, aligned, batch))
+        if self.pocket is not None:
+            out.update(score_pocket(self.pocket, aligned, batch))
         if self.refine is not None:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
         if self.search:

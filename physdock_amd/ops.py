@@ -543,3 +543,23 @@ def bias_to_frag(bias):
     x = pad.reshape(H, nqt, 32, nkt, 4, 2, 4)            # q5, kt, g, hh, e
     x = x.permute(0, 1, 3, 4, 5, 2, 6)                    # H, qt, kt, g, hh, q5, e
     return x.reshape(-1).contiguous()
+
+
+def pocket_grid_workspace_numel(P, n, A):
+    """ints of workspace pd_pocket_grid needs for P poses of A atoms on an n^3 lattice (csrc/pocket.hip)"""
+    numel = _lib.init().pd_pocket_grid_workspace_numel(int(P), int(n), int(A))
+    check(min(numel, 0), "pd_pocket_grid_workspace_numel")
+    return numel
+
+
+def pocket_grid(x, t, centre, snap, h, n, probe, lining, steps, min_enclosed, ws, out, L, R, N):
+    """pd_pocket_grid on the current stream: x fp32 [P,A,3]; t: the tables cls, radius, ligand_idx, res_start, res_atom on x's device;
+    centre: None (the ligand's) or fp32 [3] / [P,3]; steps: seven ints; ws int32; out: the output tensors by their header names"""
+    P, A = x.shape[0], x.shape[1]
+    stride = 0 if centre is None or centre.dim() == 1 else 3
+    check(_lib.init().pd_pocket_grid(
+        ptr(x), ptr(t["cls"]), ptr(t["radius"]), ptr(t["ligand_idx"]), ptr(t["res_start"]), ptr(t["res_atom"]) if N else None, ptr(centre),
+        stride, int(bool(snap)), float(h), int(n), float(probe), float(lining), (C.c_int * 7)(*[int(s) for s in steps]), int(min_enclosed),
+        ptr(ws), ws.numel(), ptr(out["centre"]), ptr(out["ok"]), ptr(out["classes"]), ptr(out["buried"]), ptr(out["counts"]),
+        ptr(out["truncated"]), ptr(out["values"]), ptr(out["atom_class"]), ptr(out["atom_buried"]), ptr(out["lining_points"]),
+        ptr(out["lining_residues"]), P, A, int(L), int(R), int(N), stream()), "pd_pocket_grid")
