@@ -1201,6 +1201,52 @@ int pd_torsion_tfd(const double* ws_a, const double* ws_b, const int* qstart, co
 int pd_torsion_deviation(const double* ws_a, const double* ws_ref, const int* rows, const int* qstart, const double* inv_max_dev,
                          const unsigned short* image, float* dev, int na, int Q, int T, int Nq, int M, void* stream);
 
+/* ---- Poses against the trunk's own distogram (distogram_score.hip; additive exports of ABI 11) -------------------------
+ * How well does a pose agree with the distances the trunk predicted?  logits fp32 [T][T][no_bins] (PhysDock.predict_distogram) over
+ * the pseudo-beta distance of two tokens; the package's own definition: tests/distogram_score_ref.py and physdock_amd/distogram.py,
+ * which builds the tables.  Agreement with the trunk is self-consistency, not accuracy, and the defaults of the Python class (contact
+ * cutoff, cap on the expected distance, classes) have not been validated.  Float64 from the fp32 inputs, fixed-order sums, no atomics:
+ * a pose's values are bit-identical whatever the batch.  Tables on the DEVICE: token_class uint8 [T] (0 inactive, 1 receptor, 2
+ * ligand), pb_atom int32 [T] (the pseudo-beta atom of an active token, inside 0 .. A-1), rows int32 [n_rows] (the n_ligand_rows ligand
+ * tokens ascending, then - with the receptor class - the n_receptor_tokens receptor tokens ascending), row_of int32 [T] (a ligand
+ * token's place in rows).  The caller guarantees that every index lies inside its array.  On the HOST, float64: centres [no_bins] and
+ * bounds_sq [no_bins - 1] (the squared bin edges).  contact_bin: the last bin that counts as a contact, -1 for none.
+ * pd_distogram_tables    : per token pair lse = log sum exp of its logits (double [T][T]), expected = sum_b softmax_b centres[b] and
+ *                          p_contact = sum_{b <= contact_bin} softmax_b (float [T][T], rounded once).
+ * pd_distogram_score     : x fp32 [P][A][3].  bin = #{k : d2 > bounds_sq[k]} of every pair of a row, nll = lse - logit[bin].  bins uint8
+ *                          [P][n_ligand_rows][T] (255 in the column of an inactive token) and ws double [P][n_rows][8]: per row the sum
+ *                          of nll over its interface pairs (a receptor row: over its receptor pairs j > i), over its ligand pairs
+ *                          j > i, of |d - expected| where expected <= max_expected, of p_contact over the pairs in contact, and the
+ *                          counts of the third, of p_contact >= 0.5, of those in contact, of all in contact.
+ * pd_distogram_reduce    : values float [7][P] = nll_interface, nll_ligand, nll_receptor, nll, expected_error, contact_recovery,
+ *                          contact_precision (NaN where nothing is counted); token_nll float [P][T] (the mean interface nll of a token
+ *                          against the other side, NaN without a partner), n_contacts int32 [P], ok uint8 [P]: a pose with a non-finite
+ *                          coordinate at an active pseudo-beta atom has ok = 0, NaN floats, n_contacts 0 and zeroed bins.
+ * pd_distogram_potential : V(d) = the linear interpolation of lse - logit over the centres, constant outside them.  potential float
+ *                          [P] = its mean over the interface and the ligand pairs; forces float [P][n_ligand_rows][3] = minus the
+ *                          gradient on each ligand token's pseudo-beta atom and abs_force float [P][n_ligand_rows] = the sum of the
+ *                          absolute values of the contributions (both or neither NULL).  ws double [P][n_ligand_rows][5].
+ * 2 <= no_bins <= 64, T <= 4096, P <= 65535: else PD_ERR_UNSUPPORTED.  A NULL required pointer, a misaligned pointer, a size < 1, a
+ * short workspace or a non-finite centre / bound: PD_ERR_ARG.  A rejected call launches nothing.                                    */
+#define PD_DISTOGRAM_MAX_BINS 64
+#define PD_DISTOGRAM_MAX_TOKENS 4096
+#define PD_DISTOGRAM_ROW_PARTIALS 8
+#define PD_DISTOGRAM_POTENTIAL_PARTIALS 5
+#define PD_DISTOGRAM_VALUES 7
+int pd_distogram_tables(const float* logits, const double* centres, int contact_bin, double* lse, float* expected, float* p_contact,
+                        int T, int no_bins, void* stream);
+int pd_distogram_score(const float* x, const int* pb_atom, const unsigned char* token_class, const int* rows, const float* logits,
+                       const double* lse, const float* expected, const float* p_contact, const double* bounds_sq, int contact_bin,
+                       float max_expected, unsigned char* bins, double* ws, long long ws_numel, int P, int A, int T, int no_bins,
+                       int n_ligand_rows, int n_rows, void* stream);
+int pd_distogram_reduce(const float* x, const int* pb_atom, const unsigned char* token_class, const int* rows, const int* row_of,
+                        const float* logits, const double* lse, unsigned char* bins, const double* ws, long long ws_numel,
+                        float* values, float* token_nll, int* n_contacts, unsigned char* ok, int P, int A, int T, int no_bins,
+                        int n_ligand_rows, int n_receptor_tokens, int n_rows, void* stream);
+int pd_distogram_potential(const float* x, const int* pb_atom, const unsigned char* token_class, const int* rows, const float* logits,
+                           const double* lse, const double* centres, double* ws, long long ws_numel, float* potential, float* forces,
+                           float* abs_force, int P, int A, int T, int no_bins, int n_ligand_rows, int n_receptor_tokens, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

@@ -30,6 +30,7 @@ from .hydrogens import Hydrogens  # noqa: F401  (riding hydrogens of every pose 
 from .receptor_geometry import ReceptorGeometry  # noqa: F401  (stereochemistry checks of every pose's receptor; csrc/receptor_geometry.hip)
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .pocket import PocketGrid  # noqa: F401  (pocket volume, enclosure and lining residues of every pose on a lattice; csrc/pocket.hip)
+from .distogram import DistogramScore  # noqa: F401  (poses ranked by the trunk's own distogram, per-token detail, a potential with forces; csrc/distogram_score.hip)
 from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface area of every pose, Shrake - Rupley; csrc/sasa.hip)
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)
 from .conformers import ConformerEnsemble  # noqa: F401  (distance-geometry conformers of a ligand, the template pool; csrc/conformers.hip)

@@ -293,6 +293,11 @@ def _declare(L):
     sig("pd_torsion_deviation", p, p, p, p, p, p, p, i, i, i, i, i, p)
     sig("pd_shape_overlay_workspace_numel", i, i, i, restype=ll)
     sig("pd_shape_overlay", p, ll, p, p, i, i, i, p, ll, p, p, i, i, i, d, i, d, d, p, ll, p, p, p, p, p, p, p, p, p, p)
+    hd = C.POINTER(C.c_double)                                                               # float64 values on the HOST
+    sig("pd_distogram_tables", p, hd, i, p, p, p, i, i, p)                                   # ABI 11, additive (distogram_score.hip)
+    sig("pd_distogram_score", p, p, p, p, p, p, p, p, hd, i, f, p, p, ll, i, i, i, i, i, i, p)
+    sig("pd_distogram_reduce", p, p, p, p, p, p, p, p, p, ll, p, p, p, p, i, i, i, i, i, i, i, p)
+    sig("pd_distogram_potential", p, p, p, p, p, p, hd, p, ll, p, p, p, i, i, i, i, i, i, p)
 
 
 def ptr(t):

@@ -32,15 +32,15 @@ import torch
 from . import ops
 
 MAX_POSES = 8192                      # PD_POSE_CLUSTERS_MAX_POSES
-ORDERS = (None, "confidence", "vina", "vina_refined")
+ORDERS = (None, "confidence", "vina", "vina_refined", "distogram")
 METRICS = ("rmsd", "interactions", "conformer", "shape", "torsion")
 _PER_MODE = ("leader", "size", "radius", "medoid", "spread", "mean_score")
 
 
 class PoseClusters:
     """An immutable spec: `cutoff` (A for `metric="rmsd"` and `"conformer"`, a Tanimoto distance for `"interactions"` and `"shape"`, a TFD in 0 .. 1 for `"torsion"`), `by` - the order `redock` walks
-    the poses in (None: pose ids; "confidence", "vina", "vina_refined": the result's `order_confidence`, `order_vina`,
-    `order_vina_refined`) - and `metric`.  `cluster` and `binding_modes` take their order from the caller."""
+    the poses in (None: pose ids; "confidence", "vina", "vina_refined", "distogram": the result's `order_confidence`, `order_vina`,
+    `order_vina_refined`, `order_distogram`) - and `metric`.  `cluster` and `binding_modes` take their order from the caller."""
 
     __slots__ = ("cutoff", "by", "metric")
 
@@ -176,7 +176,7 @@ class PoseClusters:
 
 
 def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=None, interactions=None, conformer_rmsd=None,
-                               shape=None, torsions=None) -> None:
+                               shape=None, torsions=None, distogram=None) -> None:
     """redock(clusters=): raise ValueError for what the spec needs and the call lacks - before any sampling"""
     if clusters is None:
         return
@@ -196,6 +196,8 @@ def check_redock_prerequisites(clusters, *, confidence=None, vina=None, refine=N
         raise ValueError("clusters=PoseClusters(by='vina') needs vina=")
     if clusters.by == "vina_refined" and (refine is None or vina is None):
         raise ValueError("clusters=PoseClusters(by='vina_refined') needs refine= and vina=")
+    if clusters.by == "distogram" and not distogram:
+        raise ValueError("clusters=PoseClusters(by='distogram') needs distogram=")
 
 
 def cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=None, ligand_symmetry=None) -> dict:
@@ -223,6 +225,8 @@ def cluster_kept_poses(clusters, aligned, ligand_idx, out, interactions=None, li
         order = out["order_vina"]
     elif clusters.by == "vina_refined":
         order, scores = out["order_vina_refined"], out["refined"]["score"]
+    elif clusters.by == "distogram":
+        order = out["order_distogram"]
     else:
         order = torch.arange(aligned.shape[0], dtype=torch.int32, device=aligned.device)
     valid = out["validity"]["valid"] if "validity" in out else None

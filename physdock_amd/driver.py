@@ -308,6 +308,35 @@ def score_pocket(pocket, aligned, batch) -> dict:
     return res
 
 
+#: what redock(distogram=) reports of DistogramScore.score of the kept poses; `potential` comes from DistogramScore.potential
+DISTOGRAM_KEYS = ("nll_interface", "nll_ligand", "token_nll", "expected_error", "contact_recovery", "contact_precision", "potential")
+
+
+def check_distogram(distogram) -> None:
+    """redock(distogram=): raise ValueError unless it is None, False, True or a dict of `DistogramScore.from_logits` keyword arguments"""
+    if distogram is None or isinstance(distogram, bool):
+        return
+    if not isinstance(distogram, dict):
+        raise ValueError(f"distogram= takes True or a dict of DistogramScore.from_logits keyword arguments, got {type(distogram).__name__}")
+    bad = set(distogram) - {"contact_cutoff", "max_expected", "receptor", "min_bin", "max_bin", "pseudo_beta"}
+    if bad:
+        raise ValueError(f"distogram=: unknown DistogramScore.from_logits keyword arguments {sorted(bad)}")
+
+
+def score_distogram(spec, aligned, out) -> dict:
+    """redock(distogram=): {"distogram": the DISTOGRAM_KEYS of `spec.score` / `spec.potential` of the kept poses, "order_distogram":
+    their ids by ascending nll_interface} and, when their validity was checked too, "order_distogram_valid" (valid poses in front)"""
+    from .ranking import rank_by_score
+    if spec is None:
+        raise RuntimeError("distogram=: the sampler returned no conditioning to take the distogram from")
+    found = dict(spec.score(aligned), **spec.potential(aligned))
+    res = {"distogram": {k: found[k] for k in DISTOGRAM_KEYS}}
+    res["order_distogram"] = rank_by_score(found["nll_interface"])
+    if "validity" in out:
+        res["order_distogram_valid"] = rank_by_score(found["nll_interface"], valid=out["validity"]["valid"])
+    return res
+
+
 def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses: Optional[torch.Tensor] = None,
            accept_fn: Optional[Callable[[torch.Tensor], bool]] = None, chirality=None, physics_correction: bool = False,
            max_samples: int = 5, max_rounds: int = 10, num_samples_per_round: int = 5, steps: int = 40,
@@ -317,7 +346,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None, pocket=None) -> dict:
+           torsions=None, pocket=None, distogram=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -416,11 +445,23 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `atom_buried` and `lining_points` of its `measure` of the returned `poses` (the cavity each pose's own receptor leaves around the
     ligand, how much of it the ligand fills, which atoms stick out and which residues line it) and, as the batch carries `x_gt`,
     `pocket_gt` = the same of the ground truth (one pose).  One built over another number of atoms raises ValueError before anything is
-    sampled.  Nothing else changes."""
+    sampled.  Nothing else changes.
+    `distogram` (True for the defaults, or a dict of `distogram.DistogramScore.from_logits` keyword arguments): the kept poses are
+    scored against the trunk's own distogram - the logits are `model.predict_distogram` of the (s, z) of the last sampler call, taken
+    once per system exactly as `confidence=` takes them (a model whose sampler does not return its conditioning raises ValueError).
+    The result gains `distogram` = `nll_interface`, `nll_ligand`, `token_nll`, `expected_error`, `contact_recovery`,
+    `contact_precision` of `DistogramScore.score` and `potential` of the returned `poses`, `order_distogram` = `rank_by_score` of
+    `nll_interface` (the pose the trunk's distances agree with best first) and, with `validity=`, `order_distogram_valid`;
+    `clusters=PoseClusters(by="distogram")` walks `order_distogram` and needs it; with `sdf=` the records gain the item
+    `distogram_nll`.  A batch without `token_id_to_pseudo_beta_atom_id` is scored on the first atom of every token.  Nothing else
+    changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
         raise ValueError("confidence= needs a model whose sampler returns its conditioning (return_conditioning=)")
+    if distogram and not getattr(model, "supports_conditioning_reuse", False):
+        raise ValueError("distogram= needs a model whose sampler returns its conditioning (return_conditioning=)")
+    need_sz = confidence is not None or bool(distogram)      # the trunk's (s, z) of the last sampler call
     reuse = bool(reuse_conditioning and getattr(model, "supports_conditioning_reuse", False))
     for rnd in range(max_rounds):
         if not st.begin_round(rnd):
@@ -436,7 +477,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
                 call.update(conditioning=st.cond)
             elif st.later_round_shares_conditioning(rnd):
                 call.update(return_conditioning=True)
-        want_sz = confidence is not None and call.get("conditioning") is None and not call.get("return_conditioning")
+        want_sz = need_sz and call.get("conditioning") is None and not call.get("return_conditioning")
         if want_sz:
             call.update(return_conditioning=True)
         with torch.no_grad():
@@ -444,13 +485,14 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
         got = None
         if isinstance(x_pred, tuple):
             x_pred, got = x_pred
-            if confidence is not None:
+            if need_sz:
                 st.conf_sz = got[2:]
             if want_sz:
-                got = None                   # asked for the confidence head alone: not kept for later rounds
-        elif confidence is not None and call.get("conditioning") is not None:
+                got = None                   # asked for the confidence head / the distogram alone: not kept for later rounds
+        elif need_sz and call.get("conditioning") is not None:
             st.conf_sz = call["conditioning"][2:]
         st.consume(rnd, x_pred, got)
+    st.take_distogram(model)
     return st.result()
 
 
@@ -579,12 +621,13 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None, torsions=None, pocket=None):
+                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
         check_redock_prerequisites(clusters, confidence=confidence, vina=vina, refine=refine, interactions=interactions,
-                                   conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions)
+                                   conformer_rmsd=conformer_rmsd, shape=shape, torsions=torsions, distogram=distogram)
+        check_distogram(distogram)
         check_redock_shape(shape, batch)
         check_redock_torsions(torsions, batch)
         check_search(search, refine)
@@ -613,7 +656,8 @@ class _RedockState:
         ref_mol_num_error = ref_mol is None or (n_mol is not None and n_mol != int(self.is_lig.sum()))     # redocking.py:195-196
         self.sampler_ref_mol, self.eta = (None, 1.5) if ref_mol_num_error else (ref_mol, 1.0)      # ... :292,296
         self.cond = None                     # the conditioning that rounds with the same features share
-        self.conf_sz = None                  # confidence=: (s, z) of the most recent sampler call, set by the caller
+        self.conf_sz = None                  # confidence= / distogram=: (s, z) of the most recent sampler call, set by the caller
+        self.distogram_spec = None           # distogram=: the system's DistogramScore, built once behind the round loop
         self.done, self.templates = False, None
 
     def begin_round(self, rnd) -> bool:
@@ -680,6 +724,13 @@ class _RedockState:
         if rnd + 1 >= self.max_rounds:
             self.done = True
 
+    def take_distogram(self, model) -> None:
+        """distogram=: the system's logits and tables from the (s, z) of its most recent sampler call - once, behind the round loop"""
+        if self.distogram and self.conf_sz is not None:
+            from .distogram import DistogramScore
+            kw = self.distogram if isinstance(self.distogram, dict) else {}
+            self.distogram_spec = DistogramScore.from_conditioning(model, self.batch, self.conf_sz, **kw)
+
     def result(self) -> dict:
         """top-up with rejected poses, alignment into the ground-truth frame, ranking, the pose scorers in their order (score_vina
         reads out["validity"], cluster_kept_poses almost everything, score_sdf comes last) and the PDB text"""
@@ -724,6 +775,8 @@ class _RedockState:
             out.update(score_shape(self.shape, aligned, batch, ligand_idx, out))
         if self.torsions is not None:
             out.update(score_torsions(self.torsions, aligned, batch, ligand_idx, self.ref_mol_poses))
+        if self.distogram:
+            out.update(score_distogram(self.distogram_spec, aligned, out))
         if self.clusters is not None:
             out.update(cluster_kept_poses(self.clusters, aligned, ligand_idx, out, interactions=self.interactions,
                                           ligand_symmetry=self.ligand_symmetry))
@@ -749,6 +802,8 @@ def _redock_group(model, items, common, confidence=None) -> List[dict]:
         if bad:
             raise ValueError(f"redock_many(group=): sampler_kwargs {sorted(bad)} are not supported by grouped sampling")
         states.append(_RedockState(b, pb, **{"confidence": confidence, **args}))
+        if states[-1].distogram and not getattr(model, "supports_conditioning_reuse", False):
+            raise ValueError("distogram= needs a model whose sampler returns its conditioning (return_conditioning=)")
     for k in ("steps", "karras_noise_schedule_power", "num_samples_per_round", "use_graph", "mmff_backend", "mmff_iters"):
         # one sampler call per round serves the whole group: what it shares must be the same for every system
         vals = {repr(st.kw.get(k)) if k in _MANY_SAMPLER_KEYS else repr(dict(common, **kw).get(k)) for st, (_, kw) in zip(states, items)}
@@ -771,7 +826,7 @@ def _redock_group(model, items, common, confidence=None) -> List[dict]:
                     ref_mol=[st.sampler_ref_mol for st in active], ref_mol_poses=[st.templates for st in active],
                     seeds=[st.kw.get("seed", (st.seed + rnd) if st.seed is not None else 0) for st in active],
                     sample_offsets=[st.kw.get("sample_offset", 0) for st in active], conditionings=[st.cond for st in active],
-                    return_conditioning=confidence is not None or any(want_cond))
+                    return_conditioning=confidence is not None or any(want_cond) or any(bool(st.distogram) for st in active))
         if any(nz is not None for nz in noises):
             call.update(noises=noises)
         for k in ("use_graph", "mmff_backend", "mmff_iters"):
@@ -781,7 +836,9 @@ def _redock_group(model, items, common, confidence=None) -> List[dict]:
             r = model.sample_diffusion_many([st.pbatch for st in active], **call)
         outs, conds = r if isinstance(r, tuple) else (r, [None] * len(active))
         for st, want, x, c in zip(active, want_cond, outs, conds):
-            if confidence is not None and c is not None:
+            if (confidence is not None or st.distogram) and c is not None:
                 st.conf_sz = c[2:]               # (s, z) at the group's padded token count: conditioning_s_z crops them
             st.consume(rnd, x, c if want else None)
+    for st in states:
+        st.take_distogram(model)
     return [st.result() for st in states]

@@ -16,6 +16,7 @@ relaxation branch runs (physics.py), ``conditioning=`` / ``return_conditioning=`
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, Optional
 
@@ -595,6 +596,25 @@ class PhysDock(nn.Module):
         from .loss import PhysDockLoss
         cum_loss, losses = PhysDockLoss(self.config)(outputs, feats)
         return outputs, cum_loss, losses
+
+    @torch.no_grad()
+    def predict_distogram(self, batch, conditioning=None):
+        """The distance head at inference: p_distogram fp32 [T,T,no_bins] at the system's real token count - `linear_distogram` of the
+        trunk's pair representation z, symmetrised, exactly as `forward` computes it (reference models/model.py:107-108), so that
+        given the same z the logits are bit-equal to `forward(batch)["p_distogram"]`.  `conditioning`: None runs the trunk; else the
+        (a, ap, s, z) tuple `sample_diffusion(return_conditioning=True)` returned, or its last two tensors (s, z) - only the head runs
+        (z may be at a group's padded token count, as `sample_diffusion_many` returns it)."""
+        eng = self.engine(batch["x_gt"].device)
+        if conditioning is None and eng.ws.nbytes() > self.workspace_limit_bytes:
+            self.release_workspace()
+        batch = self._prepare_batch(batch)
+        z = eng.conditioning(batch)[3] if conditioning is None else conditioning[-1]
+        c_z = z.shape[-1]
+        T = batch["target_feat"].shape[0] if conditioning is None else math.isqrt(z.numel() // c_z)
+        if z.numel() != T * T * c_z or T < batch["_T_real"]:
+            raise ValueError(f"predict_distogram: the conditioning's z has shape {tuple(z.shape)}, the batch holds {batch['_T_real']} tokens")
+        pd = eng.lin(z.reshape(T * T, c_z), "linear_distogram", T * T).reshape(T, T, -1)[:batch["_T_real"], :batch["_T_real"]]
+        return pd + pd.transpose(0, 1)
 
 
 def weighted_rigid_align(x_pred, x_gt, weights):

@@ -563,3 +563,47 @@ def pocket_grid(x, t, centre, snap, h, n, probe, lining, steps, min_enclosed, ws
         ptr(ws), ws.numel(), ptr(out["centre"]), ptr(out["ok"]), ptr(out["classes"]), ptr(out["buried"]), ptr(out["counts"]),
         ptr(out["truncated"]), ptr(out["values"]), ptr(out["atom_class"]), ptr(out["atom_buried"]), ptr(out["lining_points"]),
         ptr(out["lining_residues"]), P, A, int(L), int(R), int(N), stream()), "pd_pocket_grid")
+
+
+def _host_doubles(v):
+    """float64 values as the host array an entry point reads before it launches"""
+    v = [float(a) for a in v]
+    return (C.c_double * max(len(v), 1))(*v)
+
+
+def distogram_tables(logits, centres, contact_bin, lse, expected, p_contact):
+    """pd_distogram_tables on the current stream: logits fp32 [T,T,K] -> lse float64 [T,T], expected, p_contact fp32 [T,T]; centres: K
+    host floats (csrc/distogram_score.hip)"""
+    T, K = logits.shape[0], logits.shape[2]
+    check(_lib.init().pd_distogram_tables(ptr(logits), _host_doubles(centres), int(contact_bin), ptr(lse), ptr(expected), ptr(p_contact),
+                                          T, K, stream()), "pd_distogram_tables")
+
+
+def distogram_score(x, t, bounds_sq, contact_bin, max_expected, bins, ws, out, nL, nR, NR):
+    """pd_distogram_score + pd_distogram_reduce on the current stream: x fp32 [P,A,3]; t: the tables pb_atom, token_class, rows, row_of,
+    logits, lse, expected, p_contact on x's device; bounds_sq: K - 1 host floats; bins uint8 [P,nL,T]; ws float64 [P * NR * 8]; out: the
+    output tensors values, token_nll, n_contacts, ok"""
+    P, A = x.shape[0], x.shape[1]
+    T, K = t["logits"].shape[0], t["logits"].shape[2]
+    some = lambda v: ptr(v) if v.numel() else None
+    L_ = _lib.init()
+    check(L_.pd_distogram_score(ptr(x), ptr(t["pb_atom"]), ptr(t["token_class"]), some(t["rows"]), ptr(t["logits"]), ptr(t["lse"]),
+                                ptr(t["expected"]), ptr(t["p_contact"]), _host_doubles(bounds_sq), int(contact_bin), float(max_expected),
+                                some(bins), some(ws), ws.numel(), P, A, T, K, int(nL), int(NR), stream()), "pd_distogram_score")
+    check(L_.pd_distogram_reduce(ptr(x), ptr(t["pb_atom"]), ptr(t["token_class"]), some(t["rows"]), ptr(t["row_of"]), ptr(t["logits"]),
+                                 ptr(t["lse"]), some(bins), some(ws), ws.numel(), ptr(out["values"]), ptr(out["token_nll"]),
+                                 ptr(out["n_contacts"]), ptr(out["ok"]), P, A, T, K, int(nL), int(nR), int(NR), stream()),
+          "pd_distogram_reduce")
+
+
+def distogram_potential(x, t, centres, ws, potential, forces, abs_force, nL, nR):
+    """pd_distogram_potential on the current stream: potential fp32 [P]; forces fp32 [P,nL,3] and abs_force fp32 [P,nL], or both None;
+    ws float64 [P * nL * 5]"""
+    P, A = x.shape[0], x.shape[1]
+    T, K = t["logits"].shape[0], t["logits"].shape[2]
+    some = lambda v: ptr(v) if v is not None and v.numel() else None
+    if forces is not None and not forces.numel():                  # no ligand token: nothing to write, and the pair is both or neither
+        forces = abs_force = None
+    check(_lib.init().pd_distogram_potential(ptr(x), ptr(t["pb_atom"]), ptr(t["token_class"]), some(t["rows"]), ptr(t["logits"]),
+                                             ptr(t["lse"]), _host_doubles(centres), some(ws), ws.numel(), ptr(potential), some(forces),
+                                             some(abs_force), P, A, T, K, int(nL), int(nR), stream()), "pd_distogram_potential")

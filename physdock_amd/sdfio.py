@@ -442,7 +442,8 @@ def redock_items(out) -> Dict[str, object]:
     with the ground truth and `ranking` `ligand_rmsd` (`ranking["rmsd_all"]`) and, with `lddt_pli=`, `lddt_pli`
     (`ranking["lddt_pli_all"]`), with `clusters=` `cluster` (`clusters["labels"]`), with `conformer_rmsd=` and the ground truth
     `conformer_rmsd` (`conformer_rmsd["to_gt"]`), with `shape=` `shape_tanimoto` and `tanimoto_combo` (`shape["shape_tanimoto"]`,
-    `shape["combo"]`), with `torsions=` and the ground truth `tfd` (`torsions["to_gt"]`)"""
+    `shape["combo"]`), with `torsions=` and the ground truth `tfd` (`torsions["to_gt"]`), with `distogram=` `distogram_nll`
+    (`distogram["nll_interface"]`)"""
     n = int(out["poses"].shape[0])
     items: Dict[str, object] = {"pose": torch.arange(n, dtype=torch.int32, device=out["poses"].device)}
     if "confidence" in out:
@@ -464,6 +465,8 @@ def redock_items(out) -> Dict[str, object]:
         items["tanimoto_combo"] = out["shape"]["combo"]
     if "to_gt" in out.get("torsions", {}):
         items["tfd"] = out["torsions"]["to_gt"]
+    if "distogram" in out:
+        items["distogram_nll"] = out["distogram"]["nll_interface"]
     return items
 
 
