@@ -676,6 +676,45 @@ int pd_vina_refine(const float* x, const int* lig_idx, const unsigned char* type
                    const int* intra_atom, int n_intra, int max_iters, double grad_tol, double max_step, double* ws,
                    long long ws_numel, float* x_refined, double* energy_start, double* energy, int* iterations, int* evaluations,
                    int* status, double* moved, double* energy_trace, int P, int A, int L, int T, void* stream);
+/* pd_vina_refine with flexible receptor side chains, the move set of `vina --flex` (vina_flex.hip; ABI 11, additive;
+ * physdock_amd/flex.py builds the tables, tests/flex_refine_ref.py is the written definition).  M = L + F movable rows: rows 0 .. L-1
+ * the ligand atoms of pd_vina_refine's tables, rows L .. M-1 the flexible side-chain atoms; N = T + S torsions, the ligand's T
+ * first.  Tables: mov_idx [M] the rows' pose indices; type [A]; fixed_mask [A] 1 = a receptor atom that is not flexible; active [M]
+ * 1 = the row takes part in E (a ligand hydrogen does not); rot [N][2] (a_k, b_k) as LOCAL rows, b_k on the moving side (for a side
+ * chain a_k on the backbone side, the distal side moves); rot_mask [N][ceil(M / 32)] the rows that move with torsion k; pair_start
+ * [M + 1] / pair_atom [n_pair]: for every row the ACTIVE rows it forms a pair with (ascending LOCAL rows; every pair appears from
+ * both of its rows) - ligand pairs as pd_vina_refine's intra list, every (ligand row, flexible row), and the flexible rows more
+ * than three bonds apart; excl_start [M + 1] / excl_atom [n_excl]: for every flexible row the FIXED atoms (pose indices) within
+ * three bonds of it (empty for a ligand row).  All of it float64:
+ *   E(y)      (inter + intra) + receptor, every term the pair function of pd_vina_refine: inter over (active ligand row, fixed atom)
+ *             and (ligand row, flexible row) pairs, intra over the ligand's pairs, receptor over (flexible row, fixed atom not in
+ *             its excl list) and (flexible row, flexible row) pairs; no n_rot factor
+ *   move(y,s) s in R^(6+N): the N torsions in table order as pd_vina_refine turns them, then the rotation s[3:6] about the centroid
+ *             of the L ligand rows and the translation s[0:3], both of the ligand rows alone
+ *   ggrad     [0:3] and [3:6] sum over the ligand rows, [6+k] over the rows of torsion k
+ * pd_vina_flex_energy: energy, inter, intra, receptor [P], grad [P][M][3], ggrad [P][6+N] of the poses as they are; any output may
+ * be NULL.  pd_vina_flex_refine: pd_vina_refine's minimiser (the same code), stopping rules and outputs in the 6 + N coordinates;
+ * x_refined [P][A][3] = x with the movable rows replaced, every other row copied; inter, intra, receptor [P] (may be NULL): the parts
+ * of `energy` (one more evaluation at the end, not counted in `evaluations`); moved [P]: RMSD of the L ligand rows, moved_flex [P] (may
+ * be NULL): RMSD of the F flexible rows (0 when F == 0).  ws: pd_vina_flex_workspace_numel(P, M, N) = P ((6+N)^2 + 3 M) doubles.  One
+ * launch, one block of 256 threads per pose, 6 M doubles of LDS, no atomics, every sum in a fixed order: bit-identical from launch
+ * to launch and for a pose alone or inside a batch.  With F == S == 0 it is pd_vina_refine.  NULL required pointers, misaligned
+ * pointers, sizes < 1 (F, T, S < 0), max_iters < 0, grad_tol < 0, max_step <= 0 or a short workspace: PD_ERR_ARG; M > 1024, N >
+ * PD_VINA_REFINE_MAX_TORSIONS, A > 2^22, P > 65535: PD_ERR_UNSUPPORTED.  A rejected call writes nothing.  The indices inside the
+ * tables are the caller's to keep in range.                                                                                    */
+int pd_vina_flex_workspace_numel(int P, int M, int N);
+int pd_vina_flex_energy(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                        const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                        const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl, double* energy,
+                        double* inter, double* intra, double* receptor, double* grad, double* ggrad, int P, int A, int L, int F,
+                        int T, int S, void* stream);
+int pd_vina_flex_refine(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                        const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                        const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl, int max_iters,
+                        double grad_tol, double max_step, double* ws, long long ws_numel, float* x_refined, double* energy_start,
+                        double* energy, double* inter, double* intra, double* receptor, int* iterations, int* evaluations,
+                        int* status, double* moved, double* moved_flex, double* energy_trace, int P, int A, int L, int F, int T,
+                        int S, void* stream);
 /* Monte-Carlo global search of P poses, K independent chains each: perturb, minimise locally with the BFGS of pd_vina_refine,
  * Metropolis test, keep the best (vina_refine.hip; ABI 11, additive; the loop every docking program that carries Vina's scoring
  * function runs - here the package's own definition, tests/vina_search_ref.py, not a port of Vina's monte_carlo).  Tables, E, move

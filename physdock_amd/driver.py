@@ -160,6 +160,32 @@ def score_searched(search, refine, aligned, validity, vina) -> dict:
     return res
 
 
+def check_flex(flex, batch) -> None:
+    """redock(flex=): raise ValueError unless it is a `flex.FlexRefine` over the batch's atoms - before anything is sampled"""
+    if flex is None:
+        return
+    if not callable(getattr(flex, "refine", None)) or not hasattr(flex, "n_flex_atoms") or not hasattr(flex, "n_pose_atoms"):
+        raise ValueError("flex= takes a flex.FlexRefine of the system")
+    n = int(batch["x_gt"].shape[0])
+    if flex.n_pose_atoms != n:
+        raise ValueError(f"flex= was built over {flex.n_pose_atoms} pose atoms, the batch holds {n}")
+
+
+def score_flex_refined(flex, aligned, validity, vina, receptor_geometry) -> dict:
+    """redock(flex=): {"flex_refined": FlexRefine.refine of the kept poses} - with `validity=` also flex_refined["validity"], its check of
+    `x_refined`; with `receptor_geometry=` also flex_refined["receptor_geometry"], its check of `x_refined` (the side chains moved, so
+    the receptor is checked again); with `vina=` "order_vina_flex": the poses' ids by their score after it, best first"""
+    from .ranking import rank_by_score
+    res = {"flex_refined": flex.refine(aligned)}
+    if validity is not None:
+        res["flex_refined"]["validity"] = validity.check(res["flex_refined"]["x_refined"])
+    if receptor_geometry is not None:
+        res["flex_refined"]["receptor_geometry"] = receptor_geometry.check(res["flex_refined"]["x_refined"])
+    if vina is not None:
+        res["order_vina_flex"] = rank_by_score({"score": res["flex_refined"]["score"]})
+    return res
+
+
 def score_interactions(interactions, aligned, batch) -> dict:
     """redock(interactions=): {"interactions": InteractionFingerprint.fingerprint of the kept poses} and, when the batch carries the
     ground truth, "interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
@@ -346,7 +372,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None, pocket=None, distogram=None) -> dict:
+           torsions=None, pocket=None, distogram=None, flex=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -454,7 +480,12 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `nll_interface` (the pose the trunk's distances agree with best first) and, with `validity=`, `order_distogram_valid`;
     `clusters=PoseClusters(by="distogram")` walks `order_distogram` and needs it; with `sdf=` the records gain the item
     `distogram_nll`.  A batch without `token_id_to_pseudo_beta_atom_id` is scored on the first atom of every token.  Nothing else
-    changes."""
+    changes.
+    `flex` (a `flex.FlexRefine` of the system; one built over another number of atoms raises ValueError before anything is sampled):
+    the result gains `flex_refined` = its `refine` of the returned `poses` (the ligand and the chosen side chains minimised together:
+    `x_refined`, energies and their parts, scores before and after, `moved`, `moved_flex`, `residue_moved`), with `validity=` also
+    `flex_refined["validity"]`, with `receptor_geometry=` also `flex_refined["receptor_geometry"]` (its `check` of `x_refined`: the
+    side chains moved) and with `vina=` also `order_vina_flex`.  The returned `poses` are not replaced; nothing else changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -621,7 +652,7 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None):
+                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
@@ -634,6 +665,7 @@ class _RedockState:
         check_hydrogens(hydrogens, batch)
         check_pocket(pocket, batch)
         check_receptor_geometry(receptor_geometry, batch)
+        check_flex(flex, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
         check_redock_sdf(sdf, batch, hydrogens)
         self.pool_log = None
@@ -769,6 +801,8 @@ class _RedockState:
             out.update(score_refined(self.refine, aligned, self.validity, self.vina))
         if self.search:
             out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
+        if self.flex is not None:
+            out.update(score_flex_refined(self.flex, aligned, self.validity, self.vina, self.receptor_geometry))
         if self.conformer_rmsd is not None:
             out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, batch, ligand_idx, self.ref_mol_poses))
         if self.shape is not None:

@@ -14,8 +14,8 @@ for the ligand's internal geometry is needed, and the 6 + T coordinates replace 
 
 It stops when the largest component of the generalised gradient falls below `grad_tol` (status 0), after `max_iters` accepted steps
 (status 1), or when the line search finds no lower point (status 2).  **Two caveats.**  The weights are Vina's published ones,
-unvalidated on real complexes and not fitted to this model's poses, as for `VinaScore`; and the receptor is rigid.  Out of scope:
-receptor flexibility, Cartesian relaxation.
+unvalidated on real complexes and not fitted to this model's poses, as for `VinaScore`; and the receptor is rigid here -
+`flex.FlexRefine` runs the same minimiser with chosen side chains flexible.  Out of scope: Cartesian relaxation.
 
 Does a better pose exist within a few angstrom?  `search(x_pred)` asks the same energy with the loop every docking program that
 carries Vina's scoring function runs (kernel `pd_vina_search`, one block per (pose, chain); tests/vina_search_ref.py is the written
@@ -32,7 +32,8 @@ definition - the package's own, not a port of Vina's `monte_carlo`):
 The chains' state lives on the device between launches and the draws depend on (seed, pose id, chain, step) alone, so cutting the
 steps (`steps_per_launch`) or the poses into launches changes no bit.  Not Vina's search: cube draws instead of its ball, no Hessian
 carried over between steps, no final merging of modes (`PoseClusters.binding_modes` on `x_chains` gives the modes).  A lower Vina
-energy is not a lower RMSD.  Out of scope: grid maps, receptor flexibility, feeding the search back into the sampler.
+energy is not a lower RMSD.  Out of scope: grid maps, flexible side chains inside the search (`flex.FlexRefine` refines with them),
+feeding the search back into the sampler.
 
 `VinaRefine` holds one system's tables, built once on the host; `refine(x_pred)` and `energy(x_pred)` return device tensors and never
 synchronise.  `driver.redock(..., refine=)` reports the refinement of the kept poses; the returned poses are not replaced.
