@@ -752,6 +752,39 @@ int pd_vina_search(const float* x, const int* lig_idx, const unsigned char* type
                    int* trace_iterations, int* trace_status, int P, int K, int A, int L, int T, void* stream);
 int pd_vina_search_select(const float* x, const int* lig_idx, const float* x_chains, const double* energy_chains, int* best_chain,
                           double* energy, float* x_search, int P, int K, int A, int L, void* stream);
+/* pd_vina_search over pd_vina_flex_refine's tables: the Monte-Carlo search with flexible side chains (vina_flex.hip; ABI 11,
+ * additive; tests/flex_search_ref.py is the written definition).  Tables, E = (inter + intra) + receptor, move and the minimiser as
+ * pd_vina_flex_refine takes them, M = L + F, N = T + S, n = 6 + N; start, draws, Metropolis test and best as pd_vina_search, with
+ * two changes: the entity is e = (w0 (2 + N)) >> 32, and e == 2 + k proposes s[6+k] = pi (2 u_1 - 1) for a ligand torsion (k < T),
+ * chi_amp (2 u_1 - 1) for a side-chain torsion (T <= k < N).  The rigid part of a proposal acts on the ligand rows alone; every
+ * descent runs in all n coordinates from a fresh H = I.  With F == S == 0 it is pd_vina_search.  step0, n_steps, steps_total and the
+ * workspace as there: the chain state (H [n][n], pos, cur, best [M][3], E_cur, E_best, E_start, the counters) lives in ws between
+ * launches and a search cut into launches is the same search bit for bit.  Outputs, written by every launch: x_chains [P][K][M][3]
+ * (fp32: the movable rows of each chain's best), energy_chains, energy_start [P][K], best_step, accepted, evaluations [P][K]; the
+ * five traces of pd_vina_search (may be NULL).  ws: pd_vina_flex_search_workspace_numel(P, K, M, N) = P K (n^2 + 9 M + 8) doubles
+ * (13 320 per chain at M = 1024, n = 64; negative: the error code).  One block of 256 threads per (pose, chain), 6 M doubles of LDS,
+ * no atomics, every sum in pd_vina_flex_refine's order.
+ * pd_vina_flex_search_select (one block per pose, after the last launch, same ws): best_chain [P] = the chain with the lowest E_best
+ * in ws (the lowest index on a tie); x_search [P][A][3] = x with the movable rows of that chain's float64 best, rounded once;
+ * energy [P] and inter, intra, receptor [P] (may be NULL) from one more evaluation of it (not counted), energy == (inter + intra) +
+ * receptor; moved [P], moved_flex [P] (may be NULL): RMSD of the ligand rows and of the flexible rows from x (0 when F == 0).
+ * Errors as pd_vina_search and pd_vina_flex_refine, checked in the latter's order (chi_amp < 0 or NaN: PD_ERR_ARG); M > 1024, N >
+ * PD_VINA_REFINE_MAX_TORSIONS, A > 2^22, K > 64, P K > 65535: PD_ERR_UNSUPPORTED.  A rejected call writes nothing.             */
+long long pd_vina_flex_search_workspace_numel(int P, int K, int M, int N);
+int pd_vina_flex_search(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                        const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                        const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl, int max_iters,
+                        double grad_tol, double max_step, unsigned long long seed, int pose0, int step0, int n_steps,
+                        int steps_total, double temperature, double translate_amp, double rotate_amp, double chi_amp, double* ws,
+                        long long ws_numel, float* x_chains, double* energy_chains, double* energy_start, int* best_step,
+                        int* accepted, int* evaluations, double* trace_energy, int* trace_entity, int* trace_accept,
+                        int* trace_iterations, int* trace_status, int P, int K, int A, int L, int F, int T, int S, void* stream);
+int pd_vina_flex_search_select(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                               const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                               const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl,
+                               const double* ws, long long ws_numel, int* best_chain, double* energy, double* inter, double* intra,
+                               double* receptor, float* x_search, double* moved, double* moved_flex, int P, int K, int A, int L,
+                               int F, int T, int S, void* stream);
 /* Protein - ligand interaction fingerprint of P poses of one ligand in its receptor: which residues does a pose touch, and how?
  * (plif.hip; ABI 11, additive; per-residue fingerprints in the manner of PLIP and ProLIF, heavy atoms only - the reference has no
  * counterpart.)  Tables, built once per system (physdock_amd/interactions.py): lig_idx [L] the ligand's atoms in a pose;

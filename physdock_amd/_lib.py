@@ -261,7 +261,11 @@ def _declare(L):
     sig("pd_vina_flex_energy", p, p, p, p, p, p, p, p, p, i, p, p, i, p, p, p, p, p, p, i, i, i, i, i, i, p)
     sig("pd_vina_flex_refine", p, p, p, p, p, p, p, p, p, i, p, p, i, i, d, d, p, ll, p, p, p, p, p, p, p, p, p, p, p, p,
         i, i, i, i, i, i, p)
-    sig("pd_vina_search_workspace_numel", i, i, i, i, restype=ll)                          # ABI 11, additive (vina_refine.hip)
+    sig("pd_vina_flex_search_workspace_numel", i, i, i, i, restype=ll)                     # ABI 11, additive (vina_flex.hip)
+    sig("pd_vina_flex_search", p, p, p, p, p, p, p, p, p, i, p, p, i, i, d, d, C.c_ulonglong, i, i, i, i, d, d, d, d, p, ll,
+        p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p)
+    sig("pd_vina_flex_search_select", p, p, p, p, p, p, p, p, p, i, p, p, i, p, ll, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p)
+    sig("pd_vina_search_workspace_numel", i, i, i, i, restype=ll)                         # ABI 11, additive (vina_refine.hip)
     sig("pd_vina_search", p, p, p, p, p, p, p, p, p, i, i, d, d, C.c_ulonglong, i, i, i, i, d, d, d, p, ll, p, p, p, p, p, p,
         p, p, p, p, p, i, i, i, i, i, p)
     sig("pd_vina_search_select", p, p, p, p, p, p, p, i, i, i, i, p)

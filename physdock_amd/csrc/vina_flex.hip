@@ -30,7 +30,17 @@
 // and the block adds the four waves in order: no atomics, bit-identical from launch to launch and independent of P.  The BFGS
 // vectors live one coordinate per lane; H and the accepted conformation in the caller's workspace (per pose n^2 + 3 M doubles); the
 // conformation under evaluation and its gradient in LDS (6 M doubles: 48 KB at M = 1024, with 2 KB of static scratch).
+//
+// pd_vina_flex_search is pd_vina_search's Monte-Carlo loop over this table (tests/flex_search_ref.py is its written definition): K
+// chains per pose, each perturbing one entity per step - the ligand's translation, its rotation, one ligand torsion or one chi -
+// minimising with `descend` in all 6 + T + S coordinates, applying the Metropolis test to E = (inter + intra) + receptor and keeping
+// its best.  One block per (pose, chain), the LDS layout above; per chain the workspace holds H, the descent's conformation, cur and
+// best and the chain's scalars (n^2 + 9 M + 8 doubles), which makes a search resumable launch by launch.  The step loop is a copy of
+// vina_search_kernel's (vina_refine.hip) with the entity count 2 + T + S and the chi amplitude: the two kernels are kept apart so
+// that pd_vina_search's code object does not change.  pd_vina_flex_search_select picks the pose's best chain from the float64 `best`
+// of the workspace and evaluates it once more for the parts of E.
 #include "common.h"
+#include "philox.h"
 #include "physdock_hip.h"
 #include "vina_descend.h"
 
@@ -281,6 +291,165 @@ __global__ __launch_bounds__(NT) void vina_flex_refine_kernel(const FlexTab t, c
     }
 }
 
+// ------------------------------------------------------------------ the Monte-Carlo search (tests/flex_search_ref.py is its definition)
+constexpr int FS_SCALARS = 8;                                            // E_cur, E_best, E_start, best_step, accepted, evaluations, 2 spare
+constexpr int FS_MAX_K = 64, FS_MAX_BLOCKS = 65535;
+constexpr double FS_PI = 3.14159265358979323846;
+
+struct FlexSearchArgs {
+    unsigned long long seed;
+    int pose0, step0, n_steps, steps_total, K, T, max_iters;             // T: the ligand's torsions, the first T of the table
+    double grad_tol, max_step, temperature, translate_amp, rotate_amp, chi_amp;
+    float* x_chains; double* energy_chains; double* energy_start; int* best_step; int* accepted; int* evaluations;
+    double* trace_energy; int* trace_entity; int* trace_accept; int* trace_iterations; int* trace_status;
+};
+
+__host__ __device__ __forceinline__ long long fs_stride(int M, int N) { return (long long)(6 + N) * (6 + N) + 9ll * M + FS_SCALARS; }
+
+// One block per (pose, chain): the chain runs its steps step0 + 1 .. step0 + n_steps on its own (step 0, the start descent, when
+// step0 == 0).  Its state - cur, best [M][3], E_cur, E_best, E_start and the counters - lives in the workspace between launches, and
+// the draws depend on (seed, pose id, chain, step) alone, so a search cut into launches is the same search.  Every decision is taken
+// by all threads alike from values that are the same in every thread.
+__global__ __launch_bounds__(NT) void vina_flex_search_kernel(const FlexTab t, const float* __restrict__ x, double* __restrict__ ws,
+                                                              const FlexSearchArgs a) {
+    extern __shared__ double sm[];
+    __shared__ double red[12], cen[3], gg[64], sx[64], sh[64], sv[64];
+    const int tid = threadIdx.x, lane = tid & 63, M = t.M, A = t.A, n = 6 + t.N;
+    const int p = blockIdx.x / a.K, c = blockIdx.x - p * a.K;
+    const Lds s = {sm, sm + 3 * M, red, cen, gg, sx, sh, sv};
+    double* H = ws + (long long)blockIdx.x * fs_stride(M, t.N);
+    double* pos = H + n * n;                                             // the descent's accepted conformation
+    double* cur = pos + 3 * M;
+    double* best = cur + 3 * M;
+    double* sc = best + 3 * M;
+    const float* xp = x + (long long)p * A * 3;
+    const long long pc = blockIdx.x;
+    const Philox ph{(uint32_t)a.seed, (uint32_t)(a.seed >> 32)};
+    const uint32_t q = (uint32_t)(a.pose0 + p);
+    double e_cur = 0.0, e_best = 0.0, e_start = 0.0;
+    int best_step = 0, accepted = 0, evaluations = 0;
+    if (a.step0 > 0) {
+        e_cur = sc[0]; e_best = sc[1]; e_start = sc[2];
+        best_step = (int)sc[3]; accepted = (int)sc[4]; evaluations = (int)sc[5];
+    }
+    for (int m = a.step0 > 0 ? a.step0 + 1 : 0; m <= a.step0 + a.n_steps; ++m) {
+        int entity = 0;
+        double u4 = 0.0;
+        if (m == 0) {
+            for (int i = tid; i < 3 * M; i += NT) {
+                const double v = (double)xp[3 * t.mov_idx[i / 3] + i % 3];
+                pos[i] = v; s.y[i] = v;
+            }
+        } else {
+            uint32_t w[4] = {q, (uint32_t)c, (uint32_t)m, 0u}, w4[4] = {q, (uint32_t)c, (uint32_t)m, 1u};
+            ph.gen(w); ph.gen(w4);
+            entity = (int)(((uint64_t)w[0] * (uint64_t)(2 + t.N)) >> 32);
+            const double u1 = ((double)w[1] + 0.5) * 0x1p-32, u2 = ((double)w[2] + 0.5) * 0x1p-32, u3 = ((double)w[3] + 0.5) * 0x1p-32;
+            u4 = ((double)w4[0] + 0.5) * 0x1p-32;
+            double sl = 0.0;                                             // this lane's coordinate of the proposal s
+            if (entity < 2) {
+                const int k = lane - 3 * entity;
+                const double amp = entity == 0 ? a.translate_amp : a.rotate_amp;
+                if (k >= 0 && k < 3) sl = amp * (2.0 * (k == 0 ? u1 : (k == 1 ? u2 : u3)) - 1.0);
+            } else if (lane == 6 + entity - 2) {
+                sl = (entity - 2 < a.T ? FS_PI : a.chi_amp) * (2.0 * u1 - 1.0);   // a ligand torsion, or a chi
+            }
+            move(t, cur, s.y, cen, 1.0, sl);                             // y = move(cur, s)
+            for (int i = tid; i < 3 * M; i += NT) pos[i] = s.y[i];
+        }
+        Descent d;
+        descend(t, xp, H, pos, s, a.max_iters, a.grad_tol, a.max_step, nullptr, d);
+        evaluations += d.nev;
+        const double e_new = d.fp;
+        const bool finite = isfinite(e_new);
+        bool acc, nb;
+        if (m == 0) {
+            acc = true; nb = true;
+            e_start = e_new;
+        } else {
+            acc = finite && (e_new < e_cur || u4 < exp((e_cur - e_new) / a.temperature));
+            nb = finite && e_new < e_best;
+            if (acc) ++accepted;
+        }
+        if (acc) {
+            e_cur = e_new;
+            for (int i = tid; i < 3 * M; i += NT) cur[i] = pos[i];
+        }
+        if (nb) {
+            e_best = e_new; best_step = m;
+            for (int i = tid; i < 3 * M; i += NT) best[i] = pos[i];
+        }
+        if (tid == 0) {
+            if (a.trace_energy) a.trace_energy[pc * (a.steps_total + 1) + m] = e_new;
+            if (m > 0) {
+                const long long o = pc * a.steps_total + (m - 1);
+                if (a.trace_entity) a.trace_entity[o] = entity;
+                if (a.trace_accept) a.trace_accept[o] = acc ? 1 : 0;
+                if (a.trace_iterations) a.trace_iterations[o] = d.it;
+                if (a.trace_status) a.trace_status[o] = d.st;
+            }
+        }
+        __syncthreads();                                                 // cur is published before the next proposal reads it
+    }
+    for (int i = tid; i < 3 * M; i += NT) a.x_chains[pc * 3 * M + i] = (float)best[i];   // each thread reads what it wrote, or an earlier launch did
+    if (tid == 0) {
+        sc[0] = e_cur; sc[1] = e_best; sc[2] = e_start;
+        sc[3] = (double)best_step; sc[4] = (double)accepted; sc[5] = (double)evaluations;
+        a.energy_chains[pc] = e_best; a.energy_start[pc] = e_start;
+        a.best_step[pc] = best_step; a.accepted[pc] = accepted; a.evaluations[pc] = evaluations;
+    }
+}
+
+struct FlexSelectOut {
+    int* best_chain; double *energy, *inter, *intra, *receptor; float* x_search; double *moved, *moved_flex;
+};
+
+// One block per pose: the chain with the lowest E_best of the workspace (the lowest index on a tie), x with that chain's movable rows
+// (float64 `best`, rounded once), the parts of its energy from one more evaluation (not counted) and the two RMSDs from the pose.
+__global__ __launch_bounds__(NT) void vina_flex_search_select_kernel(const FlexTab t, const float* __restrict__ x,
+                                                                     const double* __restrict__ ws, int K, const FlexSelectOut o) {
+    extern __shared__ double sm[];
+    __shared__ double red[12];
+    const int tid = threadIdx.x, lane = tid & 63, p = blockIdx.x, L = t.L, M = t.M, A = t.A, n = 6 + t.N;
+    const long long stride = fs_stride(M, t.N), tail = (long long)n * n + 9ll * M;
+    int b = 0;
+    double e = ws[(long long)p * K * stride + tail + 1];
+    for (int c = 1; c < K; ++c) {                                        // every thread alike
+        const double v = ws[((long long)p * K + c) * stride + tail + 1];
+        if (v < e) { e = v; b = c; }
+    }
+    const double* best = ws + ((long long)p * K + b) * stride + (long long)n * n + 6ll * M;
+    double* y = sm;
+    double* gy = sm + 3 * M;
+    const float* xp = x + (long long)p * A * 3;
+    float* ob = o.x_search + (long long)p * A * 3;
+    for (int i = tid; i < 3 * A; i += NT) ob[i] = xp[i];
+    for (int i = tid; i < 3 * M; i += NT) y[i] = best[i];
+    __syncthreads();                                                     // the movable rows are overwritten after the copy
+    double ei, ea, er;
+    evaluate(t, xp, y, gy, red, ei, ea, er);
+    __syncthreads();                                                     // red is read before it is written again
+    double dl = 0.0, df = 0.0;
+    for (int i = tid; i < M; i += NT) {
+        const int a = t.mov_idx[i];
+        const double dx = y[3 * i] - (double)xp[3 * a], dy = y[3 * i + 1] - (double)xp[3 * a + 1], dz = y[3 * i + 2] - (double)xp[3 * a + 2];
+        const double q = dx * dx + dy * dy + dz * dz;
+        if (i < L) dl += q; else df += q;
+        ob[3 * a] = (float)y[3 * i]; ob[3 * a + 1] = (float)y[3 * i + 1]; ob[3 * a + 2] = (float)y[3 * i + 2];
+    }
+    dl = wave_sum(dl); df = wave_sum(df);
+    if (lane == 0) { red[tid >> 6] = dl; red[4 + (tid >> 6)] = df; }
+    __syncthreads();
+    if (tid == 0) {
+        o.best_chain[p] = b; o.energy[p] = (ei + ea) + er;
+        if (o.inter) o.inter[p] = ei;
+        if (o.intra) o.intra[p] = ea;
+        if (o.receptor) o.receptor[p] = er;
+        o.moved[p] = sqrt((((red[0] + red[1]) + red[2]) + red[3]) / (double)L);
+        if (o.moved_flex) o.moved_flex[p] = M > L ? sqrt((((red[4] + red[5]) + red[6]) + red[7]) / (double)(M - L)) : 0.0;
+    }
+}
+
 bool aligned(const void* q, uintptr_t a) { return ((uintptr_t)q & (a - 1)) == 0; }
 
 // PD_OK, or the code the tables and sizes earn
@@ -345,5 +514,66 @@ PD_EXPORT int pd_vina_flex_refine(const float* x, const int* mov_idx, const unsi
                        energy_trace};
     hipLaunchKernelGGL(vina_flex_refine_kernel, dim3(P), dim3(NT), 6 * (size_t)(L + F) * sizeof(double), (hipStream_t)stream, t, x, ws,
                        max_iters, grad_tol, max_step, o);
+    return pd_check_launch();
+}
+
+PD_EXPORT long long pd_vina_flex_search_workspace_numel(int P, int K, int M, int N) {
+    if (P <= 0 || K <= 0 || M <= 0 || N < 0) return PD_ERR_ARG;
+    if (M > VF_MAX_M || N > VF_MAX_N || K > FS_MAX_K || (long long)P * K > FS_MAX_BLOCKS) return PD_ERR_UNSUPPORTED;
+    return (long long)P * K * fs_stride(M, N);
+}
+
+PD_EXPORT int pd_vina_flex_search(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                                  const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                                  const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl,
+                                  int max_iters, double grad_tol, double max_step, unsigned long long seed, int pose0, int step0,
+                                  int n_steps, int steps_total, double temperature, double translate_amp, double rotate_amp,
+                                  double chi_amp, double* ws, long long ws_numel, float* x_chains, double* energy_chains,
+                                  double* energy_start, int* best_step, int* accepted, int* evaluations, double* trace_energy,
+                                  int* trace_entity, int* trace_accept, int* trace_iterations, int* trace_status, int P, int K, int A,
+                                  int L, int F, int T, int S, void* stream) {
+    const int rc = check_tables(x, mov_idx, type, fixed_mask, active, rot, rot_mask, pair_start, pair_atom, n_pair, excl_start, excl_atom,
+                                n_excl, P, A, L, F, T, S);
+    if (rc == PD_ERR_ARG) return rc;
+    if (!ws || !x_chains || !energy_chains || !energy_start || !best_step || !accepted || !evaluations) return PD_ERR_ARG;
+    if (max_iters < 0 || !(grad_tol >= 0.0) || !(max_step > 0.0)) return PD_ERR_ARG;
+    if (K < 1 || pose0 < 0 || step0 < 0 || n_steps < 0 || steps_total < 0 || (long long)step0 + n_steps > steps_total) return PD_ERR_ARG;
+    if (!(temperature > 0.0) || !(translate_amp >= 0.0) || !(rotate_amp >= 0.0) || !(chi_amp >= 0.0)) return PD_ERR_ARG;
+    if (!aligned(ws, 8) || !aligned(x_chains, 4) || !aligned(energy_chains, 8) || !aligned(energy_start, 8) || !aligned(best_step, 4) ||
+        !aligned(accepted, 4) || !aligned(evaluations, 4) || !aligned(trace_energy, 8) || !aligned(trace_entity, 4) ||
+        !aligned(trace_accept, 4) || !aligned(trace_iterations, 4) || !aligned(trace_status, 4))
+        return PD_ERR_ARG;
+    if (rc != PD_OK) return rc;
+    if (K > FS_MAX_K || (long long)P * K > FS_MAX_BLOCKS || (long long)pose0 + P > 0x7fffffffll) return PD_ERR_UNSUPPORTED;
+    if (ws_numel < pd_vina_flex_search_workspace_numel(P, K, L + F, T + S)) return PD_ERR_ARG;
+    const FlexTab t = {mov_idx, type, fixed_mask, active, rot, rot_mask, pair_start, pair_atom, excl_start, excl_atom, A, L, L + F, T + S};
+    const FlexSearchArgs a = {seed, pose0, step0, n_steps, steps_total, K, T, max_iters, grad_tol, max_step, temperature, translate_amp,
+                              rotate_amp, chi_amp, x_chains, energy_chains, energy_start, best_step, accepted, evaluations, trace_energy,
+                              trace_entity, trace_accept, trace_iterations, trace_status};
+    hipLaunchKernelGGL(vina_flex_search_kernel, dim3(P * K), dim3(NT), 6 * (size_t)(L + F) * sizeof(double), (hipStream_t)stream, t, x, ws,
+                       a);
+    return pd_check_launch();
+}
+
+PD_EXPORT int pd_vina_flex_search_select(const float* x, const int* mov_idx, const unsigned char* type, const unsigned char* fixed_mask,
+                                         const unsigned char* active, const int* rot, const unsigned* rot_mask, const int* pair_start,
+                                         const int* pair_atom, int n_pair, const int* excl_start, const int* excl_atom, int n_excl,
+                                         const double* ws, long long ws_numel, int* best_chain, double* energy, double* inter,
+                                         double* intra, double* receptor, float* x_search, double* moved, double* moved_flex, int P,
+                                         int K, int A, int L, int F, int T, int S, void* stream) {
+    const int rc = check_tables(x, mov_idx, type, fixed_mask, active, rot, rot_mask, pair_start, pair_atom, n_pair, excl_start, excl_atom,
+                                n_excl, P, A, L, F, T, S);
+    if (rc == PD_ERR_ARG) return rc;
+    if (!ws || !best_chain || !energy || !x_search || !moved || K < 1) return PD_ERR_ARG;
+    if (!aligned(ws, 8) || !aligned(best_chain, 4) || !aligned(energy, 8) || !aligned(inter, 8) || !aligned(intra, 8) ||
+        !aligned(receptor, 8) || !aligned(x_search, 4) || !aligned(moved, 8) || !aligned(moved_flex, 8))
+        return PD_ERR_ARG;
+    if (rc != PD_OK) return rc;
+    if (K > FS_MAX_K || (long long)P * K > FS_MAX_BLOCKS) return PD_ERR_UNSUPPORTED;
+    if (ws_numel < pd_vina_flex_search_workspace_numel(P, K, L + F, T + S)) return PD_ERR_ARG;
+    const FlexTab t = {mov_idx, type, fixed_mask, active, rot, rot_mask, pair_start, pair_atom, excl_start, excl_atom, A, L, L + F, T + S};
+    const FlexSelectOut o = {best_chain, energy, inter, intra, receptor, x_search, moved, moved_flex};
+    hipLaunchKernelGGL(vina_flex_search_select_kernel, dim3(P), dim3(NT), 6 * (size_t)(L + F) * sizeof(double), (hipStream_t)stream, t, x,
+                       ws, K, o);
     return pd_check_launch();
 }

@@ -186,6 +186,32 @@ def score_flex_refined(flex, aligned, validity, vina, receptor_geometry) -> dict
     return res
 
 
+def check_flex_search(flex_search, flex) -> None:
+    """redock(flex_search=): raise ValueError unless `flex_search` is None, False, True or a dict of `FlexRefine.search` keyword
+    arguments, and when it asks for a search without `flex=` - before anything is sampled"""
+    if flex_search is None or flex_search is False:
+        return
+    if flex_search is not True and not isinstance(flex_search, dict):
+        raise ValueError(f"flex_search= takes True or a dict of FlexRefine.search keyword arguments, got {type(flex_search).__name__}")
+    if flex is None:
+        raise ValueError("flex_search= needs flex= (the system's flex.FlexRefine)")
+
+
+def score_flex_searched(flex_search, flex, aligned, validity, vina, receptor_geometry) -> dict:
+    """redock(flex_search=): {"flex_searched": FlexRefine.search of the kept poses} - with `validity=` also flex_searched["validity"] and
+    with `receptor_geometry=` also flex_searched["receptor_geometry"], their checks of `x_search`; with `vina=`
+    "order_vina_flex_searched": the poses' ids by their score after the search, best first"""
+    from .ranking import rank_by_score
+    res = {"flex_searched": flex.search(aligned, **(flex_search if isinstance(flex_search, dict) else {}))}
+    if validity is not None:
+        res["flex_searched"]["validity"] = validity.check(res["flex_searched"]["x_search"])
+    if receptor_geometry is not None:
+        res["flex_searched"]["receptor_geometry"] = receptor_geometry.check(res["flex_searched"]["x_search"])
+    if vina is not None:
+        res["order_vina_flex_searched"] = rank_by_score({"score": res["flex_searched"]["score"]})
+    return res
+
+
 def score_interactions(interactions, aligned, batch) -> dict:
     """redock(interactions=): {"interactions": InteractionFingerprint.fingerprint of the kept poses} and, when the batch carries the
     ground truth, "interaction_recovery": its `compare` of their bits with the fingerprint of `x_gt`"""
@@ -372,7 +398,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None, pocket=None, distogram=None, flex=None) -> dict:
+           torsions=None, pocket=None, distogram=None, flex=None, flex_search=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -485,7 +511,13 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     the result gains `flex_refined` = its `refine` of the returned `poses` (the ligand and the chosen side chains minimised together:
     `x_refined`, energies and their parts, scores before and after, `moved`, `moved_flex`, `residue_moved`), with `validity=` also
     `flex_refined["validity"]`, with `receptor_geometry=` also `flex_refined["receptor_geometry"]` (its `check` of `x_refined`: the
-    side chains moved) and with `vina=` also `order_vina_flex`.  The returned `poses` are not replaced; nothing else changes."""
+    side chains moved) and with `vina=` also `order_vina_flex`.  The returned `poses` are not replaced; nothing else changes.
+    `flex_search` (True for the defaults, or a dict of `FlexRefine.search` keyword arguments; needs `flex=`, a missing one or another
+    type raises ValueError before anything is sampled): the result gains `flex_searched` = `flex.search` of the returned `poses` (the
+    Monte-Carlo search with the side chains flexible: `x_search`, `energy` and its parts, `best_chain`, every chain's best and its
+    counts, scores before and after, `moved`, `moved_flex`, `residue_moved`), with `validity=` also `flex_searched["validity"]`, with
+    `receptor_geometry=` also `flex_searched["receptor_geometry"]` (their checks of `x_search`) and with `vina=` also
+    `order_vina_flex_searched`.  The returned `poses` are not replaced; nothing else changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -652,7 +684,7 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None):
+                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None, flex_search=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
@@ -665,6 +697,7 @@ class _RedockState:
         check_hydrogens(hydrogens, batch)
         check_pocket(pocket, batch)
         check_receptor_geometry(receptor_geometry, batch)
+        check_flex_search(flex_search, flex)
         check_flex(flex, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
         check_redock_sdf(sdf, batch, hydrogens)
@@ -803,6 +836,8 @@ class _RedockState:
             out.update(score_searched(self.search, self.refine, aligned, self.validity, self.vina))
         if self.flex is not None:
             out.update(score_flex_refined(self.flex, aligned, self.validity, self.vina, self.receptor_geometry))
+        if self.flex_search:
+            out.update(score_flex_searched(self.flex_search, self.flex, aligned, self.validity, self.vina, self.receptor_geometry))
         if self.conformer_rmsd is not None:
             out.update(score_conformer_rmsd(self.conformer_rmsd, aligned, batch, ligand_idx, self.ref_mol_poses))
         if self.shape is not None:

@@ -20,14 +20,26 @@ geometry is needed.  tests/flex_refine_ref.py is the written definition.
 With no flexible residue it is `VinaRefine.refine`.  **Caveats.**  The weights are Vina's published ones, unvalidated on real
 complexes and not fitted to this model's poses; the backbone and the residues that were not selected stay rigid; there is no
 rotamer library and no torsional preference, so a chi angle goes wherever the pair energy sends it; heavy atoms only.  Limits: L + F
-<= 1024 movable atoms, T + S <= 58 torsions, 65535 poses.  Out of scope: flexible residues inside `VinaRefine.search`, backbone motion,
-repairing geometry, a neighbour prefilter of the fixed atoms, several systems per launch.
+<= 1024 movable atoms, T + S <= 58 torsions, 65535 poses.  Out of scope: backbone motion, repairing geometry, a neighbour prefilter of
+the fixed atoms, several systems per launch.
 
-`FlexRefine` is an immutable spec of one system, built once on the host; `refine(x_pred)` and `energy(x_pred)` return device tensors
-and never synchronise.  `driver.redock(..., flex=)` reports the refinement of the kept poses; the returned poses are not replaced.
+`FlexRefine.search` is the Monte-Carlo loop of `VinaRefine.search` over these coordinates (kernels `pd_vina_flex_search` and
+`pd_vina_flex_search_select`; tests/flex_search_ref.py is the written definition): `chains` chains per pose start at `refine`'s
+result; a step draws one entity uniformly among the 2 + T + S - the ligand's translation, its rotation, one ligand torsion
+(+-pi) or one chi (+-`chi_amp`) - perturbs it, minimises ligand and side chains together from a fresh H = I, and applies the
+Metropolis test to E.  The draws are `VinaRefine.search`'s (same counters), so with no flexible residue it is that search.  A local
+minimiser never crosses the barrier between two rotamers; a chi proposal does.  **Caveats of the search.**  The entity choice is
+uniform, as Vina's: a site with many chis spends most of its steps on side chains (no weight parameter); no rotamer library; the
+backbone is rigid; Vina's weights are unvalidated here.  Limits: chains <= 64; the chain state is n^2 + 9 M + 8 doubles per chain,
+so the poses are cut into launches under `workspace_bytes`.
+
+`FlexRefine` is an immutable spec of one system, built once on the host; `refine(x_pred)`, `energy(x_pred)` and `search(x_pred)`
+return device tensors and never synchronise (but for `search`'s default rotation amplitude).  `driver.redock(..., flex=)` reports
+the refinement of the kept poses, with `flex_search=` also the search; the returned poses are not replaced.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -35,7 +47,7 @@ import torch
 
 from . import ops
 from .receptor_geometry import _CHI, _Residues, _host, residue_bonds_from_names
-from .refine import MAX_TORSIONS, VinaRefine, _adjacency, _side
+from .refine import MAX_CHAINS, MAX_SEARCH_BLOCKS, MAX_TORSIONS, VinaRefine, _adjacency, _side
 from .scoring import MAX_POSES, VinaScore
 
 __all__ = ["FlexRefine", "side_chain_torsions_from_names", "MAX_MOVABLE", "SELECT_CUTOFF"]
@@ -319,15 +331,100 @@ class FlexRefine:
         ops.check(L_.pd_vina_flex_refine(*head, int(max_iters), float(grad_tol), float(max_step), ops.ptr(ws), numel,
                                          *[ops.ptr(out[k]) for k in order], ops.ptr(out.get("energy_trace")), *self._sizes(x), ops.stream()),
                   "pd_vina_flex_refine")
-        t = self.tables(x.device)
+        out["residue_moved"] = self._residue_moved(out["x_refined"], x, self.tables(x.device))
+        out["score_start"] = self.vina.score(x)["score"]
+        out["score"] = self.vina.score(out["x_refined"])["score"]
+        return out
+
+    def _residue_moved(self, x_new, x, t):
+        """[P,R_f] float64: the largest displacement of an atom of each flexible residue between the fp32 poses x and x_new"""
+        P = x.shape[0]
         fl = t["mov_idx"][self.n_atoms:].long()
-        disp = (out["x_refined"][:, fl].double() - x[:, fl].double()).pow(2).sum(-1).sqrt()         # [P,F]
+        disp = (x_new[:, fl].double() - x[:, fl].double()).pow(2).sum(-1).sqrt()                    # [P,F]
         rm = torch.zeros(P, len(self.residue_rows), device=x.device, dtype=torch.float64)
         if self.n_flex_atoms:
             rm.scatter_reduce_(1, t["residue_of_row"][None].expand(P, -1), disp, "amax", include_self=True)
-        out["residue_moved"] = rm
+        return rm
+
+    def search(self, x_pred: torch.Tensor, chains: int = 8, steps: int = 20, seed: int = 0, temperature: float = 1.2,
+               translate_amp: float = 2.0, rotate_amp: Optional[float] = None, chi_amp: float = math.pi, max_iters: int = 20,
+               grad_tol: float = 1e-4, max_step: float = 1.0, steps_per_launch: Optional[int] = None, pose0: int = 0, trace: bool = False,
+               workspace_bytes: int = 256 << 20) -> Dict[str, torch.Tensor]:
+        """Monte-Carlo search of every pose with the side chains flexible (module docstring; tests/flex_search_ref.py).  x_pred [P,A,3]
+        (device) -> dict of device tensors: x_search [P,A,3] (fp32; the movable rows of the pose's best chain, every other row copied),
+        energy [P] = (inter + intra) + receptor [P] (float64), best_chain [P] (int32), x_chains [P,K,A,3] (every chain's best as a full
+        pose), energy_chains, energy_start [P,K] (float64; the latter is `refine`'s energy), best_step, accepted, evaluations [P,K]
+        (int32), moved, moved_flex [P] (float64: RMSD of the ligand / the flexible atoms from x_pred to x_search, A), residue_moved
+        [P,R_f], score_start / score [P] as `refine` reports them; with `trace=True` trace_energy [P,K,steps+1] and trace_entity,
+        trace_accept, trace_iterations, trace_status [P,K,steps].  The pose id of x_pred[p] is pose0 + p.  `chi_amp` (rad): the
+        amplitude of a side-chain proposal.  `rotate_amp=None`: `VinaRefine.default_rotate_amp` (one number read back; nothing else
+        is).  `steps_per_launch` cuts the steps into launches, `workspace_bytes` the poses (at least one pose per launch, at most
+        65535 // chains): neither changes a bit."""
+        chains, steps, pose0 = int(chains), int(steps), int(pose0)
+        if int(max_iters) < 0 or not float(grad_tol) >= 0 or not float(max_step) > 0:
+            raise ValueError(f"FlexRefine.search: max_iters={max_iters}, grad_tol={grad_tol}, max_step={max_step}")
+        if not 1 <= chains <= MAX_CHAINS or steps < 0 or pose0 < 0 or not float(temperature) > 0 or not float(translate_amp) >= 0:
+            raise ValueError(f"FlexRefine.search: chains={chains} (1 .. {MAX_CHAINS}), steps={steps}, pose0={pose0}, temperature={temperature}, "
+                             f"translate_amp={translate_amp}")
+        if (rotate_amp is not None and not float(rotate_amp) >= 0) or not float(chi_amp) >= 0:
+            raise ValueError(f"FlexRefine.search: rotate_amp={rotate_amp}, chi_amp={chi_amp}")
+        if steps_per_launch is not None and int(steps_per_launch) < 1:
+            raise ValueError(f"FlexRefine.search: steps_per_launch={steps_per_launch}")
+        if int(workspace_bytes) < 1:
+            raise ValueError(f"FlexRefine.search: workspace_bytes={workspace_bytes}")
+        x, head = self._poses(x_pred, "search")
+        if rotate_amp is None:
+            rotate_amp = VinaRefine.default_rotate_amp(self, x, translate_amp)
+        L_ = ops._lib.init()
+        P, A, M, N, K = x.shape[0], x.shape[1], self.n_movable, self.n_torsions, chains
+        sizes = lambda n: (n, K) + self._sizes(x)[1:]
+        dev = x.device
+        f64 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.float64)
+        i32 = lambda *shape: torch.empty(*shape, device=dev, dtype=torch.int32)
+        raw = {"x_chains": torch.empty(P, K, M, 3, device=dev), "energy_chains": f64(P, K), "energy_start": f64(P, K), "best_step": i32(P, K),
+               "accepted": i32(P, K), "evaluations": i32(P, K)}
+        tr = {}
+        if trace:
+            tr = {"trace_energy": f64(P, K, steps + 1), "trace_entity": i32(P, K, steps), "trace_accept": i32(P, K, steps),
+                  "trace_iterations": i32(P, K, steps), "trace_status": i32(P, K, steps)}
+        out = {"x_search": torch.empty_like(x), "energy": f64(P), "inter": f64(P), "intra": f64(P), "receptor": f64(P), "best_chain": i32(P),
+               "moved": f64(P), "moved_flex": f64(P)}
+        per_chain = L_.pd_vina_flex_search_workspace_numel(1, 1, M, N)
+        ops.check(min(per_chain, 0), "pd_vina_flex_search_workspace_numel")
+        cap = max(min(int(workspace_bytes) // (8 * per_chain * K), MAX_SEARCH_BLOCKS // K), 1)
+        per = steps if steps_per_launch is None else int(steps_per_launch)
+        order = ("x_chains", "energy_chains", "energy_start", "best_step", "accepted", "evaluations")
+        torder = ("trace_energy", "trace_entity", "trace_accept", "trace_iterations", "trace_status")
+        sel = ("best_chain", "energy", "inter", "intra", "receptor", "x_search", "moved", "moved_flex")
+        ws = f64(per_chain * K * min(cap, P))
+        for a in range(0, P, cap):
+            b = min(a + cap, P)
+            n = b - a
+            numel = per_chain * K * n
+            hd = (ops.ptr(x[a:b]),) + head[1:]
+            step0 = 0
+            while True:
+                ns = min(per, steps - step0)
+                ops.check(L_.pd_vina_flex_search(*hd, int(max_iters), float(grad_tol), float(max_step), int(seed) & 0xFFFFFFFFFFFFFFFF, pose0 + a,
+                                                 step0, ns, steps, float(temperature), float(translate_amp), float(rotate_amp), float(chi_amp),
+                                                 ops.ptr(ws), numel, *[ops.ptr(raw[k][a:b]) for k in order],
+                                                 *[ops.ptr(tr[k][a:b]) if trace else None for k in torder], *sizes(n), ops.stream()),
+                          "pd_vina_flex_search")
+                step0 += ns
+                if step0 >= steps:
+                    break
+            ops.check(L_.pd_vina_flex_search_select(*hd, ops.ptr(ws), numel, *[ops.ptr(out[k][a:b]) for k in sel], *sizes(n), ops.stream()),
+                      "pd_vina_flex_search_select")
+        t = self.tables(dev)
+        mov = t["mov_idx"].long()
+        full = x[:, None].expand(P, K, A, 3).contiguous()
+        full[:, :, mov] = raw["x_chains"]
+        out["x_chains"] = full
+        out.update({k: raw[k] for k in order[1:]})
+        out["residue_moved"] = self._residue_moved(out["x_search"], x, t)
         out["score_start"] = self.vina.score(x)["score"]
-        out["score"] = self.vina.score(out["x_refined"])["score"]
+        out["score"] = self.vina.score(out["x_search"])["score"]
+        out.update(tr)
         return out
 
     def describe(self) -> List[str]:

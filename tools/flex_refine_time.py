@@ -26,14 +26,8 @@ from physdock_amd.refine import VinaRefine  # noqa: E402
 from physdock_amd.scoring import VinaScore  # noqa: E402
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--calls", type=int, default=5)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--max-iters", type=int, default=50)
-    args = ap.parse_args()
-    n_pose, Lg, A = 64, 32, 2048
+def system(n_pose=64, Lg=32, A=2048):
+    """the timed system: (VinaScore, VinaRefine, poses [n_pose,A,3] on the device, ten chains of five receptor atoms lining the pocket)"""
     rng = np.random.default_rng(64)
     side = 13
     grid = np.stack(np.meshgrid(*[np.arange(side)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(np.float64)
@@ -63,6 +57,18 @@ def main():
     lining = rec[(vina.rec_mask[rec] > 0)]
     lining = lining[np.argsort(np.sqrt(((x[0, lining][:, None] - y0[None]) ** 2).sum(-1)).min(1), kind="stable")]
     chains = [lining[5 * k:5 * k + 5].tolist() for k in range(10)]
+    return vina, r, xd, chains
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--max-iters", type=int, default=50)
+    args = ap.parse_args()
+    n_pose, Lg, A = 64, 32, 2048
+    vina, r, xd, chains = system(n_pose, Lg, A)
     lines = []
     base = per_call_us(lambda: r.refine(xd, max_iters=args.max_iters), args.calls, args.windows)
     out = r.refine(xd, max_iters=args.max_iters)
