@@ -1319,6 +1319,42 @@ int pd_distogram_potential(const float* x, const int* pb_atom, const unsigned ch
                            const double* lse, const double* centres, double* ws, long long ws_numel, float* potential, float* forces,
                            float* abs_force, int P, int A, int T, int no_bins, int n_ligand_rows, int n_receptor_tokens, void* stream);
 
+/* ---- lDDT of the ligand pocket and pocket RMSDs (pocket_accuracy.hip; additive exports of ABI 11) ----------------------------
+ * Did the model draw the right pocket?  x fp32 [P][A][3] against one ground truth; the package's own definition (not OpenStructure's
+ * bytes): tests/pocket_accuracy_ref.py and physdock_amd/pocket_accuracy.py, which builds the tables.  Float64 from the fp32
+ * coordinates, integer counts, fixed-order sums, no atomics: a pose's values are bit-identical whatever the batch.  Tables on the
+ * DEVICE: the Np pocket atoms by (pocket residue, atom) as patom int32 [Np] (pose atom), patom_partner int32 [Np] (the pose atom whose
+ * name it may exchange with; itself for none), patom_kind uint8 [Np] (bit 0: CA, bit 1: N / CA / C / O), patom_ref double [Np][3] (the
+ * reference coordinates); res_atom_start int32 [Rp+1] (the pocket atoms of each of the Rp pocket residues); the pairs in CSR form over
+ * the pocket atoms, pair_start int32 [Np+1], pair_atom int32 (pose atom, ascending per row), pair_dist double; atom_partner int32 [A]
+ * (as patom_partner, per pose atom) and atom_slot int32 [A] (the pocket residue 0 .. Rp-1 of a pose atom, -1 outside the pocket);
+ * named int32 [n_named], every pose atom a table names, ascending.  The caller guarantees that every index lies inside its array.
+ * pd_pocket_accuracy : a pair is conserved at t when | |p_i - p_j| - pair_dist | < thr_t.  Per pocket residue with partners the
+ *                      conserved (pair, threshold) entries of its rows are counted as given and with its partners exchanged in the
+ *                      pose; swapped int32 [P][Rp] = 1 where the second count is strictly greater.  Then, with all chosen exchanges
+ *                      applied on both sides of every pair: conserved int32 [P][4], lddt_lp float [P] = sum conserved / (4 n_pairs),
+ *                      residue_lddt float [P][Rp] (both 0 without pairs).  Fit: Horn's quaternion (proper rotations only) of the pose's
+ *                      CA atoms on the reference's: quat double [P][4] (w, x, y, z; first non-zero component positive) and t double
+ *                      [P][3] with ref ~ R(quat) x + t; rmsd float [P][3] = CA, backbone and all pocket atoms under that transform,
+ *                      residue_rmsd float [P][Rp]; exchanges applied.  fit_ok uint8 [P] = 0 with NaN RMSDs and transform for fewer than
+ *                      3 CA atoms or a CA set (either side) whose scatter matrix has its middle eigenvalue <= 1e-8 of the largest.
+ *                      ok uint8 [P] = 0 for a non-finite coordinate at a named atom: NaN floats, zero integers, fit_ok 0.
+ *                      ws: pd_pocket_accuracy_workspace_numel(P, Rp) = 4 P Rp ints, 16-byte aligned.  A row of pairs is walked
+ *                      PD_POCKET_ACCURACY_TILE at a time.
+ * A <= 4096, Rp <= 1024, P <= 65535: else PD_ERR_UNSUPPORTED.  A NULL required pointer (pair_atom / pair_dist may be NULL when
+ * n_pairs == 0), a misaligned pointer, a size < 1, Rp > Np, n_named < Np, Np or n_named > A, a threshold <= 0 or a short workspace:
+ * PD_ERR_ARG.  A rejected call launches nothing.                                                                                   */
+#define PD_POCKET_ACCURACY_MAX_ATOMS 4096
+#define PD_POCKET_ACCURACY_MAX_RESIDUES 1024
+#define PD_POCKET_ACCURACY_TILE 256
+int pd_pocket_accuracy_workspace_numel(int P, int Rp);
+int pd_pocket_accuracy(const float* x, const int* patom, const int* patom_partner, const unsigned char* patom_kind,
+                       const double* patom_ref, const int* res_atom_start, const int* pair_start, const int* pair_atom,
+                       const double* pair_dist, const int* atom_partner, const int* atom_slot, const int* named, double thr0,
+                       double thr1, double thr2, double thr3, int* ws, long long ws_numel, float* lddt_lp, float* residue_lddt,
+                       int* conserved, int* swapped, float* rmsd, float* residue_rmsd, double* quat, double* t, unsigned char* ok,
+                       unsigned char* fit_ok, int P, int A, int Np, int Rp, int n_pairs, int n_named, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

@@ -28,6 +28,7 @@ from .interactions import InteractionFingerprint  # noqa: F401  (per-residue int
 from .ring_interactions import RingInteractions  # noqa: F401  (pi-stacking, pi-cation and halogen bonds of every pose; csrc/plif_rings.hip)
 from .hydrogens import Hydrogens  # noqa: F401  (riding hydrogens of every pose and angle-tested hydrogen bonds; csrc/hydrogens.hip)
 from .receptor_geometry import ReceptorGeometry  # noqa: F401  (stereochemistry checks of every pose's receptor; csrc/receptor_geometry.hip)
+from .pocket_accuracy import PocketAccuracy, swap_table_from_names  # noqa: F401  (lDDT-LP and pocket RMSD of every pose against the ground truth; csrc/pocket_accuracy.hip)
 from .flex import FlexRefine, side_chain_torsions_from_names  # noqa: F401  (the same with flexible side chains; csrc/vina_flex.hip)
 from .refine import VinaRefine  # noqa: F401  (rigid-body and torsion refinement of every pose in its receptor; csrc/vina_refine.hip)
 from .pocket import PocketGrid  # noqa: F401  (pocket volume, enclosure and lining residues of every pose on a lattice; csrc/pocket.hip)

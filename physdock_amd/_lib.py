@@ -306,6 +306,8 @@ def _declare(L):
     sig("pd_distogram_score", p, p, p, p, p, p, p, p, hd, i, f, p, p, ll, i, i, i, i, i, i, p)
     sig("pd_distogram_reduce", p, p, p, p, p, p, p, p, p, ll, p, p, p, p, i, i, i, i, i, i, i, p)
     sig("pd_distogram_potential", p, p, p, p, p, p, hd, p, ll, p, p, p, i, i, i, i, i, i, p)
+    sig("pd_pocket_accuracy_workspace_numel", i, i)                                          # ABI 11, additive (pocket_accuracy.hip)
+    sig("pd_pocket_accuracy", p, p, p, p, p, p, p, p, p, p, p, p, d, d, d, d, p, ll, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, p)
 
 
 def ptr(t):

@@ -22,6 +22,7 @@
 // and only when quat is asked for.  TJ is 64, 16, 4 or 1: the largest with G >= M (so that M = 1 .. 4 run 64 columns per block)
 // whose tile fits 64 KiB of LDS.  A value depends on its own two structures and the table only, never on na, nb, TJ or the launch.
 #include "common.h"
+#include "geom3.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -30,7 +31,6 @@ constexpr int BF_MAX_L = 1024;          // ligand atoms, as pd_sym_rmsd: two str
 constexpr int BF_MAX_M = 65535;         // table rows: an unsigned short entry addresses an atom
 constexpr int BF_MAX_N = 65535;         // rows / columns: blockIdx.y
 constexpr int BF_LDS_BYTES = 65536 - 256;
-constexpr int BF_MAX_SWEEPS = 50;       // cyclic Jacobi converges quadratically: a 4x4 is done after six to eight
 
 typedef pd_u64 u64;
 
@@ -41,93 +41,6 @@ inline int bf_tile(int L, int M) {
     int tj = M <= 4 ? 64 : (M <= 16 ? 16 : (M <= 64 ? 4 : 1));
     while (tj > 1 && (long long)(tj + 1) * bf_lds_stride(L) * 8 > BF_LDS_BYTES) tj /= 4;
     return tj;
-}
-
-// One Jacobi rotation in the (P, Q) plane of the symmetric 4x4 matrix a (upper triangle) and, with VEC, of the eigenvector matrix v:
-// the formulas of Rutishauser / Numerical Recipes.  Compile-time indices only: everything stays in registers.
-template <int P, int Q, bool VEC>
-__host__ __device__ __forceinline__ void bf_rotate(double (&a)[4][4], double (&v)[4][4], int sweep) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    const double g = 100.0 * fabs(apq);
-    if (sweep > 3 && fabs(a[P][P]) + g == fabs(a[P][P]) && fabs(a[Q][Q]) + g == fabs(a[Q][Q])) {
-        a[P][Q] = 0.0;
-        return;
-    }
-    const double h = a[Q][Q] - a[P][P];
-    double t;
-    if (fabs(h) + g == fabs(h)) {
-        t = apq / h;
-    } else {
-        const double theta = 0.5 * h / apq;
-        t = 1.0 / (fabs(theta) + sqrt(1.0 + theta * theta));
-        if (theta < 0.0) t = -t;
-    }
-    const double c = 1.0 / sqrt(1.0 + t * t), s = t * c, tau = s / (1.0 + c);
-    a[P][P] -= t * apq;
-    a[Q][Q] += t * apq;
-    a[P][Q] = 0.0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        if (r == P || r == Q) continue;
-        double& arp = r < P ? a[r][P] : a[P][r];
-        double& arq = r < Q ? a[r][Q] : a[Q][r];
-        const double x = arp, y = arq;
-        arp = x - s * (y + x * tau);
-        arq = y + s * (x - y * tau);
-    }
-    if (VEC) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double x = v[r][P], y = v[r][Q];
-            v[r][P] = x - s * (y + x * tau);
-            v[r][Q] = y + s * (x - y * tau);
-        }
-    }
-}
-
-// lambda_max of Horn's matrix N of the covariance S[3 x + y] = sum_k a[k][x] b[k][y]; with VEC also its unit eigenvector q = (w, x, y,
-// z), first non-zero component positive (the first of equal eigenvalues)
-template <bool VEC>
-__host__ __device__ inline double bf_lambda_max(const double (&S)[9], double* q) {
-    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
-    double a[4][4], v[4][4];
-    a[0][0] = Sxx + Syy + Szz; a[0][1] = Syz - Szy;       a[0][2] = Szx - Sxz;        a[0][3] = Sxy - Syx;
-    a[1][1] = Sxx - Syy - Szz; a[1][2] = Sxy + Syx;       a[1][3] = Szx + Sxz;
-    a[2][2] = -Sxx + Syy - Szz; a[2][3] = Syz + Szy;
-    a[3][3] = -Sxx - Syy + Szz;
-    a[1][0] = a[2][0] = a[2][1] = a[3][0] = a[3][1] = a[3][2] = 0.0;      // (the lower triangle is never read)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[r][c] = r == c ? 1.0 : 0.0;
-#pragma unroll 1
-    for (int sweep = 0; sweep < BF_MAX_SWEEPS; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[0][3]) + fabs(a[1][2]) + fabs(a[1][3]) + fabs(a[2][3]);
-        if (off == 0.0) break;
-        bf_rotate<0, 1, VEC>(a, v, sweep);
-        bf_rotate<0, 2, VEC>(a, v, sweep);
-        bf_rotate<0, 3, VEC>(a, v, sweep);
-        bf_rotate<1, 2, VEC>(a, v, sweep);
-        bf_rotate<1, 3, VEC>(a, v, sweep);
-        bf_rotate<2, 3, VEC>(a, v, sweep);
-    }
-    double lam = a[0][0];
-    int best = 0;
-    if (a[1][1] > lam) { lam = a[1][1]; best = 1; }
-    if (a[2][2] > lam) { lam = a[2][2]; best = 2; }
-    if (a[3][3] > lam) { lam = a[3][3]; best = 3; }
-    if (VEC) {
-        double w = 0.0, x = 0.0, y = 0.0, z = 0.0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (c == best) { w = v[0][c]; x = v[1][c]; y = v[2][c]; z = v[3][c]; }
-        const double inv = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-        const double lead = w != 0.0 ? w : (x != 0.0 ? x : (y != 0.0 ? y : z));
-        const double sgn = lead < 0.0 ? -inv : inv;
-        q[0] = w * sgn; q[1] = x * sgn; q[2] = y * sgn; q[3] = z * sgn;
-    }
-    return lam;
 }
 
 // the nine covariance sums of row a against column b seen through table row m, k ascending
@@ -234,7 +147,7 @@ __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restr
         for (int m = g; m < M; m += G) {
             double S[9];
             bf_covariance(sm, b, perms_t, L, M, m, S);
-            const double lam = bf_lambda_max<false>(S, nullptr);
+            const double lam = horn_lambda_max<false>(S, nullptr);
             double msd = (Gsum - 2.0 * lam) / (double)L;
             if (!(msd > 0.0)) msd = 0.0;
             pd_dkey k = {(u64)__double_as_longlong(msd), (unsigned)m};
@@ -273,7 +186,7 @@ __global__ __launch_bounds__(256) void bestfit_rmsd_kernel(const double* __restr
     if (quat) {
         double S[9], q[4];
         bf_covariance(sm, b, perms_t, L, M, (int)best.m, S);
-        bf_lambda_max<true>(S, q);
+        horn_lambda_max<true>(S, q);
         quat[4 * o] = q[0]; quat[4 * o + 1] = q[1]; quat[4 * o + 2] = q[2]; quat[4 * o + 3] = q[3];
     }
 }

@@ -273,6 +273,20 @@ def score_receptor_geometry(receptor_geometry, aligned, batch, out) -> dict:
     return {"receptor_geometry": res}
 
 
+def check_pocket_accuracy(pocket_accuracy, batch) -> None:
+    """redock(pocket_accuracy=): raise ValueError unless it is a `pocket_accuracy.PocketAccuracy` over the batch's atoms and the batch
+    carries the ground truth"""
+    if pocket_accuracy is None:
+        return
+    if not callable(getattr(pocket_accuracy, "score", None)) or not hasattr(pocket_accuracy, "n_pocket_residues"):
+        raise ValueError("pocket_accuracy= takes a pocket_accuracy.PocketAccuracy of the system")
+    if batch.get("x_gt") is None:
+        raise ValueError("pocket_accuracy= needs the ground truth (x_gt) in the batch")
+    n = int(batch["x_gt"].shape[0])
+    if pocket_accuracy.n_pose_atoms != n:
+        raise ValueError(f"pocket_accuracy= was built over {pocket_accuracy.n_pose_atoms} pose atoms, the batch holds {n}")
+
+
 def check_conformer_rmsd(conformer_rmsd, batch) -> None:
     """redock(conformer_rmsd=): raise ValueError unless it is a `bestfit.BestFitRmsd` over the batch's ligand atoms"""
     if conformer_rmsd is None:
@@ -398,7 +412,7 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None, pocket=None, distogram=None, flex=None, flex_search=None) -> dict:
+           torsions=None, pocket=None, distogram=None, flex=None, flex_search=None, pocket_accuracy=None) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -517,7 +531,12 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     Monte-Carlo search with the side chains flexible: `x_search`, `energy` and its parts, `best_chain`, every chain's best and its
     counts, scores before and after, `moved`, `moved_flex`, `residue_moved`), with `validity=` also `flex_searched["validity"]`, with
     `receptor_geometry=` also `flex_searched["receptor_geometry"]` (their checks of `x_search`) and with `vina=` also
-    `order_vina_flex_searched`.  The returned `poses` are not replaced; nothing else changes."""
+    `order_vina_flex_searched`.  The returned `poses` are not replaced; nothing else changes.
+    `pocket_accuracy` (a `pocket_accuracy.PocketAccuracy` of the system; one built over another number of atoms, or a batch without
+    `x_gt`, raises ValueError before anything is sampled): the result gains `pocket_accuracy` = its `score` of the returned `poses` (the
+    lDDT of the ligand pocket with the naming swaps, per residue too, and the pocket's CA / backbone / heavy-atom RMSD after the
+    superposition of its CA atoms, with the transform); with `sdf=` the records gain the items `lddt_lp` and `pocket_ca_rmsd`.  Nothing
+    else changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -684,7 +703,8 @@ class _RedockState:
                  steps=40, karras_noise_schedule_power=1000, confidence=None, ligand_symmetry=None, validity=None,
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
-                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None, flex_search=None):
+                 conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None, flex_search=None,
+                 pocket_accuracy=None):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
@@ -697,6 +717,7 @@ class _RedockState:
         check_hydrogens(hydrogens, batch)
         check_pocket(pocket, batch)
         check_receptor_geometry(receptor_geometry, batch)
+        check_pocket_accuracy(pocket_accuracy, batch)
         check_flex_search(flex_search, flex)
         check_flex(flex, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
@@ -824,6 +845,8 @@ class _RedockState:
             out.update(score_hydrogens(self.hydrogens, aligned, batch))
         if self.receptor_geometry is not None:
             out.update(score_receptor_geometry(self.receptor_geometry, aligned, batch, out))
+        if self.pocket_accuracy is not None:
+            out["pocket_accuracy"] = self.pocket_accuracy.score(aligned)
         if self.pool_log is not None:
             out["conformers"] = self.pool_log
         if self.surface is not None:

@@ -443,7 +443,8 @@ def redock_items(out) -> Dict[str, object]:
     (`ranking["lddt_pli_all"]`), with `clusters=` `cluster` (`clusters["labels"]`), with `conformer_rmsd=` and the ground truth
     `conformer_rmsd` (`conformer_rmsd["to_gt"]`), with `shape=` `shape_tanimoto` and `tanimoto_combo` (`shape["shape_tanimoto"]`,
     `shape["combo"]`), with `torsions=` and the ground truth `tfd` (`torsions["to_gt"]`), with `distogram=` `distogram_nll`
-    (`distogram["nll_interface"]`)"""
+    (`distogram["nll_interface"]`), with `pocket_accuracy=` `lddt_lp` and `pocket_ca_rmsd` (`pocket_accuracy["lddt_lp"]`,
+    `pocket_accuracy["ca_rmsd"]`)"""
     n = int(out["poses"].shape[0])
     items: Dict[str, object] = {"pose": torch.arange(n, dtype=torch.int32, device=out["poses"].device)}
     if "confidence" in out:
@@ -467,6 +468,9 @@ def redock_items(out) -> Dict[str, object]:
         items["tfd"] = out["torsions"]["to_gt"]
     if "distogram" in out:
         items["distogram_nll"] = out["distogram"]["nll_interface"]
+    if "pocket_accuracy" in out:
+        items["lddt_lp"] = out["pocket_accuracy"]["lddt_lp"]
+        items["pocket_ca_rmsd"] = out["pocket_accuracy"]["ca_rmsd"].contiguous()
     return items
 
 
