@@ -1355,6 +1355,27 @@ int pd_pocket_accuracy(const float* x, const int* patom, const int* patom_partne
                        int* conserved, int* swapped, float* rmsd, float* residue_rmsd, double* quat, double* t, unsigned char* ok,
                        unsigned char* fit_ok, int P, int A, int Np, int Rp, int n_pairs, int n_named, void* stream);
 
+/* ---- ligand features from the molecular graph (ligand_features.hip; additive export of ABI 11) ---------------------------------
+ * From a library of G ligand graphs to the reference's ligand feature blocks in one launch (the reference: RDKit on the host,
+ * PhysDock/data/tools/rdkit.py get_features_from_ref_mol and feature_loader.py:327-352).  The package's own definition, not RDKit's
+ * bytes: tests/ligand_features_ref.py and physdock_amd/ligand.py, which builds the tables.  Tables on the DEVICE, CSR over the
+ * ligands: atom_start, bond_start int32 [G+1], pair_start int64 [G+1] (prefix sums of L^2); atoms int32 [n_atoms][4] = (atomic number,
+ * formal charge, hydrogen count, flags: bit 0 written aromatic, bits 1-2 chirality 0 none / 1 @ / 2 @@); bonds int32 [n_bonds][4] =
+ * (i, j local to the ligand, twice the bond order, 0).  Outputs: atom_table int8 [n_atoms][16] = ref_charge, ref_element (Z - 1),
+ * ref_is_aromatic, ref_degree, ref_hybridization, ref_implicit_valence, ref_chirality, ref_in_ring_of_3 .. 8, then zeros; pair_table
+ * int8 [n_pairs][8] = d_token, token_bonds, bond_type, bond_as_double, bond_in_ring, bond_is_conjugated, bond_is_aromatic, zero;
+ * ref_feat float [n_atoms][167] (columns 0 .. 2, ref_pos, are written as zero) and rel_tok_feat float [n_pairs][42] in the reference's
+ * column order.  One block per ligand, integers only, no atomics: a ligand's bits do not depend on the library around it.
+ * Every ligand needs 1 <= L <= PD_LIGAND_FEATURES_MAX_ATOMS atoms and at most PD_LIGAND_FEATURES_MAX_BONDS bonds; one whose rows leave
+ * the arrays is not written and a bond that leaves its ligand is skipped.  A NULL pointer (bonds may be NULL when n_bonds == 0), a
+ * misaligned pointer, G < 1, n_atoms < G, n_pairs < n_atoms: PD_ERR_ARG; G > 65535 or sizes beyond G ligands of the largest size:
+ * PD_ERR_UNSUPPORTED.  A rejected call launches nothing.                                                                          */
+#define PD_LIGAND_FEATURES_MAX_ATOMS 128
+#define PD_LIGAND_FEATURES_MAX_BONDS 512
+int pd_ligand_features(const int* atom_start, const int* bond_start, const long long* pair_start, const int* atoms, const int* bonds,
+                       signed char* atom_table, signed char* pair_table, float* ref_feat, float* rel_tok_feat, int G, int n_atoms,
+                       int n_bonds, long long n_pairs, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

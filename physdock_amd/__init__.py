@@ -37,3 +37,5 @@ from .surface import BuriedSurface  # noqa: F401  (ligand burial and interface a
 from .clustering import PoseClusters  # noqa: F401  (binding modes of the poses: greedy leader clustering on the device; csrc/cluster.hip)
 from .conformers import ConformerEnsemble  # noqa: F401  (distance-geometry conformers of a ligand, the template pool; csrc/conformers.hip)
 from .sdfio import SdfTemplate, parse_sdf  # noqa: F401  (ligand poses as SD file records, formatted on the device, and their reader; csrc/sdf.hip)
+from .smiles import parse_smiles  # noqa: F401  (a SMILES reader on the host, without a dependency)
+from .ligand import Ligand, LigandLibrary  # noqa: F401  (ligands from SMILES to the reference's ligand feature blocks and a reference conformer; csrc/ligand_features.hip)

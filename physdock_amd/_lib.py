@@ -308,12 +308,13 @@ def _declare(L):
     sig("pd_distogram_potential", p, p, p, p, p, p, hd, p, ll, p, p, p, i, i, i, i, i, i, p)
     sig("pd_pocket_accuracy_workspace_numel", i, i)                                          # ABI 11, additive (pocket_accuracy.hip)
     sig("pd_pocket_accuracy", p, p, p, p, p, p, p, p, p, p, p, p, d, d, d, d, p, ll, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, p)
+    sig("pd_ligand_features", p, p, p, p, p, p, p, p, p, i, i, i, ll, p)                     # ABI 11, additive (ligand_features.hip)
 
 
 def ptr(t):
     if t is None:
         return None
-    assert t.is_cuda and t.dtype in (torch.float32, torch.float64, torch.int32, torch.int64, torch.int16, torch.uint8, torch.bfloat16, torch.float16), (t.device, t.dtype)
+    assert t.is_cuda and t.dtype in (torch.float32, torch.float64, torch.int32, torch.int64, torch.int16, torch.uint8, torch.int8, torch.bfloat16, torch.float16), (t.device, t.dtype)
     return t.data_ptr()
 
 

@@ -27,6 +27,8 @@ an MMFF clean-up, macrocycle handling, hydrogens, parity with RDKit.  Limits: L 
 prune_rms=)` drops near-duplicates by their best-fit RMSD and `coverage(poses, x_ref)` measures whether the pool contains a reference
 conformer (`bestfit.BestFitRmsd`).
 `driver.redock(..., physics_correction=True, conformers=)` takes the pool from `embed` when no `ref_mol_poses` is given.
+`ideal_bounds(ligand)` builds the same kind of table without a reference conformer, from ideal bond lengths and angles: the bounds
+behind `ligand.Ligand.embed_reference`.
 """
 from __future__ import annotations
 
@@ -39,7 +41,7 @@ from . import ops
 from .scoring import _bond_list, _host
 from .validity import DEFAULT_RADIUS, VDW_RADII
 
-__all__ = ["ConformerEnsemble", "bounds_from_bonds", "smooth_bounds", "MAX_ATOMS", "MAX_CENTRES", "MAX_CONFORMERS", "STATUS", "STAGES"]
+__all__ = ["ConformerEnsemble", "bounds_from_bonds", "ideal_bounds", "smooth_bounds", "MAX_ATOMS", "MAX_CENTRES", "MAX_CONFORMERS", "STATUS", "STAGES"]
 
 #: limits of the kernel (csrc/conformers.hip)
 MAX_ATOMS, MAX_CENTRES, MAX_CONFORMERS = 128, 64, 4096
@@ -117,6 +119,114 @@ def smooth_bounds(lo, up):
         i, j = (int(v) for v in np.argwhere(lo > up)[0])
         raise ValueError(f"ConformerEnsemble: the bounds contradict each other, smoothing leaves lo > up for the pair ({i}, {j})")
     return lo, up
+
+
+#: single-bond covalent radii (Cordero et al. 2008), A; any other element: COVALENT_FALLBACK x its `VDW_RADII` entry
+COVALENT_RADII = {1: 0.31, 5: 0.84, 6: 0.76, 7: 0.71, 8: 0.66, 9: 0.57, 14: 1.11, 15: 1.07, 16: 1.05, 17: 1.02, 34: 1.20, 35: 1.20, 53: 1.39}
+COVALENT_FALLBACK = 0.45
+#: what a bond is shorter by than the sum of the radii: single, conjugated single, aromatic, double, triple
+SHRINK_SINGLE, SHRINK_CONJUGATED, SHRINK_AROMATIC, SHRINK_DOUBLE, SHRINK_TRIPLE = 0.0, 0.06, 0.13, 0.19, 0.32
+#: the angle at a centre by its hybridisation index (1 SP, 2 SP2, 3 and above), and inside a ring of 3, 4, 5 atoms
+IDEAL_ANGLES, RING_ANGLES = {1: 180.0, 2: 120.0}, {3: 60.0, 4: 90.0, 5: 108.0}
+TETRAHEDRAL_ANGLE = 109.4712
+#: the signed volume of three unit vectors to the corners of a regular tetrahedron
+TETRAHEDRAL_VOLUME = 4.0 / (3.0 * np.sqrt(3.0))
+
+
+def ideal_bounds(ligand) -> Dict[str, object]:
+    """Bounds without a reference conformer, from a `ligand.Ligand` (host, float64; **the package's own table, unvalidated beyond the
+    bond lengths of one crystal ligand**, NOTES.md) -> dict: `lo`, `up` [L,L] smoothed (`smooth_bounds`), `lengths` [n_bonds], `centres`
+    int32 [n,4] with `vol_lo`, `vol_hi` [n], `unspecified_centres` (atoms `chirality.centres_from_bonds` finds that carry no `@`).
+
+    1-2  r_i + r_j - shrink +- TOL_12 (`COVALENT_RADII`; shrink 0 single, 0.06 conjugated single, 0.13 aromatic, 0.19 double, 0.32 triple)
+    1-3  the cosine law +- TOL_13 with the centre's angle: 180 / 120 / 109.4712 degrees for hybridisation index 1 / 2 / >= 3
+         (`Ligand.perceive`), the regular polygon's 60 / 90 / 108 when both neighbours share a ring of 3 / 4 / 5 atoms with the centre
+    1-4  [cis - TOL_14, trans + TOL_14] in closed form from those lengths and angles (several paths: the widest interval); cis +-
+         TOL_PLANAR when all four atoms lie in one ring and the central bond is aromatic
+    else [VDW_SCALE (r_i + r_j), UP_FAR] with `validity.VDW_RADII`
+    A centre written `@` / `@@` with four substituents, at most one of them a hydrogen: (c, n1, n2, n3) are the heavy neighbours of
+    `chiral_order` without the first (with a hydrogen: without it), V = (n1 - c) . ((n2 - c) x (n3 - c)) lies within VOL_RANGE x
+    (sign x TETRAHEDRAL_VOLUME x the three ideal lengths); the sign is + for `@@` and - for `@`, reversed when the hydrogen stands at
+    an odd place of the order.  Anchor: `N[C@@H](C)C(=O)O` is L-alanine, (CB - CA) . ((N - CA) x (C - CA)) > 0."""
+    from .chirality import centres_from_bonds
+    L = ligand.n_atoms
+    z, orders = ligand.elements, ligand.bond_orders
+    bonds = [(int(i), int(j)) for i, j in ligand.bonds.tolist()]
+    p = ligand.perceive()
+    hyb, rings = p["hybridization"], [frozenset(r) for r in p["rings"]]
+    vdw = np.asarray([VDW_RADII.get(int(e), DEFAULT_RADIUS) for e in z], dtype=np.float64)
+    cov = np.asarray([COVALENT_RADII.get(int(e), COVALENT_FALLBACK * VDW_RADII.get(int(e), DEFAULT_RADIUS)) for e in z], dtype=np.float64)
+    length, aromatic_bond = {}, {}
+    for b, (i, j) in enumerate(bonds):
+        o = float(orders[b])
+        shrink = (SHRINK_AROMATIC if o == 1.5 else SHRINK_DOUBLE if o == 2.0 else SHRINK_TRIPLE if o == 3.0 else
+                  SHRINK_CONJUGATED if (o == 1.0 and p["conjugated"][b]) else SHRINK_SINGLE)
+        length[i, j] = length[j, i] = cov[i] + cov[j] - shrink
+        aromatic_bond[i, j] = aromatic_bond[j, i] = o == 1.5
+    adj = [set() for _ in range(L)]
+    for i, j in bonds:
+        adj[i].add(j); adj[j].add(i)
+
+    def angle(i, j, k):                                      # at j, radians
+        small = [len(r) for r in rings if len(r) <= 5 and i in r and j in r and k in r]
+        deg = RING_ANGLES[min(small)] if small else IDEAL_ANGLES.get(int(hyb[j]), TETRAHEDRAL_ANGLE)
+        return np.deg2rad(deg)
+
+    lo = VDW_SCALE * (vdw[:, None] + vdw[None])
+    up = np.full((L, L), UP_FAR)
+    rank = np.zeros((L, L), dtype=np.int8)                   # as `bounds_from_bonds`: 1 a 1-4 pair, 2 planar, 3 a 1-3 pair, 4 bonded
+
+    def put(i, j, r, a, b):
+        if r < rank[i, j]:
+            return
+        if r == rank[i, j] and r in (1, 2):                  # a second path between the ends: the widest interval
+            a, b = min(a, lo[i, j]), max(b, up[i, j])
+        rank[i, j] = rank[j, i] = r
+        lo[i, j] = lo[j, i] = a
+        up[i, j] = up[j, i] = b
+
+    for i in range(L):
+        for j in adj[i]:
+            put(i, j, 4, length[i, j] - TOL_12, length[i, j] + TOL_12)
+            for k in adj[j] - {i}:
+                a, b, t1 = length[i, j], length[j, k], angle(i, j, k)
+                d13 = float(np.sqrt(a * a + b * b - 2.0 * a * b * np.cos(t1)))
+                put(i, k, 3, d13 - TOL_13, d13 + TOL_13)
+                for l in adj[k] - {i, j}:
+                    c, t2 = length[k, l], angle(j, k, l)
+                    along = b - a * np.cos(t1) - c * np.cos(t2)
+                    cis = float(np.hypot(along, a * np.sin(t1) - c * np.sin(t2)))
+                    trans = float(np.hypot(along, a * np.sin(t1) + c * np.sin(t2)))
+                    if aromatic_bond[j, k] and any(i in r and j in r and k in r and l in r for r in rings):
+                        put(i, l, 2, cis - TOL_PLANAR, cis + TOL_PLANAR)
+                    else:
+                        put(i, l, 1, cis - TOL_14, trans + TOL_14)
+    np.fill_diagonal(lo, 0.0)
+    np.fill_diagonal(up, 0.0)
+    lo, up = smooth_bounds(lo, up)
+
+    centres, vol = [], []
+    for c in range(L):
+        order = ligand.chiral_order.get(c)
+        if not ligand.chiral[c] or order is None or len(order) != 4 or sum(1 for v in order if v < 0) > 1:
+            continue
+        sign = 1.0 if int(ligand.chiral[c]) == 2 else -1.0
+        if -1 in order:
+            if order.index(-1) % 2:
+                sign = -sign
+            three = [v for v in order if v >= 0]
+        else:
+            three = list(order[1:])
+        centres.append((c, *three))
+        vol.append(sign * TETRAHEDRAL_VOLUME * float(np.prod([length[c, v] for v in three])))
+    vol = np.asarray(vol, dtype=np.float64)
+    written = {c[0] for c in centres}
+    found = centres_from_bonds(L, bonds, elements=[int(e) for e in z], bond_orders=[float(o) for o in orders],
+                               implicit_h=[int(h) for h in ligand.h_count])
+    return {"lo": lo, "up": up, "lengths": np.asarray([length[i, j] for i, j in bonds], dtype=np.float64),
+            "centres": np.asarray(centres, dtype=np.int32).reshape(-1, 4),
+            "vol_lo": np.minimum(VOL_RANGE[0] * vol, VOL_RANGE[1] * vol), "vol_hi": np.maximum(VOL_RANGE[0] * vol, VOL_RANGE[1] * vol),
+            "unspecified_centres": sorted({int(q[0]) for q in found} - written)}
 
 
 class ConformerEnsemble:

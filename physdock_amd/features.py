@@ -6,8 +6,9 @@ The reference builds the model's feature dict on the CPU in DataLoader workers a
 the device once (a few hundred kB) and every derived tensor produced there by the kernels of csrc/features.hip and
 pd_template_feat: target / MSA features (make_feats, :803-851), the inter-chain token-bond search (_make_token_bonds,
 :853-911), the pair masks (:982-983), the template block (get_template_feat, :944-968; 62 % of the bytes of a cfg1 feature
-dict) and the type correction (:995-997).  What produces the raw arrays - CCD metadata lookup, the RDKit ligand featuriser,
-MSA pairing (`FeatureLoader.load`, :1004-1173) - stays on the host and out of scope.
+dict) and the type correction (:995-997).  What produces the raw arrays - CCD metadata lookup, MSA pairing
+(`FeatureLoader.load`, :1004-1173) - stays on the host and out of scope; the ligand's blocks come from `ligand.LigandLibrary`
+(csrc/ligand_features.hip), which stands in for the reference's RDKit featuriser.
 """
 from __future__ import annotations
 

@@ -1,0 +1,420 @@
+"""How does a molecule become model input?  `Ligand` holds one ligand's graph - from a SMILES string (`smiles.parse_smiles`), a
+`sdfio.parse_sdf` record or plain arrays - and `LigandLibrary` turns a whole screening library into the reference's ligand feature
+blocks in ONE launch (kernel `pd_ligand_features`, csrc/ligand_features.hip): the int8 tables of `get_features_from_ref_mol`
+(PhysDock/data/tools/rdkit.py) and the two packed blocks `ref_feat [L,167]` and `rel_tok_feat [L,L,42]` in the column order of
+`FeatureLoader._update_smi` (feature_loader.py:327-352).  The reference computes them with RDKit on the host, a `GetShortestPath` call
+per atom pair; RDKit is not a dependency of this package, so this is **the package's own definition, not RDKit's bytes**:
+tests/ligand_features_ref.py is the written definition, in integers.
+
+    d_token [L,L]            graph distance, min(30, d), 0 on the diagonal
+    token_bonds, bond_type   0 single, 1 double, 2 triple, 3 aromatic (order 1.5), 4 other; a pair without a bond is 0 as in the
+                             reference's zero-initialised matrices
+    bond_as_double           the order as the reference's int8 table holds it: truncated, 1 for an aromatic bond
+    bond_is_aromatic         order 1.5
+    bond_in_ring             the bond is no bridge
+    ref_in_ring_of_n         n = 3 .. 8: the atom lies on a chordless cycle of exactly n atoms
+    ref_degree               min(8, heavy neighbours);  ref_implicit_valence  min(8, h_count);  ref_element  Z - 1;  ref_charge
+    ref_is_aromatic          written aromatic, or any bond of order 1.5
+    ref_chirality            `@@` 0, `@` 1, none 2
+    bond_is_conjugated       pi atoms have a bond of order >= 1.5; donor atoms are N, O, S without one and with charge <= 0.  A single
+                             bond is conjugated between two pi atoms or a pi atom and a donor; a non-aromatic multiple bond when a
+                             conjugated single bond touches either end; an aromatic bond always
+    ref_hybridization        v = h_count + sum of orders (an atom's aromatic bonds count as their number + 1); lone pairs =
+                             max(0, group valence electrons - charge - v) // 2; n = degree + h_count + lone pairs; n <= 1 -> 0 (S),
+                             2 -> 1 (SP), 3 -> 2, 4 -> 3, 5 -> 4, 6 -> 5, more -> 6; a donor atom with n = 4 on a conjugated single bond
+                             is 2 (SP2): the amide N, the phenol O
+
+`Ligand.embed_reference` makes the 3-D reference conformer `ref_pos` by distance geometry from ideal bounds
+(`conformers.ideal_bounds`, `ConformerEnsemble`), `conf_meta` returns the reference's `CONF_META_DATA["XXX"]` entry and label features,
+`into_batch` writes a ligand into a model feature dict on the device, and `graph()` feeds every `from_bonds` constructor of the package.
+
+**Caveats.**  No aromaticity perception and no kekulisation: a Kekule ring stays Kekule in every table.  Double-bond stereo is
+ignored.  Ring sizes are those of chordless cycles, not of RDKit's ring set (they agree on ordinary ring systems, not on cages).
+Hybridisation and conjugation are the rules above, not RDKit's.  The conformer has no torsion preferences and no force-field clean-up.
+Limits: 1 .. 128 atoms and up to 512 bonds per ligand, up to 65535 ligands per launch.  Out of scope: the CCD lookup, MSA features,
+`FeatureLoader.load`."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from .pdbio import ELEMENTS
+from .smiles import MAX_ATOMS, NORMAL_VALENCES, implicit_hydrogens, parse_smiles
+
+__all__ = ["Ligand", "LigandLibrary", "ATOM_COLUMNS", "PAIR_COLUMNS", "MAX_ATOMS", "MAX_BONDS", "MAX_LIGANDS", "GROUP_ELECTRONS",
+           "chordless_rings"]
+
+MAX_BONDS, MAX_LIGANDS = 512, 65535
+#: columns of the kernel's int8 tables (rows of 16 per atom and of 8 per atom pair; the rest is zero)
+ATOM_COLUMNS = ("ref_charge", "ref_element", "ref_is_aromatic", "ref_degree", "ref_hybridization", "ref_implicit_valence",
+                "ref_chirality", "ref_in_ring_of_3", "ref_in_ring_of_4", "ref_in_ring_of_5", "ref_in_ring_of_6", "ref_in_ring_of_7",
+                "ref_in_ring_of_8")
+PAIR_COLUMNS = ("d_token", "token_bonds", "bond_type", "bond_as_double", "bond_in_ring", "bond_is_conjugated", "bond_is_aromatic")
+ATOM_ROW, PAIR_ROW, REF_FEAT, REL_TOK_FEAT = 16, 8, 167, 42
+
+
+def _group_electrons():
+    """valence electrons by atomic number (index 0 unused): the group of a main-group element, the group number of a transition metal,
+    3 for the lanthanides and actinides"""
+    out = [0] * 129
+    rows = ((1, 2), (3, 10), (11, 18), (19, 36), (37, 54), (55, 86), (87, 118))
+    for first, last in rows:
+        n = last - first + 1
+        for z in range(first, last + 1):
+            k = z - first + 1                                       # position in the period
+            if n == 2:
+                e = k
+            elif n == 8:
+                e = k
+            elif n == 18:
+                e = k if k <= 12 else k - 10
+            else:                                                   # 32: s2, fourteen f elements and the first d, nine d, six p
+                e = k if k <= 2 else (3 if k <= 17 else (k - 14 if k <= 26 else k - 24))
+            out[z] = e
+    for z in range(119, 129):
+        out[z] = 0
+    return tuple(out)
+
+
+#: the table `lone pairs` reads (the kernel holds the same numbers)
+GROUP_ELECTRONS = _group_electrons()
+
+
+def chordless_rings(n_atoms: int, bonds, max_size: int = 8) -> List[tuple]:
+    """every chordless cycle of 3 .. max_size atoms as a tuple of atoms in ring order, starting at its smallest atom towards the
+    smaller of that atom's two ring neighbours; sorted"""
+    adj = [set() for _ in range(n_atoms)]
+    for i, j in bonds:
+        adj[int(i)].add(int(j)); adj[int(j)].add(int(i))
+    found = set()
+
+    def walk(path, blocked):
+        last = path[-1]
+        for w in sorted(adj[last]):
+            if w in path or w in blocked or w < path[0]:
+                continue
+            if len(path) >= 2 and path[0] in adj[w]:
+                if path[1] < w:
+                    found.add(tuple(path) + (w,))
+                continue
+            if len(path) + 1 < max_size:
+                walk(path + [w], blocked | (adj[last] if len(path) >= 2 else set()))
+
+    for s in range(n_atoms):
+        walk([s], set())
+    return sorted(found)
+
+
+def _valence_rule(elements, bonds, bond_orders, charges):
+    """`smiles.implicit_hydrogens` per atom of a graph without written hydrogen counts.  A charge moves the valence it is measured
+    against: a cation of group 15 / 16 has one more, an anion one fewer, any other charged atom one fewer."""
+    h = np.zeros(len(elements), dtype=np.int64)
+    pairs = np.asarray(bonds).reshape(-1, 2).tolist()
+    for a in range(len(elements)):
+        z, q = int(elements[a]), int(charges[a])
+        if z not in NORMAL_VALENCES:
+            continue
+        own = [float(o) for (i, j), o in zip(pairs, bond_orders) if a in (i, j)]
+        shift = -q if z in (7, 8, 15, 16) else abs(q)
+        n_arom = sum(1 for o in own if o == 1.5)
+        h[a] = implicit_hydrogens(z, sum(o for o in own if o != 1.5) + shift, n_arom, len(own) + shift)
+    return h
+
+
+def _device(device) -> torch.device:
+    """`device` as a cache key; None is the current CUDA device, as in `ConformerEnsemble.embed`"""
+    return ops.resolve_device(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+
+
+def _frozen(a, dtype):
+    a = np.array(a, dtype=dtype)
+    a.setflags(write=False)
+    return a
+
+
+class Ligand:
+    """One ligand's graph over its heavy atoms, immutable: `elements` (atomic numbers), `bonds` int64 [n,2], `bond_orders` float64,
+    `charges`, `h_count`, `aromatic` (bool), `chiral` (0 none, 1 `@`, 2 `@@`), `chiral_order` (atom -> its neighbours in OpenSMILES
+    order, -1 a hydrogen; only what a SMILES string gives) and `isotopes`."""
+
+    def __init__(self, elements, bonds, bond_orders, charges, h_count, aromatic, chiral, chiral_order=None, isotopes=None, source=""):
+        self.elements = _frozen(elements, np.int64).reshape(-1)
+        L = self.n_atoms = int(self.elements.shape[0])
+        if not 1 <= L <= MAX_ATOMS:
+            raise ValueError(f"Ligand: {L} heavy atoms; 1 .. {MAX_ATOMS} are taken")
+        if self.elements.min() < 1 or self.elements.max() > len(ELEMENTS):
+            raise ValueError(f"Ligand: an atomic number outside 1 .. {len(ELEMENTS)}")
+        self.bonds = _frozen(bonds, np.int64).reshape(-1, 2)
+        self.bond_orders = _frozen(bond_orders, np.float64).reshape(-1)
+        nb = self.n_bonds = int(self.bonds.shape[0])
+        if self.bond_orders.shape[0] != nb:
+            raise ValueError(f"Ligand: {nb} bonds but {self.bond_orders.shape[0]} bond orders")
+        if nb > MAX_BONDS:
+            raise ValueError(f"Ligand: {nb} bonds; up to {MAX_BONDS} are taken")
+        if nb and (self.bonds.min() < 0 or self.bonds.max() >= L or (self.bonds[:, 0] == self.bonds[:, 1]).any()):
+            raise ValueError(f"Ligand: a bond leaves the {L} atoms or joins an atom to itself")
+        if len({(min(i, j), max(i, j)) for i, j in self.bonds.tolist()}) != nb:
+            raise ValueError("Ligand: two bonds between the same atoms")
+        o2 = 2.0 * self.bond_orders
+        if nb and ((o2 != np.round(o2)).any() or o2.min() < 1 or o2.max() > 8):
+            raise ValueError("Ligand: bond orders are multiples of 0.5 in 0.5 .. 4")
+        self.charges = _frozen(np.zeros(L) if charges is None else charges, np.int64).reshape(-1)
+        self.aromatic = _frozen(np.zeros(L) if aromatic is None else aromatic, bool).reshape(-1)
+        self.chiral = _frozen(np.zeros(L) if chiral is None else chiral, np.int64).reshape(-1)
+        self.isotopes = _frozen(np.zeros(L) if isotopes is None else isotopes, np.int64).reshape(-1)
+        if h_count is None:
+            h_count = _valence_rule(self.elements, self.bonds, self.bond_orders, self.charges)
+        self.h_count = _frozen(h_count, np.int64).reshape(-1)
+        for name in ("charges", "aromatic", "chiral", "isotopes", "h_count"):
+            if getattr(self, name).shape[0] != L:
+                raise ValueError(f"Ligand: {getattr(self, name).shape[0]} entries of {name} for {L} atoms")
+        if np.abs(self.charges).max() > 127 or self.h_count.min() < 0 or self.h_count.max() > 127 or not np.isin(self.chiral, (0, 1, 2)).all():
+            raise ValueError("Ligand: a charge beyond +-127, an h_count outside 0 .. 127 or a chiral code other than 0, 1, 2")
+        self.chiral_order = {int(a): tuple(int(v) for v in order) for a, order in (chiral_order or {}).items()}
+        self.source = str(source)
+        adj = self.neighbours()
+        reach, todo = {0}, [0]
+        while todo:
+            for c in adj[todo.pop()]:
+                if c not in reach:
+                    reach.add(c); todo.append(c)
+        if len(reach) != L:
+            raise ValueError(f"Ligand: the graph is not connected: atom {min(set(range(L)) - reach)} cannot be reached from atom 0")
+        self._features = {}
+
+    # ------------------------------------------------------------------ constructors
+    @staticmethod
+    def from_smiles(text: str) -> "Ligand":
+        r = parse_smiles(text)
+        return Ligand(r["elements"], r["bonds"], r["bond_orders"], r["charges"], r["h_count"], r["aromatic"], r["chiral"],
+                      r["chiral_order"], r["isotopes"], source=text.strip())
+
+    @staticmethod
+    def from_graph(elements, bonds, bond_orders, charges=None, h_count=None, aromatic=None, chiral=None) -> "Ligand":
+        """elements: atomic numbers or symbols; `h_count=None` uses the valence rule of `smiles.parse_smiles`"""
+        z = [(_SYMBOL_Z.get(e.strip().upper(), 0) if isinstance(e, str) else int(e)) for e in (elements.tolist() if hasattr(elements, "tolist") else elements)]
+        bonds = np.asarray(bonds.tolist() if hasattr(bonds, "tolist") else list(bonds), dtype=np.int64).reshape(-1, 2)
+        orders = np.ones(len(bonds)) if bond_orders is None else np.asarray(bond_orders, dtype=np.float64)
+        return Ligand(z, bonds, orders, charges, h_count, aromatic, chiral)
+
+    @staticmethod
+    def from_sdf(record: dict) -> "Ligand":
+        """a `sdfio.parse_sdf` record; its hydrogens on heavy atoms are folded into `h_count`, the heavy atoms keep their order"""
+        z = np.asarray([_SYMBOL_Z.get(str(e).strip().upper(), 0) for e in record["elements"]], dtype=np.int64)
+        bonds = np.asarray(record["bonds"], dtype=np.int64).reshape(-1, 2)
+        orders = np.asarray(record["bond_orders"], dtype=np.float64).reshape(-1)
+        charges = np.asarray(record["charges"], dtype=np.int64).reshape(-1)
+        n = len(z)
+        nbr = [[] for _ in range(n)]
+        for i, j in bonds.tolist():
+            nbr[i].append(j); nbr[j].append(i)
+        folded = np.asarray([z[a] == 1 and len(nbr[a]) == 1 and z[nbr[a][0]] != 1 for a in range(n)], dtype=bool)
+        if n > 1 and ((z == 1) & ~folded).any():
+            raise ValueError(f"Ligand.from_sdf: the hydrogen {int(np.nonzero((z == 1) & ~folded)[0][0])} is not bonded to one heavy atom")
+        extra = np.zeros(n, dtype=np.int64)
+        for a in np.nonzero(folded)[0]:
+            extra[nbr[a][0]] += 1
+        new_id = np.cumsum(~folded) - 1
+        keep_b = ~folded[bonds[:, 0]] & ~folded[bonds[:, 1]] if len(bonds) else np.zeros(0, dtype=bool)
+        h = _valence_rule(z, bonds, orders, charges)[~folded] + extra[~folded]      # the bonds to the folded hydrogens count as bonds
+        return Ligand(z[~folded], new_id[bonds[keep_b]].reshape(-1, 2), orders[keep_b], charges[~folded], h, None, None,
+                      source=str(record.get("title", "")))
+
+    # ------------------------------------------------------------------ the graph
+    def neighbours(self) -> List[List[int]]:
+        adj = [[] for _ in range(self.n_atoms)]
+        for i, j in self.bonds.tolist():
+            adj[i].append(j); adj[j].append(i)
+        return adj
+
+    def graph(self):
+        """(elements, bonds, bond_orders, charges) for the `from_bonds` constructors of the package"""
+        return self.elements.copy(), self.bonds.copy(), self.bond_orders.copy(), self.charges.copy()
+
+    def symbols(self) -> List[str]:
+        return [ELEMENTS[int(z) - 1] for z in self.elements]
+
+    def perceive(self) -> Dict[str, np.ndarray]:
+        """what `conformers.ideal_bounds` needs, by the rules of the module docstring on the host: `hybridization` [L], `conjugated`
+        [n_bonds] (bool) and `rings` (`chordless_rings`)"""
+        L, o = self.n_atoms, self.bond_orders
+        bi, bj = self.bonds[:, 0], self.bonds[:, 1]
+        arom, single, multi = o == 1.5, o == 1.0, (o >= 2.0)
+        count = lambda mask, w=None: (np.bincount(bi[mask], (w[mask] if w is not None else None), L)
+                                      + np.bincount(bj[mask], (w[mask] if w is not None else None), L))
+        pi = count(o >= 1.5) > 0
+        donor = np.isin(self.elements, (7, 8, 16)) & ~pi & (self.charges <= 0)
+        conj_single = single & ((pi[bi] & pi[bj]) | (pi[bi] & donor[bj]) | (donor[bi] & pi[bj]))
+        on_conj = count(conj_single) > 0
+        conjugated = arom | conj_single | (multi & (on_conj[bi] | on_conj[bj]))
+        n_arom = count(arom).astype(np.int64)
+        v = self.h_count + np.floor(count(~arom, o)).astype(np.int64) + np.where(n_arom > 0, n_arom + 1, 0)
+        lone = np.maximum(0, np.asarray(GROUP_ELECTRONS)[self.elements] - self.charges - v) // 2
+        n = count(np.ones(len(o), dtype=bool)).astype(np.int64) + self.h_count + lone
+        hyb = np.select([n <= 1, n == 2, n == 3, n == 4, n == 5, n == 6], [0, 1, 2, 3, 4, 5], 6)
+        hyb = np.where(donor & (n == 4) & on_conj, 2, hyb)
+        return {"hybridization": hyb.astype(np.int64), "conjugated": conjugated, "rings": chordless_rings(L, self.bonds.tolist())}
+
+    # ------------------------------------------------------------------ device side
+    def features(self, device=None) -> Dict[str, torch.Tensor]:
+        """this ligand's tables and blocks on the device (`LigandLibrary.features` of a library of one, computed once per device):
+        every name of `ATOM_COLUMNS` int8 [L], of `PAIR_COLUMNS` int8 [L,L], `ref_feat` fp32 [L,167] (columns 0 .. 2, `ref_pos`, are
+        zero) and `rel_tok_feat` fp32 [L,L,42].  `device=None` is the current CUDA device.  The kernel's result is kept; every call
+        returns fresh copies, so a caller may write into them."""
+        device = _device(device)
+        if device not in self._features:
+            lib = LigandLibrary([self])
+            self._features[device] = lib.split(lib.features(device), 0)
+        return {k: v.clone() for k, v in self._features[device].items()}
+
+    def embed_reference(self, seed: int = 0, C: int = 32, device=None) -> Dict[str, torch.Tensor]:
+        """The reference conformer: C distance-geometry conformers from `conformers.ideal_bounds(self)`
+        (`ConformerEnsemble.from_tables(...).embed`), of which the accepted one with the smallest `err` - the lowest index on a tie - is
+        `ref_pos` fp32 [L,3]; `ref_feat` is `features()["ref_feat"]` with it in columns 0 .. 2.  Also `index`, `err`, `max_violation`
+        (host numbers), `n_accepted` and `unspecified_centres`.  One read of the C errors.  RuntimeError when no conformer is accepted."""
+        from .conformers import ConformerEnsemble, ideal_bounds
+        device = _device(device)
+        t = ideal_bounds(self)
+        feats = self.features(device)
+        if self.n_atoms == 1:
+            pos = torch.zeros(1, 3, device=device)
+            index, err, viol, n_ok = 0, 0.0, 0.0, 1
+        else:
+            ens = ConformerEnsemble.from_tables(t["lo"], t["up"], t["centres"], t["vol_lo"], t["vol_hi"])
+            out = ens.embed(int(C), int(seed), keep=None, device=device)
+            ok, errs = out["ok"].cpu().numpy().astype(bool), out["err"].cpu().numpy()
+            if not ok.any():
+                raise RuntimeError(f"Ligand.embed_reference: none of {int(C)} conformers of {self.source or 'the ligand'} was accepted "
+                                   f"(seed {int(seed)})")
+            index = int(np.argmin(np.where(ok, errs, np.inf)))
+            pos, err, viol, n_ok = out["x"][index], float(errs[index]), float(out["max_violation"][index]), int(ok.sum())
+        ref_feat = feats["ref_feat"]
+        ref_feat[:, :3] = pos
+        return {"ref_pos": pos, "ref_feat": ref_feat, "index": index, "err": err, "max_violation": viol, "n_accepted": n_ok,
+                "unspecified_centres": t["unspecified_centres"]}
+
+    def conf_meta(self, ref_pos=None, device=None, seed: int = 0):
+        """(CONF_META_DATA["XXX"], label_feature) of the reference's `_update_smi` and `get_features_from_ref_mol` as numpy arrays:
+        `ref_feat`, `rel_tok_feat`, `ref_atom_name_chars`, `ref_element`, `token_bonds`; `x_gt` is `ref_pos` (given, or embedded)."""
+        f = self.features(device)
+        if ref_pos is None:
+            ref_pos = self.embed_reference(seed=seed, device=device)["ref_pos"]
+        pos = np.asarray(ref_pos.detach().cpu() if isinstance(ref_pos, torch.Tensor) else ref_pos, dtype=np.float32).reshape(self.n_atoms, 3)
+        ref_feat = f["ref_feat"].cpu().numpy().copy()
+        ref_feat[:, :3] = pos
+        L = self.n_atoms
+        meta = {"ref_feat": ref_feat, "rel_tok_feat": f["rel_tok_feat"].cpu().numpy().copy(),
+                "ref_atom_name_chars": [f"{s + str(k):<4}" for k, s in enumerate(self.symbols())],
+                "ref_element": f["ref_element"].cpu().numpy().copy(), "token_bonds": f["token_bonds"].cpu().numpy().copy()}
+        label = {"x_gt": pos.copy(), "x_exists": np.ones(L, dtype=np.int64), "a_mask": np.ones(L, dtype=np.int64),
+                 "restype": np.array([20], dtype=np.int64), "residue_index": np.arange(1, dtype=np.int64),
+                 "atom_id_to_conformer_atom_id": np.arange(L, dtype=np.int64), "conformer_id_to_chunk_sizes": np.array([L], dtype=np.int64)}
+        return meta, label
+
+    def into_batch(self, batch: Dict[str, torch.Tensor], ref_pos=None, seed: int = 0) -> Dict[str, torch.Tensor]:
+        """Overwrites, in place and on the batch's device, the ligand atoms' rows of `ref_feat` and `ref_pos` (the atoms of
+        `driver.ligand_atom_mask`) and the ligand x ligand block of `rel_tok_feat` and `token_bonds_feature` (the tokens of `is_ligand`,
+        one per atom).  `ref_pos` [L,3]: the conformer to write (default: `embed_reference(seed)`).  A batch whose ligand has another
+        atom or token count raises before anything is written."""
+        from .driver import ligand_atom_mask
+        atoms = torch.nonzero(ligand_atom_mask(batch)).flatten()
+        tokens = torch.nonzero(batch["is_ligand"].bool()).flatten()
+        L = self.n_atoms
+        if int(atoms.numel()) != L or int(tokens.numel()) != L:
+            raise ValueError(f"Ligand.into_batch: the batch's ligand has {int(atoms.numel())} atoms in {int(tokens.numel())} tokens, "
+                             f"this ligand {L} atoms")
+        device = batch["ref_feat"].device
+        if tuple(batch["ref_feat"].shape[1:]) != (REF_FEAT,) or tuple(batch["rel_tok_feat"].shape[2:]) != (REL_TOK_FEAT,):
+            raise ValueError("Ligand.into_batch: ref_feat must be [A,167] and rel_tok_feat [T,T,42]")
+        if ref_pos is None:
+            ref_pos = self.embed_reference(seed=seed, device=device)["ref_pos"]
+        pos = torch.as_tensor(ref_pos, device=device).float()
+        if tuple(pos.shape) != (L, 3):
+            raise ValueError(f"Ligand.into_batch: ref_pos must be [{L},3], got {tuple(pos.shape)}")
+        f = self.features(device)
+        rows = f["ref_feat"]
+        rows[:, :3] = pos
+        batch["ref_feat"][atoms] = rows.to(batch["ref_feat"].dtype)
+        batch["ref_pos"][atoms] = pos.to(batch["ref_pos"].dtype)
+        ti, tj = tokens[:, None], tokens[None, :]
+        batch["rel_tok_feat"][ti, tj] = f["rel_tok_feat"].to(batch["rel_tok_feat"].dtype)
+        batch["token_bonds_feature"][ti, tj] = f["token_bonds"].to(batch["token_bonds_feature"].dtype)
+        return batch
+
+    def __repr__(self):
+        return f"Ligand(n_atoms={self.n_atoms}, n_bonds={self.n_bonds}{', ' + repr(self.source) if self.source else ''})"
+
+
+_SYMBOL_Z = {s.upper(): k + 1 for k, s in enumerate(ELEMENTS)}
+_SYMBOL_Z["D"] = 1
+
+
+class LigandLibrary:
+    """G ligands as CSR tables for one launch of `pd_ligand_features`: `atom_start`, `bond_start` int32 [G+1], `pair_start` int64
+    [G+1] (prefix sums of L^2), `atoms` int32 [N,4] (Z, charge, h_count, flags: bit 0 written aromatic, bits 1 - 2 the chiral code)
+    and `bonds` int32 [B,4] (i, j local to the ligand, twice the order, 0)."""
+
+    def __init__(self, ligands: Sequence[Ligand]):
+        self.ligands = list(ligands)
+        G = self.n_ligands = len(self.ligands)
+        if not 1 <= G <= MAX_LIGANDS:
+            raise ValueError(f"LigandLibrary: {G} ligands; one launch takes 1 .. {MAX_LIGANDS}")
+        if any(not isinstance(l, Ligand) for l in self.ligands):
+            raise ValueError("LigandLibrary: every entry must be a Ligand")
+        n = np.asarray([l.n_atoms for l in self.ligands], dtype=np.int64)
+        self.atom_start = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+        self.bond_start = np.concatenate([[0], np.cumsum([l.n_bonds for l in self.ligands])]).astype(np.int32)
+        self.pair_start = np.concatenate([[0], np.cumsum(n * n)]).astype(np.int64)
+        self.atoms = np.concatenate([np.stack([l.elements, l.charges, l.h_count, l.aromatic.astype(np.int64) | (l.chiral << 1)], axis=1)
+                                     for l in self.ligands]).astype(np.int32)
+        self.bonds = np.concatenate([np.concatenate([l.bonds, np.round(2.0 * l.bond_orders).astype(np.int64)[:, None],
+                                                     np.zeros((l.n_bonds, 1), dtype=np.int64)], axis=1)
+                                     for l in self.ligands]).astype(np.int32).reshape(-1, 4)
+        self.n_atoms, self.n_bonds, self.n_pairs = int(self.atom_start[-1]), int(self.bond_start[-1]), int(self.pair_start[-1])
+        self._tables = {}
+
+    @staticmethod
+    def from_smiles(lines: Sequence[str]) -> "LigandLibrary":
+        return LigandLibrary([Ligand.from_smiles(s) for s in lines])
+
+    def tables(self, device) -> Dict[str, torch.Tensor]:
+        names = ("atom_start", "bond_start", "pair_start", "atoms", "bonds")
+        return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
+
+    def features(self, device=None) -> Dict[str, torch.Tensor]:
+        """ONE launch for the whole library -> device tensors `atom_table` int8 [N,16] (`ATOM_COLUMNS`), `pair_table` int8 [P,8]
+        (`PAIR_COLUMNS`), `ref_feat` fp32 [N,167], `rel_tok_feat` fp32 [P,42]; ligand g owns the atom rows atom_start[g] ..
+        atom_start[g+1] and the pair rows pair_start[g] .. pair_start[g+1] (`split`).  `device=None` is the current CUDA device.  Nothing is read back."""
+        device = _device(device)
+        t = self.tables(device)
+        N, P = self.n_atoms, self.n_pairs
+        out = {"atom_table": torch.empty(N, ATOM_ROW, device=device, dtype=torch.int8),
+               "pair_table": torch.empty(P, PAIR_ROW, device=device, dtype=torch.int8),
+               "ref_feat": torch.empty(N, REF_FEAT, device=device, dtype=torch.float32),
+               "rel_tok_feat": torch.empty(P, REL_TOK_FEAT, device=device, dtype=torch.float32)}
+        L_ = ops._lib.init()
+        with torch.cuda.device(device):
+            ops.check(L_.pd_ligand_features(ops.ptr(t["atom_start"]), ops.ptr(t["bond_start"]), ops.ptr(t["pair_start"]), ops.ptr(t["atoms"]),
+                                            ops.ptr(t["bonds"]) if self.n_bonds else None, ops.ptr(out["atom_table"]),
+                                            ops.ptr(out["pair_table"]), ops.ptr(out["ref_feat"]), ops.ptr(out["rel_tok_feat"]),
+                                            self.n_ligands, N, self.n_bonds, P, ops.stream()), "pd_ligand_features")
+        return out
+
+    def split(self, out: Dict[str, torch.Tensor], g: int) -> Dict[str, torch.Tensor]:
+        """ligand g's part of a `features` result, as views under the reference's names (see `Ligand.features`)"""
+        a0, a1, p0, p1 = (int(v) for v in (*self.atom_start[g:g + 2], *self.pair_start[g:g + 2]))
+        L = a1 - a0
+        r = {name: out["atom_table"][a0:a1, k] for k, name in enumerate(ATOM_COLUMNS)}
+        r.update({name: out["pair_table"][p0:p1, k].view(L, L) for k, name in enumerate(PAIR_COLUMNS)})
+        r["ref_feat"] = out["ref_feat"][a0:a1]
+        r["rel_tok_feat"] = out["rel_tok_feat"][p0:p1].view(L, L, REL_TOK_FEAT)
+        return r
+
+    def __len__(self):
+        return self.n_ligands
+
+    def __repr__(self):
+        return f"LigandLibrary(n_ligands={self.n_ligands}, n_atoms={self.n_atoms}, n_pairs={self.n_pairs})"
