@@ -1376,6 +1376,37 @@ int pd_ligand_features(const int* atom_start, const int* bond_start, const long 
                        signed char* atom_table, signed char* pair_table, float* ref_feat, float* rel_tok_feat, int G, int n_atoms,
                        int n_bonds, long long n_pairs, void* stream);
 
+/* ---- aromaticity of ligand graphs (aromaticity.hip; additive export of ABI 11) -------------------------------------------------
+ * Perceive aromatic rings in Kekule input, kekulise aromatic input, or both in turn, for a library of G ligands in one launch (the
+ * reference: RDKit perceives on read).  The package's own definition, not RDKit's bytes: tests/aromaticity_ref.py.  The tables are
+ * those of pd_ligand_features (atom_start, bond_start int32 [G+1], atoms int32 [n_atoms][4], bonds int32 [n_bonds][4]) and atoms_out,
+ * bonds_out have the same layout, so they go straight into pd_ligand_features.  o2 is twice the bond order, 3 = aromatic; neighbours
+ * are visited in ascending atom index.
+ *   mode 0 kekulise: an atom NEEDS a double bond when it has a bond with o2 == 3, its element is in the organic subset (B C N O P S
+ *     F Cl Br I with the normal valences 3; 4; 3, 5; 2; 3, 5; 2, 4, 6; 1) and, with used = (sum of o2 over its other bonds) / 2 +
+ *     (number of its aromatic bonds) + hydrogen count + shift (shift = -charge for N, O, P, S, else |charge|), the smallest normal
+ *     valence v >= used exists and v - used == 1.  The result is the lexicographically first perfect matching of the needing atoms
+ *     over aromatic bonds: the lowest unmatched needing atom tries its unmatched needing aromatic neighbours in ascending order, each
+ *     try one step, with backtracking.  Matched bonds get o2 = 4, every other aromatic bond 2, bit 0 of every atom's flags is cleared.
+ *   mode 1 perceive: candidate rings are the chordless cycles of 5 .. 7 atoms; a bond is cyclic when it is no bridge.  An atom with a
+ *     bond of o2 > 4 or more than one double bond contributes nothing; with one double bond 1 if that bond is cyclic, 0 if the atom is
+ *     a carbon and the partner N, O or S, else nothing; without one 2 for N, P (charge 0, neighbours + hydrogens == 3), 2 for O, S, Se
+ *     (charge 0, == 2), 2 for C (charge -1, == 3), 0 for C (charge +1) or B (charge 0) with == 3, else nothing.  A ring through an atom
+ *     with a bond of o2 == 3 is skipped.  A ring is aromatic when all its atoms contribute and the sum is 4n + 2: its bonds get o2 = 3,
+ *     its atoms flag bit 0; every other atom's bit 0 is cleared.  Rings are judged independently on the input orders.
+ *   mode 2 normalise: kekulise, then perceive.
+ * atoms_out: the input rows with bit 0 of the flags rewritten.  bonds_out: the input rows with column 2 rewritten and column 3 = bit 0
+ * "in a perceived aromatic ring" | bit 1 "chosen double by the matching".  status int32 [G]: 0 done; 1 no matching exists; 2 a try
+ * would have been step max_steps + 1; with 1 or 2 the ligand's rows are copied through unchanged.  counts int32 [G][4]: aromatic rings
+ * found, aromatic atoms and aromatic bonds in the rows written, matching steps.  One block per ligand, integers only, no atomics: a
+ * ligand's bits do not depend on the library around it.  Limits as for pd_ligand_features; a ligand whose rows leave the arrays is
+ * not written (nor its status and counts) and a bond that leaves its ligand is copied through and otherwise skipped.  A NULL pointer
+ * (bonds and bonds_out may be NULL when n_bonds == 0), an output that is its input, a misaligned pointer, n_ligands < 1, n_atoms <
+ * n_ligands, a mode outside 0 .. 2, max_steps < 0: PD_ERR_ARG; n_ligands > 65535 or more atoms than that many ligands of the largest
+ * size: PD_ERR_UNSUPPORTED.  A rejected call launches nothing.                                                                    */
+int pd_aromaticity(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds, int* atoms_out, int* bonds_out,
+                   int* status, int* counts, int n_ligands, int n_atoms, int n_bonds, int mode, int max_steps, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

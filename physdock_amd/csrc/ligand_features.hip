@@ -22,6 +22,7 @@
 // No index is followed out of a table: a bond that leaves its ligand is skipped and a ligand whose rows leave the arrays is not
 // written (the host layer refuses both before any launch).
 #include "common.h"
+#include "mask128.h"
 #include "physdock_hip.h"
 
 namespace {
@@ -30,18 +31,6 @@ constexpr int LF_MAX_L = PD_LIGAND_FEATURES_MAX_ATOMS;
 constexpr int LF_MAX_B = PD_LIGAND_FEATURES_MAX_BONDS;
 constexpr int LF_MAX_G = 65535;
 constexpr int LF_REF = 167, LF_REL = 42, LF_ATOM_ROW = 16, LF_PAIR_ROW = 8, LF_FAR = 30;
-
-typedef unsigned long long u64;
-
-struct Mask {
-    u64 lo, hi;
-};
-__device__ __forceinline__ bool mk_any(Mask m) { return (m.lo | m.hi) != 0; }
-__device__ __forceinline__ bool mk_has(Mask m, int a) { return ((a < 64 ? m.lo >> a : m.hi >> (a - 64)) & 1ull) != 0; }
-__device__ __forceinline__ Mask mk_bit(int a) { return a < 64 ? Mask{1ull << a, 0ull} : Mask{0ull, 1ull << (a - 64)}; }
-__device__ __forceinline__ Mask mk_or(Mask a, Mask b) { return Mask{a.lo | b.lo, a.hi | b.hi}; }
-__device__ __forceinline__ Mask mk_andn(Mask a, Mask b) { return Mask{a.lo & ~b.lo, a.hi & ~b.hi}; }
-__device__ __forceinline__ int mk_first(Mask m) { return m.lo ? __ffsll((long long)m.lo) - 1 : 63 + __ffsll((long long)m.hi); }
 
 // valence electrons by atomic number (index 0 unused): the group of a main-group element, the group number of a transition metal, 3 for
 // the lanthanides and actinides (physdock_amd/ligand.py GROUP_ELECTRONS)

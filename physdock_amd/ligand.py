@@ -28,7 +28,17 @@ tests/ligand_features_ref.py is the written definition, in integers.
 (`conformers.ideal_bounds`, `ConformerEnsemble`), `conf_meta` returns the reference's `CONF_META_DATA["XXX"]` entry and label features,
 `into_batch` writes a ligand into a model feature dict on the device, and `graph()` feeds every `from_bonds` constructor of the package.
 
-**Caveats.**  No aromaticity perception and no kekulisation: a Kekule ring stays Kekule in every table.  Double-bond stereo is
+**Aromaticity.**  The constructors perceive nothing: a Kekule ring (an SD file from the PDB, `C1=CC=CC=C1`) stays Kekule in every
+table unless it is asked for.  `Ligand.aromatized()` / `LigandLibrary.aromatized()` return the ligands with their aromatic rings
+perceived, `kekulized()` with every aromatic bond written single or double, `LigandLibrary.aromaticity(mode)` the same as device
+tables without a read-back and `LigandLibrary.features(aromatize=True)` feeds them to `pd_ligand_features` (kernel `pd_aromaticity`,
+csrc/aromaticity.hip).  Again the package's own definition, tests/aromaticity_ref.py in integers: rings are the chordless cycles of
+5 .. 7 atoms, each judged on its own (4n + 2 electrons from a short list of contributions); the Kekule form is the lexicographically
+first perfect matching of the atoms that need a double bond, so it depends on the atom numbering.  Azulene is not perceived and
+indolizine only in its five-ring (RDKit perceives both through the fused envelope); no tautomers; a double bond that lies in some
+other, non-aromatic ring still counts as cyclic.
+
+**Caveats.**  No aromaticity perception and no kekulisation by default (above).  Double-bond stereo is
 ignored.  Ring sizes are those of chordless cycles, not of RDKit's ring set (they agree on ordinary ring systems, not on cages).
 Hybridisation and conjugation are the rules above, not RDKit's.  The conformer has no torsion preferences and no force-field clean-up.
 Limits: 1 .. 128 atoms and up to 512 bonds per ligand, up to 65535 ligands per launch.  Out of scope: the CCD lookup, MSA features,
@@ -45,7 +55,7 @@ from .pdbio import ELEMENTS
 from .smiles import MAX_ATOMS, NORMAL_VALENCES, implicit_hydrogens, parse_smiles
 
 __all__ = ["Ligand", "LigandLibrary", "ATOM_COLUMNS", "PAIR_COLUMNS", "MAX_ATOMS", "MAX_BONDS", "MAX_LIGANDS", "GROUP_ELECTRONS",
-           "chordless_rings"]
+           "chordless_rings", "AROMATICITY_MODES", "AROMATICITY_STATUS"]
 
 MAX_BONDS, MAX_LIGANDS = 512, 65535
 #: columns of the kernel's int8 tables (rows of 16 per atom and of 8 per atom pair; the rest is zero)
@@ -54,6 +64,9 @@ ATOM_COLUMNS = ("ref_charge", "ref_element", "ref_is_aromatic", "ref_degree", "r
                 "ref_in_ring_of_8")
 PAIR_COLUMNS = ("d_token", "token_bonds", "bond_type", "bond_as_double", "bond_in_ring", "bond_is_conjugated", "bond_is_aromatic")
 ATOM_ROW, PAIR_ROW, REF_FEAT, REL_TOK_FEAT = 16, 8, 167, 42
+#: the `mode` argument of `pd_aromaticity` and what its `status` says
+AROMATICITY_MODES = {"kekulise": 0, "perceive": 1, "normalise": 2}
+AROMATICITY_STATUS = {0: "done", 1: "no Kekule structure exists", 2: "the matching ran out of steps"}
 
 
 def _group_electrons():
@@ -270,6 +283,15 @@ class Ligand:
             self._features[device] = lib.split(lib.features(device), 0)
         return {k: v.clone() for k, v in self._features[device].items()}
 
+    def aromatized(self, device=None) -> "Ligand":
+        """this ligand with its aromatic rings perceived (`LigandLibrary.aromatized` of a library of one): aromatic input is kekulised
+        first, so partly aromatic input is handled.  ValueError when no Kekule structure exists."""
+        return LigandLibrary([self]).aromatized(device).ligands[0]
+
+    def kekulized(self, device=None) -> "Ligand":
+        """this ligand with every aromatic bond written single or double (`LigandLibrary.kekulized` of a library of one)"""
+        return LigandLibrary([self]).kekulized(device).ligands[0]
+
     def embed_reference(self, seed: int = 0, C: int = 32, device=None) -> Dict[str, torch.Tensor]:
         """The reference conformer: C distance-geometry conformers from `conformers.ideal_bounds(self)`
         (`ConformerEnsemble.from_tables(...).embed`), of which the accepted one with the smallest `err` - the lowest index on a tie - is
@@ -355,7 +377,8 @@ _SYMBOL_Z["D"] = 1
 class LigandLibrary:
     """G ligands as CSR tables for one launch of `pd_ligand_features`: `atom_start`, `bond_start` int32 [G+1], `pair_start` int64
     [G+1] (prefix sums of L^2), `atoms` int32 [N,4] (Z, charge, h_count, flags: bit 0 written aromatic, bits 1 - 2 the chiral code)
-    and `bonds` int32 [B,4] (i, j local to the ligand, twice the order, 0)."""
+    and `bonds` int32 [B,4] (i, j local to the ligand, twice the order, 0).  `status` is None, or int32 [G] on a library that
+    `aromatized` / `kekulized` returned: what `pd_aromaticity` said of each ligand (`AROMATICITY_STATUS`)."""
 
     def __init__(self, ligands: Sequence[Ligand]):
         self.ligands = list(ligands)
@@ -375,6 +398,7 @@ class LigandLibrary:
                                      for l in self.ligands]).astype(np.int32).reshape(-1, 4)
         self.n_atoms, self.n_bonds, self.n_pairs = int(self.atom_start[-1]), int(self.bond_start[-1]), int(self.pair_start[-1])
         self._tables = {}
+        self.status = None
 
     @staticmethod
     def from_smiles(lines: Sequence[str]) -> "LigandLibrary":
@@ -384,12 +408,72 @@ class LigandLibrary:
         names = ("atom_start", "bond_start", "pair_start", "atoms", "bonds")
         return ops.cached_upload(self._tables, device, lambda up: {k: up(getattr(self, k)) for k in names})
 
-    def features(self, device=None) -> Dict[str, torch.Tensor]:
-        """ONE launch for the whole library -> device tensors `atom_table` int8 [N,16] (`ATOM_COLUMNS`), `pair_table` int8 [P,8]
-        (`PAIR_COLUMNS`), `ref_feat` fp32 [N,167], `rel_tok_feat` fp32 [P,42]; ligand g owns the atom rows atom_start[g] ..
-        atom_start[g+1] and the pair rows pair_start[g] .. pair_start[g+1] (`split`).  `device=None` is the current CUDA device.  Nothing is read back."""
+    def aromaticity(self, mode: str = "normalise", max_steps: int = 65536, device=None) -> Dict[str, torch.Tensor]:
+        """ONE launch of `pd_aromaticity` for the whole library -> device tensors `atoms` int32 [N,4] and `bonds` int32 [B,4] in the
+        layout of the library's own tables (bit 0 of the atom flags and twice the bond order rewritten; bond column 3: bit 0 in a
+        perceived aromatic ring, bit 1 chosen double by the matching), `status` int32 [G] (`AROMATICITY_STATUS`; a ligand with a
+        status other than 0 is copied through unchanged) and `counts` int32 [G,4] (aromatic rings found, aromatic atoms, aromatic
+        bonds, matching steps).  mode: "kekulise", "perceive" (Kekule input) or "normalise" (kekulise, then perceive).  `max_steps`
+        bounds the tries of the matching per ligand.  Nothing is read back."""
+        if mode not in AROMATICITY_MODES:
+            raise ValueError(f"LigandLibrary.aromaticity: mode {mode!r}; one of {sorted(AROMATICITY_MODES)}")
+        if isinstance(max_steps, bool) or int(max_steps) != max_steps or not 0 <= int(max_steps) < 2 ** 31:
+            raise ValueError(f"LigandLibrary.aromaticity: max_steps {max_steps!r}; an integer in 0 .. 2^31 - 1")
         device = _device(device)
         t = self.tables(device)
+        G, N, B = self.n_ligands, self.n_atoms, self.n_bonds
+        out = {"atoms": torch.empty(N, 4, device=device, dtype=torch.int32), "bonds": torch.empty(B, 4, device=device, dtype=torch.int32),
+               "status": torch.empty(G, device=device, dtype=torch.int32), "counts": torch.empty(G, 4, device=device, dtype=torch.int32)}
+        L_ = ops._lib.init()
+        with torch.cuda.device(device):
+            ops.check(L_.pd_aromaticity(ops.ptr(t["atom_start"]), ops.ptr(t["bond_start"]), ops.ptr(t["atoms"]),
+                                        ops.ptr(t["bonds"]) if B else None, ops.ptr(out["atoms"]), ops.ptr(out["bonds"]) if B else None,
+                                        ops.ptr(out["status"]), ops.ptr(out["counts"]), G, N, B, AROMATICITY_MODES[mode], int(max_steps),
+                                        ops.stream()), "pd_aromaticity")
+        return out
+
+    def _rewritten(self, mode: str, device, errors: str, max_steps: int, what: str) -> "LigandLibrary":
+        if errors not in ("raise", "keep"):
+            raise ValueError(f"LigandLibrary.{what}: errors {errors!r}; 'raise' or 'keep'")
+        out = self.aromaticity(mode, max_steps, device)
+        atoms, bonds, status = (out[k].cpu().numpy() for k in ("atoms", "bonds", "status"))      # the one read-back
+        ligands = []
+        for g, lig in enumerate(self.ligands):
+            if status[g]:
+                if errors == "raise":
+                    raise ValueError(f"LigandLibrary.{what}: ligand {g} ({lig.source or 'no source'}): status {int(status[g])}, "
+                                     f"{AROMATICITY_STATUS.get(int(status[g]), 'unknown')}")
+                ligands.append(lig)
+                continue
+            a0, a1, b0, b1 = (int(v) for v in (*self.atom_start[g:g + 2], *self.bond_start[g:g + 2]))
+            ligands.append(Ligand(lig.elements, lig.bonds, 0.5 * bonds[b0:b1, 2], lig.charges, lig.h_count, atoms[a0:a1, 3] & 1, lig.chiral,
+                                  lig.chiral_order, lig.isotopes, source=lig.source))
+        lib = LigandLibrary(ligands)
+        lib.status = _frozen(status, np.int32)
+        return lib
+
+    def aromatized(self, device=None, errors: str = "raise", max_steps: int = 65536) -> "LigandLibrary":
+        """A new library of new ligands with their aromatic rings perceived (`aromaticity("normalise")`, one read-back): aromatic
+        bonds of order 1.5 and the `aromatic` flags rewritten; `h_count`, `charges`, `chiral`, `chiral_order`, `isotopes` and `source`
+        are kept.  errors="raise": a ligand without a Kekule structure (or whose matching ran out of `max_steps`) raises ValueError
+        with its index, source and status; errors="keep": it is left unchanged and reported in `.status` of the result."""
+        return self._rewritten("normalise", device, errors, max_steps, "aromatized")
+
+    def kekulized(self, device=None, errors: str = "raise", max_steps: int = 65536) -> "LigandLibrary":
+        """The same with every aromatic bond written single or double and every `aromatic` flag cleared (`aromaticity("kekulise")`)"""
+        return self._rewritten("kekulise", device, errors, max_steps, "kekulized")
+
+    def features(self, device=None, aromatize: bool = False) -> Dict[str, torch.Tensor]:
+        """ONE launch for the whole library -> device tensors `atom_table` int8 [N,16] (`ATOM_COLUMNS`), `pair_table` int8 [P,8]
+        (`PAIR_COLUMNS`), `ref_feat` fp32 [N,167], `rel_tok_feat` fp32 [P,42]; ligand g owns the atom rows atom_start[g] ..
+        atom_start[g+1] and the pair rows pair_start[g] .. pair_start[g+1] (`split`).  `device=None` is the current CUDA device.  Nothing is read back.
+        `aromatize=True`: `aromaticity("normalise")` first and the features of its tables - two launches, still no read-back - with
+        `aromaticity_status` int32 [G] beside; a ligand whose status is not 0 has the features of its unchanged graph."""
+        device = _device(device)
+        t = self.tables(device)
+        if aromatize:
+            perceived = self.aromaticity("normalise", device=device)
+            t = dict(t, atoms=perceived["atoms"], bonds=perceived["bonds"])
         N, P = self.n_atoms, self.n_pairs
         out = {"atom_table": torch.empty(N, ATOM_ROW, device=device, dtype=torch.int8),
                "pair_table": torch.empty(P, PAIR_ROW, device=device, dtype=torch.int8),
@@ -401,6 +485,8 @@ class LigandLibrary:
                                             ops.ptr(t["bonds"]) if self.n_bonds else None, ops.ptr(out["atom_table"]),
                                             ops.ptr(out["pair_table"]), ops.ptr(out["ref_feat"]), ops.ptr(out["rel_tok_feat"]),
                                             self.n_ligands, N, self.n_bonds, P, ops.stream()), "pd_ligand_features")
+        if aromatize:
+            out["aromaticity_status"] = perceived["status"]
         return out
 
     def split(self, out: Dict[str, torch.Tensor], g: int) -> Dict[str, torch.Tensor]:
