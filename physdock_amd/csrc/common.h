@@ -18,6 +18,17 @@ static inline int pd_check_launch() {
 
 #define PD_LOG2E 1.4426950408889634f
 
+// One IEEE fp32 rounding each, never fused.  The toolchain's __fmul_rn / __fadd_rn are plain `x * y` / `x + y`: once inlined, the
+// default -ffp-contract=fast-honor-pragmas makes one FMA of a product that feeds a sum.  The pragma keeps the operations apart.
+__device__ __forceinline__ float pd_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float pd_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 __device__ __forceinline__ float pd_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float pd_silu(float x) { return x / (1.0f + __expf(-x)); }
 // The same on the hardware reciprocal (v_rcp_f32, 1 ulp) instead of an IEEE division, which hipcc expands into ten VALU instructions

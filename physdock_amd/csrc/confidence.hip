@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void confidence_pair_init_kernel(const float* 
     const int i = (int)(pair / T), j = (int)(pair - (long long)i * T);
     const long long ai = centre[i], aj = centre[j];
     const float dx = x[3 * ai] - x[3 * aj], dy = x[3 * ai + 1] - x[3 * aj + 1], dz = x[3 * ai + 2] - x[3 * aj + 2];
-    const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float d = sqrtf(pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz)));
     int bin = 0;
     float best = fabsf(d - 3.375f);
 #pragma unroll
@@ -64,10 +64,10 @@ __global__ __launch_bounds__(256) void atom_dist_embed_kernel(const float* __res
     const int c = (int)(idx - pair * c4) * 4;
     const int i = (int)(pair / A), j = (int)(pair - (long long)i * A);
     const float dx = x[3 * j] - x[3 * i], dy = x[3 * j + 1] - x[3 * i + 1], dz = x[3 * j + 2] - x[3 * i + 2];
-    const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float d = sqrtf(pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz)));
     f32x4 o;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) o[t] = __fadd_rn(__fmul_rn(d, w[c + t]), b ? b[c + t] : 0.f);
+    for (int t = 0; t < 4; ++t) o[t] = pd_add_rn(pd_mul_rn(d, w[c + t]), b ? b[c + t] : 0.f);
     *reinterpret_cast<f32x4*>(ap + pair * C + c) = o;
 }
 
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void atom_dist_embed_kernel(const float* __res
 // confidence_pair_init_kernel, operation for operation (first minimum wins, as argmin does)
 __device__ __forceinline__ int centre_bin(const float* __restrict__ x, long long ai, long long aj) {
     const float dx = x[3 * ai] - x[3 * aj], dy = x[3 * ai + 1] - x[3 * aj + 1], dz = x[3 * ai + 2] - x[3 * aj + 2];
-    const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float d = sqrtf(pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz)));
     int bin = 0;
     float best = fabsf(d - 3.375f);
 #pragma unroll
@@ -144,10 +144,10 @@ __global__ __launch_bounds__(256) void atom_dist_embed_poses_kernel(const float*
     const int c = (int)(idx - pair * c4) * 4;
     const int i = (int)(pair / A), j = (int)(pair - (long long)i * A);
     const float dx = x[3 * j] - x[3 * i], dy = x[3 * j + 1] - x[3 * i + 1], dz = x[3 * j + 2] - x[3 * i + 2];
-    const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
+    const float d = sqrtf(pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz)));
     f32x4 o;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) o[t] = __fadd_rn(__fmul_rn(d, w[c + t]), b ? b[c + t] : 0.f);
+    for (int t = 0; t < 4; ++t) o[t] = pd_add_rn(pd_mul_rn(d, w[c + t]), b ? b[c + t] : 0.f);
     *reinterpret_cast<f32x4*>(ap + pair * C + c) = o;
 }
 

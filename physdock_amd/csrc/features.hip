@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void msa_feat_kernel(const long long* __restri
     if (c < NC) v = msa[src] == c ? 1.f : 0.f;
     else {
         const float d = deletion[src];
-        v = c == NC ? fminf(fmaxf(d, 0.f), 1.f) : __fmul_rn(atanf(__fdiv_rn(d, 3.f)), two_over_pi);
+        v = c == NC ? fminf(fmaxf(d, 0.f), 1.f) : pd_mul_rn(atanf(__fdiv_rn(d, 3.f)), two_over_pi);
     }
     out[idx] = v;
 }
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(256) void chain_contacts_kernel(const float* __rest
         const float* xa = x + 3 * (long long)(i0 + a);
         const float* xb = x + 3 * (long long)(j0 + b);
         const float dx = xa[0] - xb[0], dy = xa[1] - xb[1], dz = xa[2] - xb[2];
-        const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
-        const float v = __fadd_rn(d, __fmul_rn(1.f - __fmul_rn(a_mask[i0 + a], a_mask[j0 + b]), 1000.f));
+        const float d = sqrtf(pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz)));
+        const float v = pd_add_rn(d, pd_mul_rn(1.f - pd_mul_rn(a_mask[i0 + a], a_mask[j0 + b]), 1000.f));
         if (v < best) { best = v; arg = k; }            // k ascending per thread: the first minimum is kept
     }
     sv[threadIdx.x] = best;

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256) void template_feat_kernel(const float* __restr
     const int i = (int)(idx / T), j = (int)(idx - (long long)i * T);
     const long long ai = pb[i], aj = pb[j];
     const float dx = x[3 * ai] - x[3 * aj], dy = x[3 * ai + 1] - x[3 * aj + 1], dz = x[3 * ai + 2] - x[3 * aj + 2];
-    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    const float d2 = pd_add_rn(pd_add_rn(pd_mul_rn(dx, dx), pd_mul_rn(dy, dy)), pd_mul_rn(dz, dz));
     const float m = z_mask[idx] * (is_prot[i] * is_prot[j]);
     float* o = out + idx * (NB + 1);
     for (int b = 0; b < NB; ++b) {
