@@ -1407,6 +1407,28 @@ int pd_ligand_features(const int* atom_start, const int* bond_start, const long 
 int pd_aromaticity(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds, int* atoms_out, int* bonds_out,
                    int* status, int* counts, int n_ligands, int n_atoms, int n_bonds, int mode, int max_steps, void* stream);
 
+/* ---- double-bond stereo of every pose (bond_stereo.hip; additive export of ABI 11) ---------------------------------------------
+ * Is each stated double bond cis or trans in the pose, and how far is it twisted?  (PoseBusters' double-bond stereo check; the
+ * counterpart of pd_chirality.)  The package's own definition: tests/bond_stereo_ref.py.  x fp32 [n_poses][n_atoms][3]; quads int32
+ * [n_entries][6] = (a, b, c, d, a2, d2), atom indices into the pose: b=c the double bond, a and a2 the substituents of b, d and d2
+ * those of c, a2 / d2 = -1 for none; expect uint8 [n_entries] (1 cis, 2 trans) or NULL to label only; max_twist in degrees.
+ *   dihedral fp32 [n_poses][n_entries]  the IUPAC dihedral a-b-c-d in degrees: b1 = b - a, b2 = c - b, b3 = d - c, m = b1 x b2, n = b2 x b3,
+ *            phi = atan2(|b2| (b1 . n), m . n), in float64 from the fp32 coordinates, every product and sum rounded on its own, the
+ *            result rounded once to fp32; NaN for a coordinate that is not finite or |m|^2, |n|^2 < 1e-12
+ *   twist    fp32 [n_poses][n_entries]  min(|phi|, 180 - |phi|), the largest over the pairs (a, d), (a2, d), (a, d2), (a2, d2) that
+ *            exist (so a pyramidal end shows), rounded once to fp32; NaN when one of them is not defined
+ *   state    uint8 [n_poses][n_entries] 0 undefined (dihedral NaN), 1 cis (m . n > 0), 2 trans (m . n < 0), 3 perpendicular (== 0)
+ *   per pose (each may be NULL): n_wrong int32 = entries with state != expect (without expect: undefined entries), n_twisted int32 =
+ *            entries with twist > max_twist or NaN, max_twist_seen fp32 = the largest twist, NaN if any is NaN, ok int32 = n_wrong == 0
+ * One launch, one 64-lane wave per pose, lane k takes entries k, k + 64, ...; integer sums and an exact maximum over fixed trees, no
+ * atomics: the bits are the same from launch to launch and for a pose alone or in a batch.  An index outside [0, n_atoms) (other
+ * than -1 for a2 / d2) makes its entry undefined and is not followed.  NULL x, quads, dihedral, twist or state, a count < 1, a
+ * misaligned pointer, max_twist < 0 or NaN: PD_ERR_ARG; n_entries > 1024 or n_poses > 65535: PD_ERR_UNSUPPORTED.  A rejected call
+ * launches nothing.                                                                                                               */
+int pd_bond_stereo(const float* x, const int* quads, const unsigned char* expect, float max_twist, float* dihedral, float* twist,
+                   unsigned char* state, int* n_wrong, int* n_twisted, float* max_twist_seen, int* ok, int n_poses, int n_atoms,
+                   int n_entries, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

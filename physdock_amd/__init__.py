@@ -20,6 +20,7 @@ from .metrics import (compute_plddt, compute_predicted_aligned_error, get_has_cl
                       predicted_tm_score)  # (reference data/tools/get_metrics.py; csrc/metrics.hip)
 from .symmetry import LigandSymmetry, automorphisms  # noqa: F401  (symmetry-corrected ligand RMSD for the ranking step; csrc/sym_rmsd.hip)
 from .bestfit import BestFitRmsd  # noqa: F401  (superposed symmetry-corrected ligand RMSD: the conformer accuracy of a pose; csrc/bestfit_rmsd.hip)
+from .bond_stereo import BondStereo  # noqa: F401  (cis / trans and twist of the stated double bonds of every pose; csrc/bond_stereo.hip)
 from .torsions import TorsionFingerprint  # noqa: F401  (torsion angles and torsion-fingerprint deviation of ligand poses; csrc/torsion.hip)
 from .validity import PoseValidity  # noqa: F401  (PoseBusters-style geometry checks of every pose; csrc/validity.hip)
 from .lddt_pli import LddtPli  # noqa: F401  (symmetry-aware lDDT-PLI of every pose against the ground truth; csrc/lddt_pli.hip)

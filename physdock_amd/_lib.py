@@ -310,6 +310,7 @@ def _declare(L):
     sig("pd_pocket_accuracy", p, p, p, p, p, p, p, p, p, p, p, p, d, d, d, d, p, ll, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, p)
     sig("pd_ligand_features", p, p, p, p, p, p, p, p, p, i, i, i, ll, p)                     # ABI 11, additive (ligand_features.hip)
     sig("pd_aromaticity", p, p, p, p, p, p, p, p, i, i, i, i, i, p)                          # ABI 11, additive (aromaticity.hip)
+    sig("pd_bond_stereo", p, p, p, f, p, p, p, p, p, p, p, i, i, i, p)                       # ABI 11, additive (bond_stereo.hip)
 
 
 def ptr(t):

@@ -133,7 +133,7 @@ TETRAHEDRAL_ANGLE = 109.4712
 TETRAHEDRAL_VOLUME = 4.0 / (3.0 * np.sqrt(3.0))
 
 
-def ideal_bounds(ligand) -> Dict[str, object]:
+def ideal_bounds(ligand, smooth: bool = True) -> Dict[str, object]:
     """Bounds without a reference conformer, from a `ligand.Ligand` (host, float64; **the package's own table, unvalidated beyond the
     bond lengths of one crystal ligand**, NOTES.md) -> dict: `lo`, `up` [L,L] smoothed (`smooth_bounds`), `lengths` [n_bonds], `centres`
     int32 [n,4] with `vol_lo`, `vol_hi` [n], `unspecified_centres` (atoms `chirality.centres_from_bonds` finds that carry no `@`).
@@ -143,7 +143,11 @@ def ideal_bounds(ligand) -> Dict[str, object]:
          (`Ligand.perceive`), the regular polygon's 60 / 90 / 108 when both neighbours share a ring of 3 / 4 / 5 atoms with the centre
     1-4  [cis - TOL_14, trans + TOL_14] in closed form from those lengths and angles (several paths: the widest interval); cis +-
          TOL_PLANAR when all four atoms lie in one ring and the central bond is aromatic
+         a double bond with a row (a, b, c, d, kind, a2, d2) in `ligand.bond_stereo`: the pairs (a, d) and (a2, d2) get cis +-
+         TOL_PLANAR when kind is 1 and trans +- TOL_PLANAR when it is 2, the mixed pairs (a, d2) and (a2, d) the other one - the
+         isomer is pinned and the bond planar.  A double bond without a row keeps the wide interval.  `stereo_bonds` returns the rows.
     else [VDW_SCALE (r_i + r_j), UP_FAR] with `validity.VDW_RADII`
+    `smooth=False` returns `lo`, `up` before the triangle smoothing.
     A centre written `@` / `@@` with four substituents, at most one of them a hydrogen: (c, n1, n2, n3) are the heavy neighbours of
     `chiral_order` without the first (with a hydrogen: without it), V = (n1 - c) . ((n2 - c) x (n3 - c)) lies within VOL_RANGE x
     (sign x TETRAHEDRAL_VOLUME x the three ideal lengths); the sign is + for `@@` and - for `@`, reversed when the hydrogen stands at
@@ -201,9 +205,22 @@ def ideal_bounds(ligand) -> Dict[str, object]:
                         put(i, l, 2, cis - TOL_PLANAR, cis + TOL_PLANAR)
                     else:
                         put(i, l, 1, cis - TOL_14, trans + TOL_14)
+    for a, b, c, d, kind, a2, d2 in ligand.bond_stereo.tolist():
+        for i, l, same in ((a, d, True), (a2, d2, True), (a, d2, False), (a2, d, False)):
+            if i < 0 or l < 0:
+                continue
+            la, lb, lc, t1, t2 = length[i, b], length[b, c], length[c, l], angle(i, b, c), angle(b, c, l)
+            along = lb - la * np.cos(t1) - lc * np.cos(t2)
+            cis = float(np.hypot(along, la * np.sin(t1) - lc * np.sin(t2)))
+            trans = float(np.hypot(along, la * np.sin(t1) + lc * np.sin(t2)))
+            mid = cis if (kind == 1) == same else trans
+            if rank[i, l] == 2:                              # the stated arrangement replaces a planar interval, it does not widen it
+                rank[i, l] = rank[l, i] = 1
+            put(i, l, 2, mid - TOL_PLANAR, mid + TOL_PLANAR)
     np.fill_diagonal(lo, 0.0)
     np.fill_diagonal(up, 0.0)
-    lo, up = smooth_bounds(lo, up)
+    if smooth:
+        lo, up = smooth_bounds(lo, up)
 
     centres, vol = [], []
     for c in range(L):
@@ -226,15 +243,17 @@ def ideal_bounds(ligand) -> Dict[str, object]:
     return {"lo": lo, "up": up, "lengths": np.asarray([length[i, j] for i, j in bonds], dtype=np.float64),
             "centres": np.asarray(centres, dtype=np.int32).reshape(-1, 4),
             "vol_lo": np.minimum(VOL_RANGE[0] * vol, VOL_RANGE[1] * vol), "vol_hi": np.maximum(VOL_RANGE[0] * vol, VOL_RANGE[1] * vol),
-            "unspecified_centres": sorted({int(q[0]) for q in found} - written)}
+            "unspecified_centres": sorted({int(q[0]) for q in found} - written), "stereo_bonds": ligand.bond_stereo}
 
 
 class ConformerEnsemble:
     """One ligand's tables for `pd_embed_conformers`, as host copies: `lo`, `up` float64 [L,L] (smoothed), `centres` int32 [n,4],
-    `vol_lo`, `vol_hi` float64 [n]; `box` is the half-width of the start cube, half the largest upper bound."""
+    `vol_lo`, `vol_hi` float64 [n]; `box` is the half-width of the start cube, half the largest upper bound.  `bond_stereo`: None, or
+    the `bond_stereo.BondStereo` of the ligand's stated double bonds that `embed` reports `stereo_ok` by."""
 
-    def __init__(self, lo, up, centres, vol_lo, vol_hi, device=None):
+    def __init__(self, lo, up, centres, vol_lo, vol_hi, device=None, bond_stereo=None):
         self.lo, self.up, self.centres, self.vol_lo, self.vol_hi = lo, up, centres, vol_lo, vol_hi
+        self.bond_stereo = bond_stereo
         self.n_atoms, self.n_centres = int(lo.shape[0]), int(centres.shape[0])
         self.box = 0.5 * float(up.max()) if self.n_atoms > 1 else 1.0
         self._tables = {}
@@ -243,9 +262,10 @@ class ConformerEnsemble:
 
     # ------------------------------------------------------------------ constructors
     @staticmethod
-    def from_tables(lo, up, centres=None, vol_lo=None, vol_hi=None, device=None):
+    def from_tables(lo, up, centres=None, vol_lo=None, vol_hi=None, device=None, bond_stereo=None):
         """lo, up [L,L] (used as they are: symmetric, zero diagonal, 0 < lo <= up off it), centres [n,4] with vol_lo <= vol_hi [n]
-        of one sign each"""
+        of one sign each; bond_stereo: the rows (a, b, c, d, kind, a2, d2) of `ideal_bounds(...)["stereo_bonds"]` or a
+        `bond_stereo.BondStereo` over the L atoms - `embed` then reports `stereo_ok`; it rejects nothing"""
         lo, up = np.ascontiguousarray(_host(lo, np.float64)), np.ascontiguousarray(_host(up, np.float64))
         if lo.ndim != 2 or lo.shape[0] != lo.shape[1] or up.shape != lo.shape:
             raise ValueError(f"ConformerEnsemble: lo {lo.shape} and up {up.shape} must be square and alike")
@@ -268,7 +288,13 @@ class ConformerEnsemble:
             raise ValueError(f"ConformerEnsemble: a centre leaves the {L} atoms or names an atom twice")
         if not np.isfinite(vlo).all() or not np.isfinite(vhi).all() or (vlo > vhi).any() or (vlo * vhi <= 0.0).any():
             raise ValueError("ConformerEnsemble: every centre needs vol_lo <= vol_hi of one sign")
-        return ConformerEnsemble(lo, up, c, vlo, vhi, device)
+        if bond_stereo is not None and not hasattr(bond_stereo, "accept"):
+            from .bond_stereo import BondStereo
+            rows = _host(bond_stereo, np.int64).reshape(-1, 7)
+            bond_stereo = BondStereo(rows[:, [0, 1, 2, 3, 5, 6]], rows[:, 4], L)
+        if bond_stereo is not None and bond_stereo.max_index >= L:
+            raise ValueError(f"ConformerEnsemble: bond_stereo reaches atom {bond_stereo.max_index}, the ligand holds {L}")
+        return ConformerEnsemble(lo, up, c, vlo, vhi, device, bond_stereo)
 
     @staticmethod
     def from_bonds(n_atoms: int, bonds, x_ref, elements, bond_orders=None, planar_groups=None, centres=None, device=None):
@@ -356,7 +382,9 @@ class ConformerEnsemble:
         (`bestfit.BestFitRmsd(symmetry=symmetry).pairwise(x)`) goes through the greedy leader walk of
         `PoseClusters(cutoff=prune_rms).cluster(D, valid=ok)` in conformer order: `kept` [C] (uint8: accepted and a leader) and
         `duplicate_of` [C] (int32: the leader a dropped duplicate lies within prune_rms of, -1 for leaders and rejected rows) are added
-        and `poses` holds the kept rows only.  Without the keyword nothing changes."""
+        and `poses` holds the kept rows only.  Without the keyword nothing changes.
+        An ensemble that was given `bond_stereo` adds `stereo_ok` [C] (uint8: every stated double bond of the conformer is the stated
+        isomer, `BondStereo.accept`); nothing is rejected by it."""
         if keep not in ("ok", None):
             raise ValueError(f"ConformerEnsemble.embed: keep={keep!r}; \"ok\" or None")
         if prune_rms is not None:
@@ -398,6 +426,8 @@ class ConformerEnsemble:
         tail = ws.view(C, -1)[:, 16 * L * L:]             # the workspace's tail: the final 4-D point and its gradient
         out["x4"] = tail[:, :4 * L].reshape(C, L, 4).clone()
         out["grad4"] = tail[:, 4 * L:8 * L].reshape(C, L, 4).clone()
+        if self.bond_stereo is not None:
+            out["stereo_ok"] = self.bond_stereo.accept(out["x"]).to(torch.uint8)
         if prune_rms is not None:
             from .bestfit import BestFitRmsd
             from .clustering import PoseClusters

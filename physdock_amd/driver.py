@@ -35,6 +35,7 @@ from .model import weighted_rigid_align
 from .pdbio import PdbTemplate
 from .ranking import rank_poses
 from .sdfio import check_redock_sdf, score_sdf
+from .bond_stereo import check_redock_bond_stereo, score_bond_stereo
 from .shape import check_redock_shape, score_shape
 from .torsions import check_redock_torsions, score_torsions
 
@@ -93,10 +94,11 @@ def _mol_num_atoms(ref_mol) -> Optional[int]:
     return None
 
 
-def _device_accept(x_pred, chirality, validity):
+def _device_accept(x_pred, chirality, validity, bond_stereo=None):
     """the device half of accept / reject: (per-pose list of bool, or None without a test; number of poses the validity test fails,
-    or None without it) - the chirality mask and the validity mask reach the host in ONE [*, B] read"""
+    or None without it) - the chirality mask, the double-bond stereo mask and the validity mask reach the host in ONE [*, B] read"""
     masks = ([chirality.accept(x_pred)] if chirality is not None else []) + \
+            ([bond_stereo.accept(x_pred)] if bond_stereo is not None else []) + \
             ([validity.check(x_pred)["valid"]] if validity is not None else [])
     if not masks:
         return None, None
@@ -412,7 +414,8 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
            ligand_symmetry=None, validity=None, validity_filter: bool = False, lddt_pli=None, vina=None,
            interactions=None, surface=None, refine=None, clusters=None, ring_interactions=None, hydrogens=None,
            conformers=None, sdf=None, search=None, receptor_geometry=None, conformer_rmsd=None, shape=None,
-           torsions=None, pocket=None, distogram=None, flex=None, flex_search=None, pocket_accuracy=None) -> dict:
+           torsions=None, pocket=None, distogram=None, flex=None, flex_search=None, pocket_accuracy=None, bond_stereo=None,
+           bond_stereo_filter: bool = False) -> dict:
     """One system through the reference's round loop (defaults = redocking.py:33-59).  `batch` holds device tensors
     as for `model.sample_diffusion`; with physics correction it may hold `batch_msa_feat [rounds,S,T,34]`.
     Returns dict(poses [n,A,3] in the ground-truth frame, accepted (count before the top-up), rounds (per-round log),
@@ -536,7 +539,13 @@ def redock(model, batch: Dict[str, torch.Tensor], *, ref_mol=None, ref_mol_poses
     `x_gt`, raises ValueError before anything is sampled): the result gains `pocket_accuracy` = its `score` of the returned `poses` (the
     lDDT of the ligand pocket with the naming swaps, per residue too, and the pocket's CA / backbone / heavy-atom RMSD after the
     superposition of its CA atoms, with the transform); with `sdf=` the records gain the items `lddt_lp` and `pocket_ca_rmsd`.  Nothing
-    else changes."""
+    else changes.
+    `bond_stereo` (a `bond_stereo.BondStereo` of the ligand's stated double bonds, atom indices into the pose; one built over another
+    ligand atom count or reaching past the batch's atoms raises ValueError before anything is sampled): the result gains `bond_stereo`
+    = `state`, `dihedral`, `twist`, `n_wrong`, `n_twisted` and `ok` of its `check` of the returned `poses` (is every stated double bond
+    the cis / trans isomer it was written as, and how far is it twisted); with `sdf=` the records gain the item `stereo_ok`.  With
+    `bond_stereo_filter=True` as well a pose with a wrong isomer is rejected where and when the chirality test rejects (physics
+    correction); its mask joins the chirality and validity masks in the one host read.  Without the keywords nothing changes."""
     keywords = {k: v for k, v in locals().items() if k not in ("model", "batch")}
     st = _RedockState(batch, None, **keywords)
     if confidence is not None and not getattr(model, "supports_conditioning_reuse", False):
@@ -704,7 +713,7 @@ class _RedockState:
                  validity_filter=False, lddt_pli=None, vina=None, interactions=None, surface=None, refine=None, clusters=None,
                  ring_interactions=None, hydrogens=None, conformers=None, sdf=None, search=None, receptor_geometry=None,
                  conformer_rmsd=None, shape=None, torsions=None, pocket=None, distogram=None, flex=None, flex_search=None,
-                 pocket_accuracy=None):
+                 pocket_accuracy=None, bond_stereo=None, bond_stereo_filter=False):
         # (the keywords of redock, no others: a misspelt one raises TypeError; each is kept under its own name.  steps and the schedule
         #  power go to the sampler from the caller)
         vars(self).update({k: v for k, v in locals().items() if k not in ("self", "batch", "pbatch")})
@@ -722,6 +731,7 @@ class _RedockState:
         check_flex(flex, batch)
         check_conformer_rmsd(conformer_rmsd, batch)
         check_redock_sdf(sdf, batch, hydrogens)
+        check_redock_bond_stereo(bond_stereo, bond_stereo_filter, batch)
         self.pool_log = None
         if physics_correction and ref_mol_poses is None and conformers is not None:
             ref_mol_poses, self.pool_log = conformer_pool(conformers, batch, seed)
@@ -779,7 +789,8 @@ class _RedockState:
         # on the device when a ChiralityReference or a validity filter is given (one [*, B] mask to the host), and / or through the
         # injected per-pose callable (which needs the poses on the host)
         pc = self.physics_correction
-        dev_ok, n_invalid = _device_accept(x_pred, self.chirality, self.validity if self.validity_filter else None) if pc else (None, None)
+        dev_ok, n_invalid = _device_accept(x_pred, self.chirality, self.validity if self.validity_filter else None,
+                                           self.bond_stereo if self.bond_stereo_filter else None) if pc else (None, None)
         x_cpu = x_pred.cpu() if (pc and self.accept_fn is not None) else x_pred
         flags = []
         for b, (x, xc) in enumerate(zip(x_pred, x_cpu)):
@@ -847,6 +858,8 @@ class _RedockState:
             out.update(score_receptor_geometry(self.receptor_geometry, aligned, batch, out))
         if self.pocket_accuracy is not None:
             out["pocket_accuracy"] = self.pocket_accuracy.score(aligned)
+        if self.bond_stereo is not None:
+            out.update(score_bond_stereo(self.bond_stereo, aligned))
         if self.pool_log is not None:
             out["conformers"] = self.pool_log
         if self.surface is not None:

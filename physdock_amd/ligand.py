@@ -38,8 +38,14 @@ first perfect matching of the atoms that need a double bond, so it depends on th
 indolizine only in its five-ring (RDKit perceives both through the fused envelope); no tautomers; a double bond that lies in some
 other, non-aromatic ring still counts as cyclic.
 
-**Caveats.**  No aromaticity perception and no kekulisation by default (above).  Double-bond stereo is
-ignored.  Ring sizes are those of chordless cycles, not of RDKit's ring set (they agree on ordinary ring systems, not on cages).
+**Double-bond stereo.**  `bond_stereo` holds the cis / trans arrangement of the double bonds a SMILES string marks with `/` and `\\`
+(`from_graph(bond_stereo=)`, `from_sdf(stereo="coords")` give it too); `conformers.ideal_bounds` pins those bonds, so `embed_reference`
+returns the stated isomer, and `bond_stereo.BondStereo` reads the arrangement off every pose (kernel `pd_bond_stereo`).  The feature
+tables hold no bond stereo, as the reference's do not.  cis / trans relative to the lowest-index substituents, not CIP E / Z.
+
+**Caveats.**  No aromaticity perception and no kekulisation by default (above).  A stereogenic double bond without marks
+(`unspecified_stereo_bonds`) comes out as either isomer and at any twist.  Ring sizes are those of chordless cycles, not of RDKit's
+ring set (they agree on ordinary ring systems, not on cages).
 Hybridisation and conjugation are the rules above, not RDKit's.  The conformer has no torsion preferences and no force-field clean-up.
 Limits: 1 .. 128 atoms and up to 512 bonds per ligand, up to 65535 ligands per launch.  Out of scope: the CCD lookup, MSA features,
 `FeatureLoader.load`."""
@@ -55,7 +61,7 @@ from .pdbio import ELEMENTS
 from .smiles import MAX_ATOMS, NORMAL_VALENCES, implicit_hydrogens, parse_smiles
 
 __all__ = ["Ligand", "LigandLibrary", "ATOM_COLUMNS", "PAIR_COLUMNS", "MAX_ATOMS", "MAX_BONDS", "MAX_LIGANDS", "GROUP_ELECTRONS",
-           "chordless_rings", "AROMATICITY_MODES", "AROMATICITY_STATUS"]
+           "chordless_rings", "AROMATICITY_MODES", "AROMATICITY_STATUS", "stereo_bonds_from_bonds", "normalise_bond_stereo"]
 
 MAX_BONDS, MAX_LIGANDS = 512, 65535
 #: columns of the kernel's int8 tables (rows of 16 per atom and of 8 per atom pair; the rest is zero)
@@ -121,6 +127,83 @@ def chordless_rings(n_atoms: int, bonds, max_size: int = 8) -> List[tuple]:
     return sorted(found)
 
 
+def stereo_bonds_from_bonds(n_atoms: int, bonds, bond_orders, elements, h_count) -> List[tuple]:
+    """The stereogenic double bonds of a graph over heavy atoms as sorted pairs (b, c), b < c: the order is 2.0; both ends are C or N;
+    each end has 1 or 2 heavy substituents besides the partner, at most one hydrogen, no more than two substituents in all and no
+    second bond of an order above 1; at an end with two heavy substituents the two lie in different classes of
+    `chirality.symmetry_classes`; and the bond lies in no chordless ring of at most 7 atoms (`chordless_rings`)."""
+    from .chirality import symmetry_classes
+    n = int(n_atoms)
+    pairs = [(int(i), int(j)) for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2).tolist()]
+    orders = [float(o) for o in np.asarray(bond_orders, dtype=np.float64).reshape(-1)]
+    z = [int(e) for e in np.asarray(elements).reshape(-1)]
+    h = [int(v) for v in np.asarray(h_count).reshape(-1)]
+    if not any(o == 2.0 for o in orders):
+        return []
+    nbr = [{} for _ in range(n)]
+    for (i, j), o in zip(pairs, orders):
+        nbr[i][j] = o; nbr[j][i] = o
+    cls = symmetry_classes(n, pairs, z, orders)
+    in_ring = set()
+    for ring in chordless_rings(n, pairs, max_size=7):
+        for k in range(len(ring)):
+            i, j = ring[k], ring[(k + 1) % len(ring)]
+            in_ring.add((min(i, j), max(i, j)))
+    out = []
+    for (i, j), o in zip(pairs, orders):
+        b, c = min(i, j), max(i, j)
+        if o != 2.0 or (b, c) in in_ring:
+            continue
+        for u, v in ((b, c), (c, b)):
+            subs = [w for w in nbr[u] if w != v]
+            if z[u] not in (6, 7) or not 1 <= len(subs) <= 2 or h[u] > 1 or len(subs) + h[u] > 2:
+                break
+            if any(nbr[u][w] > 1.0 for w in subs) or (len(subs) == 2 and cls[subs[0]] == cls[subs[1]]):
+                break
+        else:
+            out.append((b, c))
+    return sorted(out)
+
+
+def normalise_bond_stereo(n_atoms: int, bonds, rows) -> np.ndarray:
+    """rows (a, b, c, d, kind[, a2, d2]) - a any heavy substituent of b, d any of c, kind 1 cis / 2 trans of a against d - as the int32
+    [n,7] table (a, b, c, d, kind, a2, d2) of `smiles.parse_smiles`: b < c, a and d the lowest substituents of b and c (kind flipped
+    once for every end whose lowest substituent is not the one named), a2 and d2 the other substituent or -1, sorted by (b, c).  Only
+    the first five columns are read.  ValueError for atoms that are not bonded as stated, a kind other than 1 or 2, an end with no or
+    more than two substituents, and a bond named twice."""
+    n = int(n_atoms)
+    rows = np.asarray([] if rows is None else rows, dtype=np.int64)
+    if rows.size == 0:
+        return _frozen(np.zeros((0, 7)), np.int32)
+    if rows.ndim != 2 or rows.shape[1] not in (5, 7):
+        raise ValueError(f"bond_stereo: rows of (a, b, c, d, kind), got an array of shape {rows.shape}")
+    nbr = [set() for _ in range(n)]
+    for i, j in np.asarray(bonds, dtype=np.int64).reshape(-1, 2).tolist():
+        nbr[i].add(j); nbr[j].add(i)
+    out = {}
+    for a, b, c, d, kind in rows[:, :5].tolist():
+        if min(a, b, c, d) < 0 or max(a, b, c, d) >= n:
+            raise ValueError(f"bond_stereo: the row {(a, b, c, d, kind)} leaves the {n} atoms")
+        if b > c:
+            a, b, c, d = d, c, b, a
+        if c not in nbr[b] or a not in nbr[b] or d not in nbr[c] or a == c or d == b:
+            raise ValueError(f"bond_stereo: the atoms of the row {(a, b, c, d, kind)} are not bonded a-b=c-d")
+        if kind not in (1, 2):
+            raise ValueError(f"bond_stereo: kind {kind} of the bond ({b}, {c}); 1 is cis, 2 is trans")
+        if (b, c) in out:
+            raise ValueError(f"bond_stereo: two rows for the bond ({b}, {c})")
+        ends = []
+        for u, v, named in ((b, c, a), (c, b, d)):
+            subs = sorted(nbr[u] - {v})
+            if not 1 <= len(subs) <= 2:
+                raise ValueError(f"bond_stereo: atom {u} of the bond ({b}, {c}) has {len(subs)} substituents; 1 or 2 are taken")
+            if subs[0] != named:
+                kind = 3 - kind
+            ends.append((subs[0], subs[1] if len(subs) == 2 else -1))
+        out[b, c] = (ends[0][0], b, c, ends[1][0], kind, ends[0][1], ends[1][1])
+    return _frozen([out[k] for k in sorted(out)], np.int32).reshape(-1, 7)
+
+
 def _valence_rule(elements, bonds, bond_orders, charges):
     """`smiles.implicit_hydrogens` per atom of a graph without written hydrogen counts.  A charge moves the valence it is measured
     against: a cation of group 15 / 16 has one more, an anion one fewer, any other charged atom one fewer."""
@@ -151,9 +234,13 @@ def _frozen(a, dtype):
 class Ligand:
     """One ligand's graph over its heavy atoms, immutable: `elements` (atomic numbers), `bonds` int64 [n,2], `bond_orders` float64,
     `charges`, `h_count`, `aromatic` (bool), `chiral` (0 none, 1 `@`, 2 `@@`), `chiral_order` (atom -> its neighbours in OpenSMILES
-    order, -1 a hydrogen; only what a SMILES string gives) and `isotopes`."""
+    order, -1 a hydrogen; only what a SMILES string gives), `isotopes` and `bond_stereo`: int32 [n,7] rows (a, b, c, d, kind, a2, d2)
+    of the double bonds whose cis / trans arrangement is stated (`smiles.parse_smiles`; given as (a, b, c, d, kind) they are
+    normalised by `normalise_bond_stereo`), empty by default.  A row on a bond that `stereo_bonds_from_bonds` does not list raises;
+    `unspecified_stereo_bonds` are the listed bonds without a row."""
 
-    def __init__(self, elements, bonds, bond_orders, charges, h_count, aromatic, chiral, chiral_order=None, isotopes=None, source=""):
+    def __init__(self, elements, bonds, bond_orders, charges, h_count, aromatic, chiral, chiral_order=None, isotopes=None, source="",
+                 bond_stereo=None):
         self.elements = _frozen(elements, np.int64).reshape(-1)
         L = self.n_atoms = int(self.elements.shape[0])
         if not 1 <= L <= MAX_ATOMS:
@@ -196,6 +283,12 @@ class Ligand:
                     reach.add(c); todo.append(c)
         if len(reach) != L:
             raise ValueError(f"Ligand: the graph is not connected: atom {min(set(range(L)) - reach)} cannot be reached from atom 0")
+        self.bond_stereo = normalise_bond_stereo(L, self.bonds, bond_stereo)
+        self._stereo_bonds = None
+        for row in self.bond_stereo.tolist():
+            if (row[1], row[2]) not in self.stereo_bonds():
+                raise ValueError(f"Ligand: bond_stereo names the bond ({row[1]}, {row[2]}), which is not stereogenic "
+                                 "(`stereo_bonds_from_bonds`)")
         self._features = {}
 
     # ------------------------------------------------------------------ constructors
@@ -203,19 +296,25 @@ class Ligand:
     def from_smiles(text: str) -> "Ligand":
         r = parse_smiles(text)
         return Ligand(r["elements"], r["bonds"], r["bond_orders"], r["charges"], r["h_count"], r["aromatic"], r["chiral"],
-                      r["chiral_order"], r["isotopes"], source=text.strip())
+                      r["chiral_order"], r["isotopes"], source=text.strip(), bond_stereo=r["bond_stereo"])
 
     @staticmethod
-    def from_graph(elements, bonds, bond_orders, charges=None, h_count=None, aromatic=None, chiral=None) -> "Ligand":
-        """elements: atomic numbers or symbols; `h_count=None` uses the valence rule of `smiles.parse_smiles`"""
+    def from_graph(elements, bonds, bond_orders, charges=None, h_count=None, aromatic=None, chiral=None, bond_stereo=None) -> "Ligand":
+        """elements: atomic numbers or symbols; `h_count=None` uses the valence rule of `smiles.parse_smiles`; `bond_stereo`: rows
+        (a, b, c, d, kind), kind 1 cis / 2 trans of the substituent a of b against the substituent d of c"""
         z = [(_SYMBOL_Z.get(e.strip().upper(), 0) if isinstance(e, str) else int(e)) for e in (elements.tolist() if hasattr(elements, "tolist") else elements)]
         bonds = np.asarray(bonds.tolist() if hasattr(bonds, "tolist") else list(bonds), dtype=np.int64).reshape(-1, 2)
         orders = np.ones(len(bonds)) if bond_orders is None else np.asarray(bond_orders, dtype=np.float64)
-        return Ligand(z, bonds, orders, charges, h_count, aromatic, chiral)
+        return Ligand(z, bonds, orders, charges, h_count, aromatic, chiral, bond_stereo=bond_stereo)
 
     @staticmethod
-    def from_sdf(record: dict) -> "Ligand":
-        """a `sdfio.parse_sdf` record; its hydrogens on heavy atoms are folded into `h_count`, the heavy atoms keep their order"""
+    def from_sdf(record: dict, stereo: Optional[str] = None, device=None) -> "Ligand":
+        """a `sdfio.parse_sdf` record; its hydrogens on heavy atoms are folded into `h_count`, the heavy atoms keep their order.
+        `stereo="coords"`: every stereogenic double bond (`stereo_bonds_from_bonds`) is labelled cis / trans from the record's 3-D
+        coordinates (`bond_stereo.BondStereo.label`, one launch and one read of the labels); a bond whose dihedral is undefined or
+        exactly perpendicular stays unspecified.  The default reads no stereo."""
+        if stereo not in (None, "coords"):
+            raise ValueError(f"Ligand.from_sdf: stereo={stereo!r}; None or \"coords\"")
         z = np.asarray([_SYMBOL_Z.get(str(e).strip().upper(), 0) for e in record["elements"]], dtype=np.int64)
         bonds = np.asarray(record["bonds"], dtype=np.int64).reshape(-1, 2)
         orders = np.asarray(record["bond_orders"], dtype=np.float64).reshape(-1)
@@ -233,8 +332,18 @@ class Ligand:
         new_id = np.cumsum(~folded) - 1
         keep_b = ~folded[bonds[:, 0]] & ~folded[bonds[:, 1]] if len(bonds) else np.zeros(0, dtype=bool)
         h = _valence_rule(z, bonds, orders, charges)[~folded] + extra[~folded]      # the bonds to the folded hydrogens count as bonds
-        return Ligand(z[~folded], new_id[bonds[keep_b]].reshape(-1, 2), orders[keep_b], charges[~folded], h, None, None,
-                      source=str(record.get("title", "")))
+        lig = Ligand(z[~folded], new_id[bonds[keep_b]].reshape(-1, 2), orders[keep_b], charges[~folded], h, None, None,
+                     source=str(record.get("title", "")))
+        if stereo is None or not lig.stereo_bonds():
+            return lig
+        from .bond_stereo import BondStereo
+        nbr = lig.neighbours()
+        rows = [(min(w for w in nbr[b] if w != c), b, c, min(w for w in nbr[c] if w != b), 1) for b, c in lig.stereo_bonds()]
+        x = torch.as_tensor(np.asarray(record["coords"], dtype=np.float32)[~folded], device=_device(device))
+        state = BondStereo.from_tables(np.asarray(normalise_bond_stereo(lig.n_atoms, lig.bonds, rows))[:, [0, 1, 2, 3, 5, 6]],
+                                       None).label(x[None])[0].tolist()           # the one read-back
+        rows = [r[:4] + (s,) for r, s in zip(rows, state) if s in (1, 2)]
+        return Ligand(lig.elements, lig.bonds, lig.bond_orders, lig.charges, lig.h_count, None, None, source=lig.source, bond_stereo=rows)
 
     # ------------------------------------------------------------------ the graph
     def neighbours(self) -> List[List[int]]:
@@ -249,6 +358,18 @@ class Ligand:
 
     def symbols(self) -> List[str]:
         return [ELEMENTS[int(z) - 1] for z in self.elements]
+
+    def stereo_bonds(self) -> List[tuple]:
+        """`stereo_bonds_from_bonds` of this graph: the double bonds (b, c) that can be cis or trans (computed once)"""
+        if self._stereo_bonds is None:
+            self._stereo_bonds = tuple(stereo_bonds_from_bonds(self.n_atoms, self.bonds, self.bond_orders, self.elements, self.h_count))
+        return list(self._stereo_bonds)
+
+    @property
+    def unspecified_stereo_bonds(self) -> List[tuple]:
+        """the stereogenic double bonds (b, c) that `bond_stereo` has no row for"""
+        stated = {(r[1], r[2]) for r in self.bond_stereo.tolist()}
+        return [bc for bc in self.stereo_bonds() if bc not in stated]
 
     def perceive(self) -> Dict[str, np.ndarray]:
         """what `conformers.ideal_bounds` needs, by the rules of the module docstring on the host: `hybridization` [L], `conjugated`
@@ -305,7 +426,7 @@ class Ligand:
             pos = torch.zeros(1, 3, device=device)
             index, err, viol, n_ok = 0, 0.0, 0.0, 1
         else:
-            ens = ConformerEnsemble.from_tables(t["lo"], t["up"], t["centres"], t["vol_lo"], t["vol_hi"])
+            ens = ConformerEnsemble.from_tables(t["lo"], t["up"], t["centres"], t["vol_lo"], t["vol_hi"])       # (the bounds pin bond_stereo)
             out = ens.embed(int(C), int(seed), keep=None, device=device)
             ok, errs = out["ok"].cpu().numpy().astype(bool), out["err"].cpu().numpy()
             if not ok.any():
@@ -446,8 +567,14 @@ class LigandLibrary:
                 ligands.append(lig)
                 continue
             a0, a1, b0, b1 = (int(v) for v in (*self.atom_start[g:g + 2], *self.bond_start[g:g + 2]))
-            ligands.append(Ligand(lig.elements, lig.bonds, 0.5 * bonds[b0:b1, 2], lig.charges, lig.h_count, atoms[a0:a1, 3] & 1, lig.chiral,
-                                  lig.chiral_order, lig.isotopes, source=lig.source))
+            orders = 0.5 * bonds[b0:b1, 2]
+            double = {(min(i, j), max(i, j)) for (i, j), o in zip(lig.bonds.tolist(), orders.tolist()) if o == 2.0}
+            stereo = [r for r in lig.bond_stereo.tolist() if (r[1], r[2]) in double]      # a row whose bond is no longer double is dropped
+            if stereo:                                                                    # ... or no longer stereogenic in the new orders
+                still = set(stereo_bonds_from_bonds(lig.n_atoms, lig.bonds, orders, lig.elements, lig.h_count))
+                stereo = [r for r in stereo if (r[1], r[2]) in still]
+            ligands.append(Ligand(lig.elements, lig.bonds, orders, lig.charges, lig.h_count, atoms[a0:a1, 3] & 1, lig.chiral,
+                                  lig.chiral_order, lig.isotopes, source=lig.source, bond_stereo=stereo))
         lib = LigandLibrary(ligands)
         lib.status = _frozen(status, np.int32)
         return lib

@@ -444,7 +444,7 @@ def redock_items(out) -> Dict[str, object]:
     `conformer_rmsd` (`conformer_rmsd["to_gt"]`), with `shape=` `shape_tanimoto` and `tanimoto_combo` (`shape["shape_tanimoto"]`,
     `shape["combo"]`), with `torsions=` and the ground truth `tfd` (`torsions["to_gt"]`), with `distogram=` `distogram_nll`
     (`distogram["nll_interface"]`), with `pocket_accuracy=` `lddt_lp` and `pocket_ca_rmsd` (`pocket_accuracy["lddt_lp"]`,
-    `pocket_accuracy["ca_rmsd"]`)"""
+    `pocket_accuracy["ca_rmsd"]`), with `bond_stereo=` `stereo_ok` (`bond_stereo["ok"]`)"""
     n = int(out["poses"].shape[0])
     items: Dict[str, object] = {"pose": torch.arange(n, dtype=torch.int32, device=out["poses"].device)}
     if "confidence" in out:
@@ -471,6 +471,8 @@ def redock_items(out) -> Dict[str, object]:
     if "pocket_accuracy" in out:
         items["lddt_lp"] = out["pocket_accuracy"]["lddt_lp"]
         items["pocket_ca_rmsd"] = out["pocket_accuracy"]["ca_rmsd"].contiguous()
+    if "bond_stereo" in out:
+        items["stereo_ok"] = out["bond_stereo"]["ok"]
     return items
 
 

@@ -4,7 +4,7 @@ of this package, so this is **the package's own reader, not RDKit's**: it reads 
 
 Grammar: the organic subset `B C N O P S F Cl Br I` and the aromatic `b c n o p s`; bracket atoms `[isotope symbol @|@@ Hn charge :class]`
 with any element symbol of `pdbio.ELEMENTS` (and the aromatic `se`, `as`), the charge as `+`, `-`, `++`, `--`, `+2`, `-2` ..., the class
-read and dropped; the bonds `- = # :` and the directional `/` and `\\`, which are read as single (**double-bond stereo is ignored**);
+read and dropped; the bonds `- = # :` and the directional `/` and `\\`, which are single bonds whose direction is kept (below);
 branches; ring closures `0`-`9` and `%nn` with an optional bond symbol on either end (two different symbols raise).
 
 The result has the shape of a `sdfio.parse_sdf` record, over the heavy atoms in their order of appearance: `elements` (atomic numbers),
@@ -12,6 +12,17 @@ The result has the shape of a `sdfio.parse_sdf` record, over the heavy atoms in 
 `aromatic` (as written), `h_count`, `isotopes`, `chiral` (0 none, 1 `@`, 2 `@@`) and `chiral_order`: for every atom written with `@` or
 `@@` its neighbours in OpenSMILES order - the preceding atom, an implicit hydrogen as -1, the ring-closure partners in the order their
 digits stand on the atom, then the branches and the chain.
+
+Double-bond stereo.  Between an atom u in front and an atom v behind (a branch atom included) `/` says "v is up from u, u is down
+from v" and `\\` the opposite; a symbol in front of a ring-closure digit is read from the atom in front of it to the ring partner, so
+the two ends of one ring closure agree when they carry opposite characters (equal ones raise).  A double bond b=c with a marked
+substituent a of b and a marked substituent d of c is cis when a seen from b and d seen from c are both up or both down, else trans:
+`F/C=C/F` is trans, `F/C=C\\F` cis, `C(\\F)=C/F` is `F/C=C/F`.  The key `bond_stereo` holds int32 [n,7] rows (a, b, c, d, kind, a2, d2)
+over the heavy atoms, sorted by (b, c) with b < c: a and d are the LOWEST heavy substituents of b and c, a2 and d2 the other one or -1,
+kind is 1 cis / 2 trans of a against d (flipped once for every end whose lowest substituent is not the marked one).  A mark on a bond
+to a folded `[H]` is passed on, inverted, to that atom's other substituent.  Two marks on one end that say the same raise.  Marks
+on one end only, marks next to no double bond and marks on a bond that `ligand.stereo_bonds_from_bonds` does not list (a ring of at
+most 7 atoms, two substituents no walk of the graph tells apart) give no row.  cis / trans, not CIP E / Z.
 
 Hydrogens.  An explicit `[H]` bonded to one heavy atom is folded into that atom's `h_count` (the reference's `RemoveAllHs`) and stands
 as -1 in a `chiral_order`; hydrogens bonded to each other raise.  A bracket atom has exactly the hydrogens written.  An atom of the
@@ -43,6 +54,8 @@ _ORGANIC = ("Cl", "Br", "B", "C", "N", "O", "P", "S", "F", "I")
 _AROMATIC = {"b": 5, "c": 6, "n": 7, "o": 8, "p": 15, "s": 16}
 _AROMATIC_BRACKET = dict(_AROMATIC, se=34, **{"as": 33})
 _BOND = {"-": 1.0, "=": 2.0, "#": 3.0, ":": 1.5, "/": 1.0, "\\": 1.0}
+#: the atom behind a directional bond seen from the atom in front of it: +1 up, -1 down
+_DIRECTION = {"/": 1, "\\": -1}
 
 
 def implicit_hydrogens(z: int, order_sum: float, aromatic_bonds: int = 0, n_bonds: int = 0) -> int:
@@ -76,6 +89,7 @@ def parse_smiles(text: str) -> Dict[str, object]:
     atoms: List[list] = []
     nbrs: List[list] = []                                # per atom, in OpenSMILES order: atom ids, -1, or ("ring", key) until closed
     bonds: List[list] = []                               # [i, j, order or None (unmarked), position]
+    marks: List[tuple] = []                              # per bond: (j seen from i: +1 up, -1 down, 0 unmarked; position of the symbol)
     rings: Dict[int, tuple] = {}                         # open digits: number -> (atom, symbol or None, position, slot in nbrs)
     stack: List[tuple] = []
     prev, pending, pending_at = -1, None, -1
@@ -88,6 +102,7 @@ def parse_smiles(text: str) -> Dict[str, object]:
         a = len(atoms) - 1
         if prev >= 0:
             bonds.append([prev, a, pending, at])
+            marks.append((_DIRECTION.get(pending, 0), pending_at))
             nbrs[prev].append(a)
             nbrs[a].append(prev)
         elif pending is not None:
@@ -187,11 +202,17 @@ def parse_smiles(text: str) -> Dict[str, object]:
             if prev < 0:
                 fail(at, "a ring-closure digit with no atom in front of it")
             if num in rings:
-                a, sym, _, slot = rings.pop(num)
+                a, sym, opened, slot = rings.pop(num)
                 if a == prev:
                     fail(at, f"ring closure {num} bonds an atom to itself")
                 if sym is not None and pending is not None and _BOND[sym] != _BOND[pending]:
                     fail(at, f"ring closure {num} is written with {sym!r} on one end and {pending!r} on the other")
+                # the opening end reads a -> prev, the closing end prev -> a: the same direction in opposite characters
+                way, back = _DIRECTION.get(sym, 0), -_DIRECTION.get(pending, 0)
+                if way and back and way != back:
+                    fail(at, f"ring closure {num} is written with {sym!r} on both ends: the two ends of one ring bond say the same "
+                             "with opposite characters")
+                marks.append((way, opened - 1) if way else (back, pending_at))
                 sym = pending if sym is None else sym
                 bonds.append([a, prev, sym, at])
                 nbrs[a][slot] = prev
@@ -272,7 +293,7 @@ def parse_smiles(text: str) -> Dict[str, object]:
     for a in keep:
         if atoms[a][5]:
             chiral_order[int(new_id[a])] = [-1 if (c == -1 or folded[c]) else int(new_id[c]) for c in nbrs[a]]
-    return {
+    record = {
         "elements": np.asarray([atoms[a][0] for a in keep], dtype=np.int64),
         "bonds": np.asarray([(new_id[i], new_id[j]) for _, i, j in kept_bonds], dtype=np.int64).reshape(-1, 2),
         "bond_orders": np.asarray([orders[b] for b, _, _ in kept_bonds], dtype=np.float64),
@@ -283,3 +304,36 @@ def parse_smiles(text: str) -> Dict[str, object]:
         "chiral": np.asarray([atoms[a][5] for a in keep], dtype=np.int64),
         "chiral_order": chiral_order,
     }
+    # double-bond stereo: what every end of a double bond says of its substituents, then the rows of the stereogenic bonds
+    seen_from = {}                                       # (u, v) -> (v seen from u, position)
+    for (i, j, _, _), (way, at) in zip(bonds, marks):
+        if way:
+            seen_from[i, j], seen_from[j, i] = (way, at), (-way, at)
+    marked = []                                          # (a, b, c, d, kind) over the heavy atoms, a and d the marked substituents
+    for b, (i, j, _, _) in enumerate(bonds):
+        if orders[b] != 2.0 or folded[i] or folded[j]:
+            continue
+        ends = []
+        for u, v in ((i, j), (j, i)):
+            heavy = sorted(w for w in adj[u] if w != v and not folded[w])
+            said = {w: seen_from[u, w] for w in heavy if (u, w) in seen_from}
+            for h in sorted(w for w in adj[u] if w != v and folded[w] and (u, w) in seen_from):
+                way, at = seen_from[u, h]
+                if len(heavy) == 1:                      # the hydrogen's mark, inverted, on the one other substituent
+                    if heavy[0] in said and said[heavy[0]][0] != -way:
+                        fail(max(at, said[heavy[0]][1]), f"the two marks at the atom written at {atoms[u][6] + lead} contradict each other")
+                    said.setdefault(heavy[0], (-way, at))
+            if len(heavy) == 2 and len(said) == 2 and said[heavy[0]][0] == said[heavy[1]][0]:
+                fail(max(said[heavy[0]][1], said[heavy[1]][1]),
+                     f"the two marks at the atom written at {atoms[u][6] + lead} contradict each other: both substituents "
+                     f"{'up' if said[heavy[0]][0] > 0 else 'down'}")
+            ends.append(min(said.items()) if said else None)
+        if ends[0] is not None and ends[1] is not None:
+            (a, (up_a, _)), (d, (up_d, _)) = ends
+            marked.append((int(new_id[a]), int(new_id[i]), int(new_id[j]), int(new_id[d]), 1 if up_a == up_d else 2))
+    from .ligand import normalise_bond_stereo, stereo_bonds_from_bonds
+    if marked:
+        stereogenic = set(stereo_bonds_from_bonds(len(keep), record["bonds"], record["bond_orders"], record["elements"], record["h_count"]))
+        marked = [r for r in marked if (min(r[1], r[2]), max(r[1], r[2])) in stereogenic]
+    record["bond_stereo"] = normalise_bond_stereo(len(keep), record["bonds"], marked)
+    return record
