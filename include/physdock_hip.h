@@ -1429,6 +1429,52 @@ int pd_bond_stereo(const float* x, const int* quads, const unsigned char* expect
                    unsigned char* state, int* n_wrong, int* n_twisted, float* max_twist_seen, int* ok, int n_poses, int n_atoms,
                    int n_entries, void* stream);
 
+/* ---- circular fingerprints of ligand graphs and their comparison (fingerprint.hip; additive exports of ABI 11) -----------------
+ * Which ligands of a library are near-duplicates, which are closest to a known binder, which diverse few should be docked first?
+ * Morgan / ECFP-like fingerprints after Rogers & Hahn 2010 and Tanimoto similarity - the package's own definition, not RDKit's bytes:
+ * tests/fingerprint_ref.py.  Hash arithmetic mod 2^32: fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >>
+ * 16;  push(h, v) = fmix(h * 0x01000193 + v + 0x9E3779B9).
+ *
+ * pd_morgan_fingerprint: the tables of pd_ligand_features (atom_start, bond_start int32 [G+1], atoms int32 [n_atoms][4] = Z, charge,
+ * h_count, flags; bonds int32 [n_bonds][4] = i, j, o2, -), one launch, one block per ligand.  id_0(a) = push chained from 0 over Z,
+ * heavy degree, h_count, charge, in-ring (a bond of the atom is no bridge), flags & 1 - or atom_invariants[a] (uint32 [n_atoms]) when
+ * that pointer is not NULL.  id_r(a), r = 1 .. radius: push chained from 0 over r, id_{r-1}(a) and the neighbours' pairs (o2, id_{r-1})
+ * in ascending order, o2 then id.  env_r(a), a set of the ligand's bonds: env_0 empty, env_r(a) = env_{r-1}(a) | union over neighbours
+ * b of (env_{r-1}(b) | {bond a-b}).  Every radius-0 feature is kept; (a, r), r >= 1, exactly when no feature (a', r'), r' >= 1, with the
+ * same bond set has a smaller (r', id, a'); every atom iterates to the last radius.  A kept feature sets bit id & (n_bits - 1).
+ *   bits uint32 [G][n_bits / 32] (bit k = bit k % 32 of word k / 32), ids uint32 [n_atoms][radius + 1], kept uint8 [n_atoms][radius + 1],
+ *   n_features int32 [G] (kept features), popcount int32 [G]
+ * Integers only, no atomics but an LDS OR into the bit row: a ligand's bits do not depend on the library around it.  Limits as for
+ * pd_ligand_features; a ligand whose rows leave the arrays is not written and a bond that leaves its ligand is skipped.  A NULL pointer
+ * (bonds may be NULL when n_bonds == 0, atom_invariants always), a misaligned pointer, n_ligands < 1, n_atoms < n_ligands, a radius
+ * outside 0 .. PD_FINGERPRINT_MAX_RADIUS, n_bits other than 512, 1024, 2048, 4096: PD_ERR_ARG; n_ligands > 65535 or more atoms than
+ * that many ligands of the largest size: PD_ERR_UNSUPPORTED.
+ *
+ * pd_fingerprint_tanimoto: a uint32 [n][n_words], b uint32 [m][n_words] -> sim fp32 [n][m] and, when not NULL, common int32 [n][m].
+ * With c = popcount(a & b) and u = popcount(a) + popcount(b) - c the value is the IEEE fp32 quotient (float)c / (float)u; an empty
+ * union gives 1, as pd_plif_pairwise does.
+ * pd_fingerprint_nearest: for each row of a the k rows of b of the largest similarity -> index int32 [n][k], similarity fp32 [n][k],
+ * common int32 [n][k], best first; ordered by the exact fraction (c1 u2 against c2 u1; an empty union as 1 / 1), the smaller column
+ * on a tie; exclude_self = 1 skips column i for row i.  n x m is never stored.  1 <= k <= PD_FINGERPRINT_MAX_K, k <= m - exclude_self.
+ * pd_fingerprint_maxmin: the MaxMin diverse subset (Ashton et al. 2002): picks[0] = first, then the unpicked row whose largest
+ * similarity to the picked rows is smallest (the largest min of 1 - T), exact fractions, the smallest index on a tie -> picks int32
+ * [n_pick], max_similarity fp32 [n_pick] (that largest similarity; NaN for the first).  1 + 2 (n_pick - 1) launches, the next pick stays
+ * on the device.  ws: pd_fingerprint_maxmin_workspace_numel(n) int32.
+ * All three: 1 <= n_words <= PD_FINGERPRINT_MAX_WORDS; rows up to 65535 * 16 (else PD_ERR_UNSUPPORTED); a NULL or misaligned pointer,
+ * a count < 1, k, n_pick or first out of range, a short workspace: PD_ERR_ARG.  A rejected call launches nothing.               */
+#define PD_FINGERPRINT_MAX_RADIUS 4
+#define PD_FINGERPRINT_MAX_WORDS 128
+#define PD_FINGERPRINT_MAX_K 16
+int pd_morgan_fingerprint(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds,
+                          const unsigned* atom_invariants, unsigned* bits, unsigned* ids, unsigned char* kept, int* n_features,
+                          int* popcount, int n_ligands, int n_atoms, int n_bonds, int radius, int n_bits, void* stream);
+int pd_fingerprint_tanimoto(const unsigned* a, const unsigned* b, float* sim, int* common, int n, int m, int n_words, void* stream);
+int pd_fingerprint_nearest(const unsigned* a, const unsigned* b, int* index, float* similarity, int* common, int n, int m, int n_words,
+                           int k, int exclude_self, void* stream);
+int pd_fingerprint_maxmin_workspace_numel(int n);
+int pd_fingerprint_maxmin(const unsigned* bits, int* ws, int ws_numel, int* picks, float* max_similarity, int n, int n_words, int n_pick,
+                          int first, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

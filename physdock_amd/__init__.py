@@ -40,3 +40,4 @@ from .conformers import ConformerEnsemble  # noqa: F401  (distance-geometry conf
 from .sdfio import SdfTemplate, parse_sdf  # noqa: F401  (ligand poses as SD file records, formatted on the device, and their reader; csrc/sdf.hip)
 from .smiles import parse_smiles  # noqa: F401  (a SMILES reader on the host, without a dependency)
 from .ligand import Ligand, LigandLibrary  # noqa: F401  (ligands from SMILES to the reference's ligand feature blocks and a reference conformer; csrc/ligand_features.hip)
+from .fingerprints import MorganFingerprint  # noqa: F401  (circular fingerprints of a ligand library, Tanimoto search and MaxMin picking; csrc/fingerprint.hip)

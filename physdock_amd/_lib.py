@@ -311,6 +311,11 @@ def _declare(L):
     sig("pd_ligand_features", p, p, p, p, p, p, p, p, p, i, i, i, ll, p)                     # ABI 11, additive (ligand_features.hip)
     sig("pd_aromaticity", p, p, p, p, p, p, p, p, i, i, i, i, i, p)                          # ABI 11, additive (aromaticity.hip)
     sig("pd_bond_stereo", p, p, p, f, p, p, p, p, p, p, p, i, i, i, p)                       # ABI 11, additive (bond_stereo.hip)
+    sig("pd_morgan_fingerprint", p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, p)             # ABI 11, additive (fingerprint.hip)
+    sig("pd_fingerprint_tanimoto", p, p, p, p, i, i, i, p)
+    sig("pd_fingerprint_nearest", p, p, p, p, p, i, i, i, i, i, p)
+    sig("pd_fingerprint_maxmin_workspace_numel", i)
+    sig("pd_fingerprint_maxmin", p, p, i, p, p, i, i, i, i, p)
 
 
 def ptr(t):

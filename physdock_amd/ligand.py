@@ -413,6 +413,10 @@ class Ligand:
         """this ligand with every aromatic bond written single or double (`LigandLibrary.kekulized` of a library of one)"""
         return LigandLibrary([self]).kekulized(device).ligands[0]
 
+    def fingerprint(self, radius: int = 2, n_bits: int = 2048, atom_invariants=None, aromatize: bool = False, device=None):
+        """this ligand's circular fingerprint (`LigandLibrary.fingerprints` of a library of one): a `MorganFingerprint` of one row"""
+        return LigandLibrary([self]).fingerprints(radius, n_bits, atom_invariants, aromatize, device)
+
     def embed_reference(self, seed: int = 0, C: int = 32, device=None) -> Dict[str, torch.Tensor]:
         """The reference conformer: C distance-geometry conformers from `conformers.ideal_bounds(self)`
         (`ConformerEnsemble.from_tables(...).embed`), of which the accepted one with the smallest `err` - the lowest index on a tie - is
@@ -615,6 +619,17 @@ class LigandLibrary:
         if aromatize:
             out["aromaticity_status"] = perceived["status"]
         return out
+
+    def fingerprints(self, radius: int = 2, n_bits: int = 2048, atom_invariants=None, aromatize: bool = False, device=None):
+        """ONE launch of `pd_morgan_fingerprint` for the whole library -> an immutable `fingerprints.MorganFingerprint` (circular
+        fingerprints after Rogers & Hahn 2010, the package's own definition; see that module): `bits` [G, n_bits/32], `ids` and `kept`
+        [N, radius+1], `n_features` and `popcount` [G] on the device.  `radius` 0 .. 4, `n_bits` 512, 1024, 2048 or 4096;
+        `atom_invariants` (one unsigned 32-bit value per atom of the library) replaces the radius-0 identifiers.  `aromatize=True`:
+        `aromaticity("normalise")` first and the fingerprints of its tables - two launches, still no read-back - with
+        `aromaticity_status` beside; without it a Kekule and an aromatic spelling of one molecule differ.  ValueError on the host,
+        before any launch, for a bad `radius` or `n_bits` and for `atom_invariants` of another length."""
+        from .fingerprints import morgan_fingerprint
+        return morgan_fingerprint(self, radius, n_bits, atom_invariants, aromatize, device)
 
     def split(self, out: Dict[str, torch.Tensor], g: int) -> Dict[str, torch.Tensor]:
         """ligand g's part of a `features` result, as views under the reference's names (see `Ligand.features`)"""
