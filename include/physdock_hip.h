@@ -1475,6 +1475,71 @@ int pd_fingerprint_maxmin_workspace_numel(int n);
 int pd_fingerprint_maxmin(const unsigned* bits, int* ws, int ws_numel, int* picks, float* max_similarity, int n, int n_words, int n_pick,
                           int first, void* stream);
 
+/* ---- substructure search over a ligand library (substructure.hip; additive exports of ABI 11) -----------------------------------
+ * Which ligands contain a query pattern, how often and on which atoms?  The package's own definition, not RDKit's:
+ * tests/substructure_ref.py; physdock_amd/smarts.py reads the queries from a stated subset of SMARTS.
+ *
+ * The ligands are the tables of pd_ligand_features (or atoms / bonds as pd_aromaticity returned them).  Per atom: heavy degree,
+ * aromatic (flags & 1, or a bond with o2 = 3), ring (a bond of the atom is no bridge).  Per bond one of ten states, 2 * (0 single, 1
+ * double, 2 triple, 3 aromatic, 4 other) + (1 when the bond is no bridge).  The Q queries are packed as
+ *   q_atom_start int32 [Q+1]              prefix sums of the query atoms (1 .. PD_SUBSTRUCT_MAX_QUERY_ATOMS each)
+ *   q_op_start   int32 [n_query_atoms+1]  prefix sums of the ops of every query atom (1 .. PD_SUBSTRUCT_MAX_OPS each)
+ *   q_ops        int32 [n_ops]            code | argument << 8, postfix over a stack of truth values (PD_SUBSTRUCT_OP_*); the value
+ *                                         of an atom program is the top of the stack at its end
+ *   q_bond_start int32 [Q+1]              prefix sums of the query bonds (0 .. PD_SUBSTRUCT_MAX_QUERY_BONDS each)
+ *   q_bonds      int32 [n_query_bonds][4] (lo, hi, mask, -): lo < hi query atoms of that query, sorted by hi; bit s of mask allows
+ *                                         state s.  Every query atom but the first is the hi of a bond; its parent is the lowest lo
+ *   atom_classes int32 [n_atoms] or NULL  the word PD_SUBSTRUCT_OP_CLASS reads: bit k, inner pattern k anchors on this atom
+ * An embedding maps the query atoms injectively to the atoms of one ligand, every program true and every query bond on a ligand bond
+ * of an allowed state.  The search is depth-first in the order of the query atoms: atom 0 on every atom that passes its program,
+ * ascending (an anchor), atom k on the free neighbours of its parent's image that pass program k, ascending.  One candidate is one
+ * step; an anchor that has spent max_steps when a candidate is due stops with what it found.
+ *
+ * pd_substructure_search, one launch for G ligands x Q queries:
+ *   n_embeddings, n_unique, status int32 [G][Q]: the embeddings found (saturating at 2^31 - 1); those that are the lexicographically
+ *   smallest embedding onto their own atom set; 0 done, 2 a budget ran out (1 is reserved: not written)
+ *   atom_hits, anchor_hits uint32 [n_atoms][ceil(Q / 32)], bit q % 32 of word q / 32: the atom lies in an embedding of query q / is
+ *   the image of its atom 0
+ * pd_substructure_matches, for the one query `query` of `query_atoms` atoms: matches int32 [G][max_matches][query_atoms], the first
+ * embeddings of every ligand in the order above (unique_only = 1: the first unique ones) as atom indices local to the ligand, the
+ * rest -1; n_written int32 [G].
+ * Integers only, no atomics but a commuting LDS OR: bit-identical from launch to launch and independent of a ligand's place in the
+ * library.  A ligand or a query whose rows leave the arrays or break the limits is not written.  PD_ERR_ARG: a NULL or misaligned
+ * required pointer (bonds may be NULL when n_bonds == 0, q_bonds when n_query_bonds == 0, atom_classes always), n_ligands or
+ * n_queries < 1, n_atoms < n_ligands, max_steps < 0, table sizes that no n_queries patterns within the limits have, query outside
+ * 0 .. n_queries - 1, query_atoms outside 1 .. PD_SUBSTRUCT_MAX_QUERY_ATOMS, max_matches outside 1 .. PD_SUBSTRUCT_MAX_MATCHES,
+ * unique_only other than 0 or 1.  PD_ERR_UNSUPPORTED: n_ligands > 65535, n_queries > 1024, more atoms than that many ligands of the
+ * largest size.  A rejected call launches nothing.                                                                               */
+#define PD_SUBSTRUCT_MAX_QUERY_ATOMS 32
+#define PD_SUBSTRUCT_MAX_QUERY_BONDS 64
+#define PD_SUBSTRUCT_MAX_OPS 32
+#define PD_SUBSTRUCT_MAX_MATCHES 256
+#define PD_SUBSTRUCT_OP_TRUE 0               /* the argument is unused                                     */
+#define PD_SUBSTRUCT_OP_Z 1                  /* Z == argument                                              */
+#define PD_SUBSTRUCT_OP_AROMATIC 2
+#define PD_SUBSTRUCT_OP_ALIPHATIC 3
+#define PD_SUBSTRUCT_OP_DEGREE 4             /* heavy degree == argument                                   */
+#define PD_SUBSTRUCT_OP_H_COUNT 5
+#define PD_SUBSTRUCT_OP_CONNECTIVITY 6       /* degree + h_count == argument                               */
+#define PD_SUBSTRUCT_OP_RING 7
+#define PD_SUBSTRUCT_OP_CHARGE 8             /* charge == argument - 128                                   */
+#define PD_SUBSTRUCT_OP_CLASS 9              /* bit `argument` of the atom's class word                    */
+#define PD_SUBSTRUCT_OP_NOT 10
+#define PD_SUBSTRUCT_OP_AND 11
+#define PD_SUBSTRUCT_OP_OR 12
+#define PD_SUBSTRUCT_OP_ELEMENT_ALIPHATIC 13 /* Z == argument and not aromatic                             */
+#define PD_SUBSTRUCT_OP_ELEMENT_AROMATIC 14  /* Z == argument and aromatic                                 */
+int pd_substructure_search(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds, const int* q_atom_start,
+                           const int* q_op_start, const int* q_ops, const int* q_bond_start, const int* q_bonds,
+                           const int* atom_classes, int* n_embeddings, int* n_unique, int* status, unsigned* atom_hits,
+                           unsigned* anchor_hits, int n_ligands, int n_atoms, int n_bonds, int n_queries, int n_query_atoms, int n_ops,
+                           int n_query_bonds, int max_steps, void* stream);
+int pd_substructure_matches(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds, const int* q_atom_start,
+                            const int* q_op_start, const int* q_ops, const int* q_bond_start, const int* q_bonds,
+                            const int* atom_classes, int* matches, int* n_written, int n_ligands, int n_atoms, int n_bonds,
+                            int n_queries, int n_query_atoms, int n_ops, int n_query_bonds, int query, int query_atoms, int max_matches,
+                            int unique_only, int max_steps, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

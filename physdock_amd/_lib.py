@@ -316,6 +316,8 @@ def _declare(L):
     sig("pd_fingerprint_nearest", p, p, p, p, p, i, i, i, i, i, p)
     sig("pd_fingerprint_maxmin_workspace_numel", i)
     sig("pd_fingerprint_maxmin", p, p, i, p, p, i, i, i, i, p)
+    sig("pd_substructure_search", p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p)   # ABI 11, additive (substructure.hip)
+    sig("pd_substructure_matches", p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, i, p)
 
 
 def ptr(t):

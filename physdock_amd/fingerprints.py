@@ -25,9 +25,11 @@ does for two empty rows.  `nearest` and `maxmin` order by the exact fraction (in
 
 **Caveats.**  Kekule and aromatic spellings of one molecule differ (`c1ccccc1` against `C1=CC=CC=C1`) unless `aromatize=True`
 perceives aromaticity first, by the package's own rules.  No chirality in the invariants (the `@` code depends on the written
-neighbour order), no count vectors (ECFC), no built-in FCFP perception.  Similarity 1 with equal atom counts is necessary for two
+neighbour order), no count vectors (ECFC); the pharmacophore classes of an FCFP-like variant come from
+`substructure.pharmacophore_invariants`, an int32 device tensor that `atom_invariants` takes without a read-back.  Similarity 1 with equal atom counts is necessary for two
 ligands to be the same molecule, not sufficient: this is no canonical key.  Limits: 128 atoms and 512 bonds per ligand, 65535
-ligands per launch, 1 <= k <= 16.  Out of scope: RDKit parity, substructure search, `redock`.
+ligands per launch, 1 <= k <= 16.  Out of scope: RDKit parity, `redock`; substructure search is `substructure.py`
+(`LigandLibrary.substructure`).
 
 Device tensors hold the uint32 words as int32 (the same bits; `.view(torch.uint32)` is free): torch computes on int32."""
 from __future__ import annotations
@@ -55,9 +57,14 @@ def _check_spec(radius, n_bits, what):
 
 
 def _invariants(atom_invariants, n_atoms, what) -> Optional[np.ndarray]:
-    """`atom_invariants` as uint32 [n_atoms] held in int32, or None"""
+    """`atom_invariants` as uint32 [n_atoms] held in int32 (a numpy array, or the int32 device tensor that was given), or None"""
     if atom_invariants is None:
         return None
+    if isinstance(atom_invariants, torch.Tensor) and atom_invariants.is_cuda and atom_invariants.dtype == torch.int32:
+        if atom_invariants.dim() != 1 or atom_invariants.shape[0] != n_atoms:
+            raise ValueError(f"{what}: atom_invariants of shape {tuple(atom_invariants.shape)}; one value per atom of the library "
+                             f"({n_atoms},)")
+        return atom_invariants.detach().contiguous()         # the uint32 values as int32 on the device: taken without a read-back
     if isinstance(atom_invariants, torch.Tensor):
         atom_invariants = atom_invariants.detach().cpu().numpy()
     v = np.asarray(atom_invariants)
@@ -87,7 +94,12 @@ def morgan_fingerprint(library, radius=2, n_bits=2048, atom_invariants=None, aro
     new = lambda shape, dtype: torch.empty(shape, device=device, dtype=dtype)
     bits, ids, kept = new((G, W), torch.int32), new((N, radius + 1), torch.int32), new((N, radius + 1), torch.uint8)
     n_features, popcount = new((G,), torch.int32), new((G,), torch.int32)
-    inv_t = torch.from_numpy(inv.copy()).to(device) if inv is not None else None
+    if isinstance(inv, torch.Tensor):
+        if inv.device != device:
+            raise ValueError(f"{what}: atom_invariants on {inv.device}, the fingerprints on {device}")
+        inv_t = inv
+    else:
+        inv_t = torch.from_numpy(inv.copy()).to(device) if inv is not None else None
     L_ = ops._lib.init()
     with torch.cuda.device(device):
         ops.check(L_.pd_morgan_fingerprint(ops.ptr(t["atom_start"]), ops.ptr(t["bond_start"]), ops.ptr(t["atoms"]),

@@ -417,6 +417,10 @@ class Ligand:
         """this ligand's circular fingerprint (`LigandLibrary.fingerprints` of a library of one): a `MorganFingerprint` of one row"""
         return LigandLibrary([self]).fingerprints(radius, n_bits, atom_invariants, aromatize, device)
 
+    def substructure(self, queries, aromatize: bool = False, max_steps: int = 65536, device=None):
+        """the queries on this ligand (`LigandLibrary.substructure` of a library of one): a `SubstructureMatches` with G = 1"""
+        return LigandLibrary([self]).substructure(queries, aromatize, max_steps, device)
+
     def embed_reference(self, seed: int = 0, C: int = 32, device=None) -> Dict[str, torch.Tensor]:
         """The reference conformer: C distance-geometry conformers from `conformers.ideal_bounds(self)`
         (`ConformerEnsemble.from_tables(...).embed`), of which the accepted one with the smallest `err` - the lowest index on a tie - is
@@ -630,6 +634,17 @@ class LigandLibrary:
         before any launch, for a bad `radius` or `n_bits` and for `atom_invariants` of another length."""
         from .fingerprints import morgan_fingerprint
         return morgan_fingerprint(self, radius, n_bits, atom_invariants, aromatize, device)
+
+    def substructure(self, queries, aromatize: bool = False, max_steps: int = 65536, device=None):
+        """Which ligands contain the queries, how often and on which atoms?  ONE launch of `pd_substructure_search` for the whole
+        library x all queries -> an immutable `substructure.SubstructureMatches` on the device (see that module for the definition,
+        the package's own): `n_embeddings`, `n_unique`, `status` [G, Q] and the bit rows `atom_hits`, `anchor_hits` [N, ceil(Q/32)].
+        `queries`: a `substructure.SubstructureQueries`, or SMARTS strings (the subset of `smarts.parse_smarts`).  `max_steps` bounds
+        the candidates tried per (query, ligand, anchor); status 2 where it ran out.  `aromatize=True`: `aromaticity("normalise")`
+        first and the search of its tables; a `$()` in a query adds one launch for the inner patterns.  Nothing is read back.
+        ValueError on the host, before any launch, for a query that is not read, too many queries and a bad `max_steps`."""
+        from .substructure import substructure_search
+        return substructure_search(self, queries, aromatize, max_steps, device)
 
     def split(self, out: Dict[str, torch.Tensor], g: int) -> Dict[str, torch.Tensor]:
         """ligand g's part of a `features` result, as views under the reference's names (see `Ligand.features`)"""
