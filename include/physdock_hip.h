@@ -1540,6 +1540,47 @@ int pd_substructure_matches(const int* atom_start, const int* bond_start, const 
                             int n_queries, int n_query_atoms, int n_ops, int n_query_bonds, int query, int query_atoms, int max_matches,
                             int unique_only, int max_steps, void* stream);
 
+/* ---- canonical numbering, certificate and identity key of ligand graphs (canonical.hip; additive exports of ABI 11) ---------------
+ * Are two records the same molecule, and what is its one spelling?  The package's own definition, not InChI and not RDKit's
+ * canonical SMILES: tests/canonical_ref.py.  push and fmix are the hash functions of pd_morgan_fingerprint.
+ *
+ * The ligands are the tables of pd_ligand_features (or atoms / bonds as pd_aromaticity returned them) and
+ *   isotopes      int32 [n_atoms]         0 .. 65535
+ *   chiral_order  int32 [n_atoms][4]      of a marked atom its neighbours in the written order, local to the ligand, -1 a hydrogen,
+ *                                         padded with -2; an order of fewer than 3 or more than 4 entries is an empty row
+ *   stereo_start  int32 [G+1], stereo int32 [n_stereo][8]   rows (a, b, c, d, kind, a2, d2, -) of smiles.parse_smiles, up to
+ *                                         PD_CANONICAL_MAX_STEREO per ligand
+ *   cert_start    int32 [G+1]             prefix sums of 3 + 2 n + m + s words per ligand
+ * inv(a) = (Z, charge, h_count, isotope, flags & 1).  A colouring gives every atom the number of atoms with a strictly smaller key;
+ * the root colours by inv; one round colours by (colour, sum mod 2^32 over the bonds (a, b) of push(push(0, o2), colour[b])); refine
+ * repeats rounds until the number of colours stops growing; individualise(v) colours by (colour, a != v) and refines.  Depth-first
+ * from the refined root: at a colouring that is not discrete the members of the cell of the smallest colour with more than one atom
+ * are tried in ascending index, except a terminal atom when an earlier member is terminal on the same neighbour with the same o2.
+ * Every refine is one step; a step that is due when max_steps are spent ends the search with status 2.  A discrete colouring is a
+ * leaf; its certificate is the words n, m; per label Z | (charge + 128) << 8 | h_count << 16 | aromatic << 24 and isotope | parity <<
+ * 16; the bonds lo << 16 | hi << 8 | o2 in labels, ascending; s; the stereo rows b << 23 | c << 16 | a << 9 | d << 2 | kind in labels
+ * (b < c, a and d the lowest-label substituents, kind flipped for every end that names the other one), ascending.  parity: 0 without
+ * a mark, with h_count >= 2, an empty chiral_order row or two terminal neighbours of equal inv and o2; else the mark (1 @, 2 @@),
+ * exchanged when the row in labels has an odd number of inversions.  The smallest certificate wins, the first found on a tie.
+ *   labels, order int32 [n_atoms]  (order the inverse of labels within the ligand; the input order when no leaf was reached)
+ *   classes int32 [n_atoms]        the refined root colouring: topological symmetry classes
+ *   cert uint32 [n_cert_words], key uint32 [G][2] (push chained over the certificate from the seeds 0 and 1)
+ *   status (0 done, 2 out of steps; 1 is reserved), steps, leaves, canonical (1 exactly when status is 0) int32 [G]
+ * pd_canonical_first: first_of int32 [G], the smallest j < g with status 0, an equal key and a certificate equal word for word, else
+ * g; a ligand whose status is not 0 is its own first and nobody else's.
+ * Integers only, no atomics: bit-identical from launch to launch and independent of a ligand's place in the library.  A ligand whose
+ * rows leave the arrays or break the limits is not written.  PD_ERR_ARG: a NULL or misaligned required pointer (bonds may be NULL
+ * when n_bonds == 0, stereo when n_stereo == 0), n_ligands < 1, n_atoms < n_ligands, max_steps < 1, n_cert_words other than
+ * 3 n_ligands + 2 n_atoms + n_bonds + n_stereo.  PD_ERR_UNSUPPORTED: n_ligands > 65535, more atoms than that many ligands of the
+ * largest size, 2^31 words or more.  A rejected call launches nothing.                                                         */
+#define PD_CANONICAL_MAX_STEREO 64
+int pd_canonical_form(const int* atom_start, const int* bond_start, const int* atoms, const int* bonds, const int* isotopes,
+                      const int* chiral_order, const int* stereo_start, const int* stereo, const int* cert_start, int* labels,
+                      int* order, int* classes, unsigned* cert, unsigned* key, int* status, int* steps, int* leaves, int* canonical,
+                      int n_ligands, int n_atoms, int n_bonds, int n_stereo, long long n_cert_words, int max_steps, void* stream);
+int pd_canonical_first(const unsigned* key, const int* status, const int* cert_start, const unsigned* cert, int* first_of,
+                       int n_ligands, long long n_cert_words, void* stream);
+
 /* ---- hipGraph helpers (api.hip): capture the host-deterministic step loop once, replay it */
 int pd_graph_begin(void* stream);
 int pd_graph_end(void* stream, void** exec_out);

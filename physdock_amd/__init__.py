@@ -41,5 +41,6 @@ from .sdfio import SdfTemplate, parse_sdf  # noqa: F401  (ligand poses as SD fil
 from .smiles import parse_smiles  # noqa: F401  (a SMILES reader on the host, without a dependency)
 from .ligand import Ligand, LigandLibrary  # noqa: F401  (ligands from SMILES to the reference's ligand feature blocks and a reference conformer; csrc/ligand_features.hip)
 from .fingerprints import MorganFingerprint  # noqa: F401  (circular fingerprints of a ligand library, Tanimoto search and MaxMin picking; csrc/fingerprint.hip)
+from .canonical import CanonicalForm, write_smiles  # noqa: F401  (canonical numbering, identity key and canonical SMILES of a ligand library; csrc/canonical.hip)
 from .substructure import (SmartsPattern, SubstructureMatches, SubstructureQueries, parse_smarts,  # noqa: F401
                            pharmacophore_invariants)  # (SMARTS queries over a ligand library, matched atoms, pharmacophore classes; csrc/substructure.hip)

@@ -318,6 +318,8 @@ def _declare(L):
     sig("pd_fingerprint_maxmin", p, p, i, p, p, i, i, i, i, p)
     sig("pd_substructure_search", p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p)   # ABI 11, additive (substructure.hip)
     sig("pd_substructure_matches", p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, i, i, i, i, p)
+    sig("pd_canonical_form", p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, i, i, i, i, ll, i, p)     # ABI 11, additive (canonical.hip)
+    sig("pd_canonical_first", p, p, p, p, p, i, ll, p)
 
 
 def ptr(t):

@@ -29,6 +29,7 @@
 // maxmin: per pick, one launch raises every row's largest similarity to the picked rows against the newest pick (read from device
 // memory) and leaves each block's best candidate, one launch of a single block selects among them.  Nothing is read back.
 #include "common.h"
+#include "hash32.h"
 #include "mask128.h"
 #include "physdock_hip.h"
 
@@ -44,12 +45,6 @@ constexpr int FP_MAX_K = PD_FINGERPRINT_MAX_K;
 constexpr int FP_TILE = 16;
 constexpr int FP_MAX_ROWS = 65535 * FP_TILE;           // the tile grid's second dimension
 constexpr unsigned char FP_SKIP = 0xFF;
-
-__device__ __forceinline__ unsigned fp_fmix(unsigned h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-__device__ __forceinline__ unsigned fp_push(unsigned h, unsigned v) { return fp_fmix(h * 0x01000193u + v + 0x9E3779B9u); }
 
 __global__ __launch_bounds__(256) void morgan_kernel(const int* __restrict__ atom_start, const int* __restrict__ bond_start,
                                                     const int* __restrict__ atoms, const int* __restrict__ bonds,

@@ -421,6 +421,25 @@ class Ligand:
         """the queries on this ligand (`LigandLibrary.substructure` of a library of one): a `SubstructureMatches` with G = 1"""
         return LigandLibrary([self]).substructure(queries, aromatize, max_steps, device)
 
+    def canonical(self, aromatize: bool = False, max_steps: int = 65536, device=None):
+        """this ligand's canonical form (`LigandLibrary.canonical` of a library of one): a `CanonicalForm` with G = 1"""
+        return LigandLibrary([self]).canonical(aromatize, max_steps, device)
+
+    def canonical_smiles(self, aromatize: bool = False, max_steps: int = 65536, device=None) -> str:
+        """the one spelling of this molecule (`canonical().smiles()[0]`); ValueError when the search ran out of `max_steps`"""
+        form = self.canonical(aromatize, max_steps, device)
+        if not int(form.canonical[0]):                                                  # (a read-back)
+            raise ValueError(f"Ligand.canonical_smiles: the search ran out of {int(max_steps)} steps: no canonical numbering")
+        return form.smiles()[0]
+
+    def identity_key(self, aromatize: bool = False, max_steps: int = 65536, device=None) -> int:
+        """the 64-bit key of this molecule's certificate, k0 << 32 | k1 (a read-back); ValueError when the search ran out of steps"""
+        form = self.canonical(aromatize, max_steps, device)
+        if not int(form.canonical[0]):
+            raise ValueError(f"Ligand.identity_key: the search ran out of {int(max_steps)} steps: no canonical numbering")
+        k0, k1 = (int(v) & 0xFFFFFFFF for v in form.key[0].tolist())
+        return k0 << 32 | k1
+
     def embed_reference(self, seed: int = 0, C: int = 32, device=None) -> Dict[str, torch.Tensor]:
         """The reference conformer: C distance-geometry conformers from `conformers.ideal_bounds(self)`
         (`ConformerEnsemble.from_tables(...).embed`), of which the accepted one with the smallest `err` - the lowest index on a tie - is
@@ -645,6 +664,16 @@ class LigandLibrary:
         ValueError on the host, before any launch, for a query that is not read, too many queries and a bad `max_steps`."""
         from .substructure import substructure_search
         return substructure_search(self, queries, aromatize, max_steps, device)
+
+    def canonical(self, aromatize: bool = False, max_steps: int = 65536, device=None):
+        """Which ligands are the same molecule, and what is each one's one spelling?  ONE launch of `pd_canonical_form` for the whole
+        library -> an immutable `canonical.CanonicalForm` on the device (see that module for the definition, the package's own):
+        `labels`, `order`, `classes` [N], the certificate words `cert`, `key` [G, 2], `status`, `steps`, `leaves`, `canonical` [G];
+        `first_of`, `unique()`, `same(i, j)`, `smiles()` and `renumbered()` from there.  `max_steps` bounds the refinements per ligand;
+        status 2 where it ran out.  `aromatize=True`: `aromaticity("normalise")` first and the form of its tables.  Nothing is read
+        back.  ValueError on the host, before any launch, for a bad `max_steps`."""
+        from .canonical import canonical_form
+        return canonical_form(self, aromatize, max_steps, device)
 
     def split(self, out: Dict[str, torch.Tensor], g: int) -> Dict[str, torch.Tensor]:
         """ligand g's part of a `features` result, as views under the reference's names (see `Ligand.features`)"""
